@@ -14,7 +14,11 @@ ranks share nothing on the data path:
   --scaling strong the `--tracks` tracks are split over the ranks.
 value = frames of all ranks / max-over-ranks time of the K timed steps.
 
-Prints ONE JSON line on rank 0.  Parity: every GPU image of the batch is
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+K steps, writes `--dump-outputs DIR` if asked and prints the headline
+(metric, value, ms_per_step, kernel_ms, step_hbm): nothing else touches the
+GPU.  Everything below is behind `--full`, which adds it to the same line
+after the headline's steps.  Parity: every GPU image of the batch is
 byte-compared with the CPU port (oracle/flac_port.c, pinned to the reference)
 and a sample with the reference encoder itself (oracle/_ref/flacenc, built
 from the reference's own C sources) when that build is present; the decode
@@ -67,6 +71,16 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: parity with the CPU port and the reference "
+                         "encoder, CPU baselines, rooflines, and the decode, convert, "
+                         "ReplayGain, host-to-host, resample, chain, track2track, narrow-batch, "
+                         "strong-scaling and planning legs (the --no-* and per-leg options "
+                         "below apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left its caller (per-track image "
+                         "sizes, offsets, MD5s and CRC-32s, and a fixed seeded sample of every "
+                         "image's bytes) as DIR/<name>.npy")
     ap.add_argument("--inflight", type=int, default=12,
                     help="encode batches in flight (2..32; from 4 on the MD5 chains are "
                          "rolled, atg_engine_set_inflight)")
@@ -1463,6 +1477,45 @@ def narrow_leg(args, torch, dist, world, device, eng, opts, pcm, tracks, out_ful
                     "images compared with the full batch's (the same tracks' bytes)"}
 
 
+DUMP_SAMPLE_BYTES = 48 << 20   # the image sample's share of --dump-outputs' 64 MB
+
+
+def dump_outputs(dirname, out, res):
+    """--dump-outputs: what the last timed step handed its caller -- the
+    per-track results and the .flac images in `out` -- as <name>.npy:
+      track_status, track_out_offset, track_bytes, track_n_frames,
+      track_min_frame_bytes, track_max_frame_bytes   float64 [tracks]
+      track_md5          float32 [tracks, 16]  the STREAMINFO MD5 bytes
+      track_image_crc32  float64 [tracks]      CRC-32 of the whole image
+      image_sample       float32 [tracks, K]   image bytes at K fixed offsets
+    image_sample[t, j] is byte (pos[j] mod track_bytes[t]) of track t's
+    image, pos drawn once from a seeded generator: the same positions in
+    every run, so two builds compare output for output; the CRC covers the
+    bytes the sample leaves out."""
+    import zlib
+    os.makedirs(dirname, exist_ok=True)
+    n = len(res)
+    end = max(int(r.out_offset + r.bytes) for r in res)
+    host = out[:end].cpu().numpy()
+    k = max(1, min(8192, DUMP_SAMPLE_BYTES // 4 // max(1, n)))
+    pos = np.random.RandomState(0xD0C5).randint(0, 1 << 30, size=k).astype(np.int64)
+    sample = np.zeros((n, k), dtype=np.float32)
+    crc = np.zeros(n, dtype=np.float64)
+    for t, r in enumerate(res):
+        img = host[int(r.out_offset):int(r.out_offset + r.bytes)]
+        crc[t] = zlib.crc32(img)
+        if len(img):
+            sample[t] = img[pos % len(img)]
+    arrays = {"image_sample": sample, "track_image_crc32": crc,
+              "track_md5": np.frombuffer(b"".join(bytes(r.md5) for r in res), dtype=np.uint8)
+                             .reshape(n, 16).astype(np.float32)}
+    for f in ("status", "out_offset", "bytes", "n_frames", "min_frame_bytes",
+              "max_frame_bytes"):
+        arrays["track_" + f] = np.array([float(getattr(r, f)) for r in res], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
@@ -1547,8 +1600,57 @@ def main(argv=None):
     if world > 1:
         elapsed = reduce_max(torch, dist, elapsed, device)
     out = outs[(args.steps - 1) % depth]
-    # the batches below write their own buffers: `out` holds the images the
-    # parity check and the decode leg read
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, res)
+    kt = {k: v / args.steps for k, v in kt_sum.items()}
+    out_bytes = sum(int(r.bytes) for r in res)
+    frame_bytes = out_bytes - HEADER_BYTES * len(res)
+    total_frames = n_frames * args.steps
+    if world > 1:
+        total_frames = reduce_sum(torch, dist, total_frames, device)
+    step_alg = n_tracks * n_samples * 2 * 2 + out_bytes
+    # the headline: all a plain run reports (the K timed steps above and
+    # figures that follow from them without another launch)
+    line = {
+        "metric": METRIC,
+        "value": round(total_frames / elapsed, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "int32 residuals / f64 LPC analysis (s16 PCM in)",
+        "data": "synthetic (seeded sine+noise, 5% white noise, 2% silent tracks)",
+        "config": {"workload": "FLAC-8 batch encode, %d tracks x %d frames x 4096 samples "
+                               "per GPU, 44.1 kHz 16-bit stereo, PCM and .flac images in HBM"
+                               % (n_tracks, args.frames),
+                   "tracks_per_gpu": n_tracks, "frames_per_track": args.frames,
+                   "block_size": 4096, "preset": "FLAC-8 (-l 12 -m -e -R 6)",
+                   "parallelism": "dp%d (tracks sharded per GPU, %s scaling)"
+                                  % (world, args.scaling)},
+        "step_hbm": {"alg_bytes_per_step": step_alg,
+                     "achieved": round(step_alg / (elapsed / args.steps) / 1e9, 2),
+                     "frac": round(step_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5)},
+        "kernel_ms": {k: round(v, 4) for k, v in kt.items()},
+        "compressed_bytes_per_frame": round(frame_bytes / n_frames, 1),
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        # every handle closed here, in order, not from interpreter teardown
+        # 
+        del outs
+        eng.close()
+        _atgpu.close_all()
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+    # ---- --full: everything below.  The batches below write their own
+    # buffers: `out` holds the images the parity check and the decode leg read
     outs = [torch.empty(out_cap, dtype=torch.uint8, device=device) for _ in range(depth)]
 
     def timed(tbl, steps):
@@ -1642,12 +1744,6 @@ def main(argv=None):
                          "and their upload are redone every step"}
     del tables
     del outs
-    kt = {k: v / args.steps for k, v in kt_sum.items()}
-    out_bytes = sum(int(r.bytes) for r in res)
-    frame_bytes = out_bytes - HEADER_BYTES * len(res)
-    total_frames = n_frames * args.steps
-    if world > 1:
-        total_frames = reduce_sum(torch, dist, total_frames, device)
 
     share, share_info = cpu_share()
     threads = args.cpu_threads or share
@@ -1704,7 +1800,6 @@ def main(argv=None):
             dist.destroy_process_group()
         return 0
 
-    value = total_frames / elapsed
     # ---- rooflines.  Algorithmic bytes per launch:
     # every kernel that reads the batch reads its PCM once (16,384 B per
     # 4096-sample stereo frame); the packer also writes the compressed frames
@@ -1764,10 +1859,6 @@ def main(argv=None):
         valu["issued_wave_insts_per_launch"] = per_launch
         valu["issue_frac"] = round(per_launch / (sub_ms / 1e3) / VALU_PEAK_WAVE_INSTS, 4)
         valu["pmc_source"] = pmc.get("source")
-    step_alg = pcm_bytes + out_bytes
-    step_hbm = {"alg_bytes_per_step": step_alg,
-                "achieved": round(step_alg / (elapsed / args.steps) / 1e9, 2),
-                "frac": round(step_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5)}
 
     # ---- CPU baselines on this host's cores
     cpu = None
@@ -1818,34 +1909,12 @@ def main(argv=None):
         if rg is not None:
             verify_replaygain(rg, rg_res, pcm_host, n_tracks, n_samples, threads)
 
-    line = {
-        "metric": METRIC,
-        "value": round(value, 1),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+    line.update({
         # SURVEY 8(d)'s timer: pinned host PCM in, host images out, PCIe
         # transfers inside the clock (the host_to_host leg, same batch)
         "value_host_to_host": host.get("value") if isinstance(host, dict) else None,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "int32 residuals / f64 LPC analysis (s16 PCM in)",
-        "data": "synthetic (seeded sine+noise, 5% white noise, 2% silent tracks)",
-        "config": {"workload": "FLAC-8 batch encode, %d tracks x %d frames x 4096 samples "
-                               "per GPU, 44.1 kHz 16-bit stereo, PCM and .flac images in HBM"
-                               % (n_tracks, args.frames),
-                   "tracks_per_gpu": n_tracks, "frames_per_track": args.frames,
-                   "block_size": 4096, "preset": "FLAC-8 (-l 12 -m -e -R 6)",
-                   "parallelism": "dp%d (tracks sharded per GPU, %s scaling)"
-                                  % (world, args.scaling)},
         "roofline": roofline,
         "roofline_valu": valu,
-        "step_hbm": step_hbm,
-        "kernel_ms": {k: round(v, 4) for k, v in kt.items()},
-        "compressed_bytes_per_frame": round(frame_bytes / n_frames, 1),
         "verified_vs_oracle": verified,
         "cpu_baseline": cpu,
         "decode": decode,
@@ -1859,7 +1928,7 @@ def main(argv=None):
         "strong_scaling": strong if world > 1 else {"note": "1 GPU: the same batch as value"},
         "narrow_batches": narrow,
         "plan_per_batch": plan_miss,
-    }
+    })
     print(json.dumps(line), flush=True)
     # every handle closed here, in order, not from interpreter teardown
     # 

@@ -13,7 +13,7 @@ cd "$R"
 for k in 1 2; do
   for cfg in "${CFGS[@]}"; do
     set -- $cfg
-    timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-verify \
+    timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-verify \
         --no-host --no-t2t --no-rg4 --narrow= --no-decode --chain-decoders $1 \
         --chain-inflight $2 > "$OUT/chain_d$1_f$2_$k.log" 2>&1
   done

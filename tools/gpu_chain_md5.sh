@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$R"
 for k in 1 2; do
   for m in auto gpu; do
-    timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-verify \
+    timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-verify \
         --no-host --no-t2t --no-rg4 --narrow= --no-decode --chain-md5 $m > "$OUT/chain_${m}_$k.log" 2>&1
   done
 done

@@ -3,7 +3,7 @@
 # (expgpu/libatgpu_<v>.so; "base" = the product library)
 set -e
 mkdir -p gpurun_out/legs
-B="python -u bench.py --no-cpu-baseline --no-verify --no-chain --no-t2t --no-rg4 --narrow= --no-host"
+B="python -u bench.py --full --no-cpu-baseline --no-verify --no-chain --no-t2t --no-rg4 --narrow= --no-host"
 for v in "$@"; do
   if [ "$v" = base ]; then L=$PWD/python-audio-tools_amd/audiotools/libatgpu.so; else L=$PWD/expgpu/libatgpu_$v.so; fi
   ATGPU_LIB=$L timeout -k 10 300 $B > gpurun_out/legs/$v.log 2>&1

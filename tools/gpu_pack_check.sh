@@ -12,6 +12,6 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 120 --timeout-method threa
     tests/test_gpu_flac.py tests/test_gpu_flac_big.py tests/test_gpu_k2_packed.py \
     tests/test_gpu_chain.py > "$OUT/pytest.log" 2>&1
 for k in 1 2; do
-    timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host \
+    timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host \
         --no-t2t --no-rg4 --narrow= > "$OUT/chain$k.log" 2>&1
 done

@@ -3,7 +3,7 @@ set -e
 mkdir -p gpurun_out/rgl
 for v in "$@"; do
   if [ "$v" = base ]; then L=$PWD/python-audio-tools_amd/audiotools/libatgpu.so; else L=$PWD/expgpu/libatgpu_$v.so; fi
-  ATGPU_LIB=$L timeout -k 10 400 python -u bench.py --no-chain --no-t2t \
+  ATGPU_LIB=$L timeout -k 10 400 python -u bench.py --full --no-chain --no-t2t \
     --narrow= --no-host > gpurun_out/rgl/$v.log 2>&1
   python3 -c "import json,sys
 for l in open(sys.argv[1]):
