@@ -783,6 +783,145 @@ int atg_alac_decoder_kernel_times(atg_alac_decoder *dec, const char **names, flo
                                   int cap);
 
 /* ------------------------------------------------------------------ */
+/* True Audio (TTA1) encoder.  Replaces the body of the reference's     */
+/* audiotools.encoders.encode_tta (src/encoders/tta.c:31-114 ->         */
+/* encode_frame :144-259) for a batch of tracks of one format.  Every   */
+/* block of sample_rate * 256 / 245 PCM frames (or every explicit       */
+/* atg_track frame size) becomes one TTA frame: the Rice payload and    */
+/* its CRC-32.  The output holds frames only; the 22-byte header and    */
+/* the seektable are host work (audiotools/tta.py).  bits_per_sample    */
+/* 8, 16 or 24.  There are no encoder options.                          */
+/* ------------------------------------------------------------------ */
+/* Per-track result: the track's frames are `bytes` long at out +
+   out_offset; frame_bytes[first_frame .. first_frame + n_frames) are the
+   frame sizes including each frame's CRC: the seektable body and the list
+   encode_tta returns. */
+typedef struct {
+    uint64_t out_offset;
+    uint64_t bytes;
+    uint64_t pcm_frames;
+    uint32_t first_frame;
+    uint32_t n_frames;
+    int32_t status;
+    uint32_t reserved;
+} atg_tta_track_result;
+
+typedef struct atg_tta_encoder atg_tta_encoder;
+
+const char *atg_tta_last_error(void);
+atg_status atg_tta_encoder_create(int device, atg_tta_encoder **out);
+void atg_tta_encoder_destroy(atg_tta_encoder *enc);
+/* PCM and output in device memory (d_out 4-byte aligned).  A TTA frame has
+   no useful size bound before it is encoded (a loud sample after a quiet
+   passage costs a unary run as long as its value), so there is no
+   batch_bounds call: the code lengths are computed first, *needed (may be
+   NULL) receives the bytes the batch takes, and when that exceeds out_cap
+   the call returns ATG_ERR_CAPACITY with nothing written to d_out: call
+   again with a buffer of *needed bytes.  *needed counts output bytes
+   only.  frame_bytes (host, frame_bytes_cap entries, may be NULL)
+   receives the frame sizes; fewer entries than the batch has frames
+   (ceil(pcm_frames / block) per track, or its explicit frame sizes) is
+   ATG_ERR_INVALID. */
+atg_status atg_tta_encode_device(atg_tta_encoder *enc, const void *d_pcm, atg_pcm_format format,
+                                 const atg_track *tracks, uint32_t n_tracks, uint32_t channels,
+                                 uint32_t bits_per_sample, uint32_t sample_rate, void *d_out,
+                                 uint64_t out_cap, atg_tta_track_result *results,
+                                 uint32_t *frame_bytes, uint64_t frame_bytes_cap,
+                                 uint64_t *needed);
+/* the same for host buffers (staged through the device) */
+atg_status atg_tta_encode_host(atg_tta_encoder *enc, const void *pcm, atg_pcm_format format,
+                               const atg_track *tracks, uint32_t n_tracks, uint32_t channels,
+                               uint32_t bits_per_sample, uint32_t sample_rate, uint8_t *out,
+                               uint64_t out_cap, atg_tta_track_result *results,
+                               uint32_t *frame_bytes, uint64_t frame_bytes_cap,
+                               uint64_t *needed);
+/* the last encode: "tta_chain", "tta_size" (from the chain's end to the
+   pack's start: the totals copied to the host, the extents, the clearing of
+   the output), "tta_pack", "tta_crc" and "tta_total", first kernel to last */
+int atg_tta_encoder_kernel_times(atg_tta_encoder *enc, const char **names, float *ms, int cap);
+
+/* ------------------------------------------------------------------ */
+/* True Audio decoder.  Replaces the reference's                        */
+/* audiotools.decoders.TTADecoder (src/decoders/tta.c) for a batch of   */
+/* images.                                                             */
+/* ------------------------------------------------------------------ */
+/* status values: the reference's decoder status enum (decoders/tta.h),
+   plus the frame-read failure TTADecoder_read reports on its own */
+enum {
+    ATG_TD_OK = 0,
+    ATG_TD_IO_ERROR = 1,           /* IOError "I/O error reading header" /
+                                      "... seektable" / "... frame" */
+    ATG_TD_CRC_MISMATCH = 2,       /* ValueError "CRC error reading header" /
+                                      "... seektable", "CRC mismatch reading frame" */
+    ATG_TD_INVALID_SIGNATURE = 3,  /* ValueError "invalid header signature" */
+    ATG_TD_UNSUPPORTED_FORMAT = 4, /* ValueError "unsupported TTA format" */
+    ATG_TD_FRAME_READ = 5          /* ValueError "I/O error during frame read":
+                                      the Rice stream ran past its payload */
+};
+
+typedef struct {
+    uint32_t channels, bits_per_sample, sample_rate, total_pcm_frames;
+    uint32_t block_size;       /* sample_rate * 256 / 245 */
+    uint32_t total_tta_frames; /* ceil(total_pcm_frames / block_size) */
+    uint64_t id3_bytes;        /* ID3v2 comments skipped in front of "TTA1" */
+    uint64_t frames_offset;    /* byte (from the image start) of the first frame */
+    uint32_t stage;            /* how far parsing got: 0 header, 1 seektable, 2 done */
+    uint32_t reserved;
+} atg_tta_info;
+
+/* read_header + read_seektable over an in-memory image (host): returns an
+   ATG_TD_* status, info->stage telling a header failure from a seektable
+   failure.  Both CRCs are checked; ID3v2 comments in front are skipped.
+   The seektable's frame sizes are copied to frame_bytes (cap entries, may
+   be NULL); *n_frame_bytes receives their number. */
+int atg_tta_read_info(const uint8_t *data, uint64_t len, atg_tta_info *info,
+                      uint32_t *frame_bytes, uint32_t cap, uint32_t *n_frame_bytes);
+
+/* One stream of a decode batch: the image at data[data_offset, data_offset +
+   data_bytes) (4-byte aligned); reading starts at byte `start` of the image
+   (frames_offset, or a later frame's offset) with `remaining` PCM frames
+   left; frame_bytes are the seektable entries from that frame on. */
+typedef struct {
+    uint64_t data_offset, data_bytes, start, remaining;
+    uint32_t channels, bits_per_sample, block_size, reserved;
+    const uint32_t *frame_bytes;
+    uint64_t n_frame_bytes;
+} atg_tta_dec_track;
+
+/* n_frames frames = pcm_frames PCM frames (interleaved int32 at sample
+   index sample_offset of the batch output) decoded, then `status` ends the
+   stream: 0 when `remaining` was reached, else the status of the track's
+   frame number n_frames (the first bad one). */
+typedef struct {
+    uint64_t sample_offset;
+    uint64_t pcm_frames;
+    uint32_t first_frame;
+    uint32_t n_frames;
+    int32_t status;
+    uint32_t channels;
+} atg_tta_dec_result;
+
+typedef struct atg_tta_decoder atg_tta_decoder;
+
+const char *atg_tta_decoder_last_error(void);
+atg_status atg_tta_decoder_create(int device, atg_tta_decoder **out);
+void atg_tta_decoder_destroy(atg_tta_decoder *dec);
+atg_status atg_tta_decode_host(atg_tta_decoder *dec, const uint8_t *data, uint64_t len,
+                               const atg_tta_dec_track *tracks, uint32_t n_tracks,
+                               atg_tta_dec_result *results, uint64_t *total_samples);
+/* the last decode's PCM (total_samples int32) */
+atg_status atg_tta_decode_fetch(atg_tta_decoder *dec, int32_t *pcm, uint64_t pcm_cap);
+/* image in device memory (4-byte aligned); *d_pcm is the decoder's own
+   buffer, valid until its next call */
+atg_status atg_tta_decode_device(atg_tta_decoder *dec, const void *d_data, uint64_t len,
+                                 const atg_tta_dec_track *tracks, uint32_t n_tracks,
+                                 atg_tta_dec_result *results, const int32_t **d_pcm,
+                                 uint64_t *total_samples);
+/* "ttad_crc", "ttad_parse", "ttad_chain", "ttad_out", "ttad_total" */
+int atg_tta_decoder_kernel_times(atg_tta_decoder *dec, const char **names, float *ms,
+                                 int cap);
+
+/* ------------------------------------------------------------------ */
 /* Sinc resampler (R1-R3, track2track --sample-rate).  Replaces the     */
 /* reference's audiotools.pcmconverter.Resampler (src/pcmconverter.c    */
 /* :370-495: src_new(SRC_SINC_BEST_QUALITY) + src_process per 4096-frame */

@@ -59,6 +59,11 @@ EXPORTS = (
     "atg_alac_encoder_kernel_times", "atg_alac_decoder_last_error", "atg_alac_read_info",
     "atg_alac_decoder_create", "atg_alac_decoder_destroy", "atg_alac_decode_host",
     "atg_alac_decode_fetch", "atg_alac_decode_device", "atg_alac_decoder_kernel_times",
+    "atg_tta_last_error", "atg_tta_encoder_create", "atg_tta_encoder_destroy",
+    "atg_tta_encode_device", "atg_tta_encode_host", "atg_tta_encoder_kernel_times",
+    "atg_tta_decoder_last_error", "atg_tta_read_info", "atg_tta_decoder_create",
+    "atg_tta_decoder_destroy", "atg_tta_decode_host", "atg_tta_decode_fetch",
+    "atg_tta_decode_device", "atg_tta_decoder_kernel_times",
     "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
 )
@@ -202,6 +207,31 @@ class AlacDecResult(ctypes.Structure):
                 ("n_framesets", c_u32), ("status", c_i32), ("channels", c_u32)]
 
 
+class TtaTrackResult(ctypes.Structure):
+    _fields_ = [("out_offset", c_u64), ("bytes", c_u64), ("pcm_frames", c_u64),
+                ("first_frame", c_u32), ("n_frames", c_u32), ("status", c_i32),
+                ("reserved", c_u32)]
+
+
+class TtaInfo(ctypes.Structure):
+    _fields_ = [("channels", c_u32), ("bits_per_sample", c_u32), ("sample_rate", c_u32),
+                ("total_pcm_frames", c_u32), ("block_size", c_u32),
+                ("total_tta_frames", c_u32), ("id3_bytes", c_u64), ("frames_offset", c_u64),
+                ("stage", c_u32), ("reserved", c_u32)]
+
+
+class TtaDecTrack(ctypes.Structure):
+    _fields_ = [("data_offset", c_u64), ("data_bytes", c_u64), ("start", c_u64),
+                ("remaining", c_u64), ("channels", c_u32), ("bits_per_sample", c_u32),
+                ("block_size", c_u32), ("reserved", c_u32),
+                ("frame_bytes", ctypes.POINTER(c_u32)), ("n_frame_bytes", c_u64)]
+
+
+class TtaDecResult(ctypes.Structure):
+    _fields_ = [("sample_offset", c_u64), ("pcm_frames", c_u64), ("first_frame", c_u32),
+                ("n_frames", c_u32), ("status", c_i32), ("channels", c_u32)]
+
+
 class RsTrack(ctypes.Structure):
     _fields_ = [("pcm_offset", c_u64), ("pcm_frames", c_u64), ("in_rate", c_u32),
                 ("out_rate", c_u32), ("reads", ctypes.POINTER(c_u32)), ("n_reads", c_u64)]
@@ -218,6 +248,18 @@ AD_INIT_MESSAGES = {1: "I/O Errror", 2: "invalid unused bits", 3: "invalid alac 
                     9: "Unable to locate 'mdat' atom in stream"}
 AD_READ_MESSAGES = {1: "EOF during frame reading", 2: "invalid unused bits",
                     10: "channel length mismatch"}
+
+
+# True Audio decoder status (include/atgpu.h ATG_TD_*) and the messages the
+# reference raises (src/decoders/tta.c TTADecoder_init, TTADecoder_read)
+TD_OK, TD_IO_ERROR, TD_CRC_MISMATCH, TD_INVALID_SIGNATURE, TD_UNSUPPORTED_FORMAT, \
+    TD_FRAME_READ = range(6)
+TD_HEADER_MESSAGES = {1: "I/O error reading header", 2: "CRC error reading header",
+                      3: "invalid header signature", 4: "unsupported TTA format"}
+TD_SEEKTABLE_MESSAGES = {1: "I/O error reading seektable", 2: "CRC error reading seektable",
+                         4: "unsupported TTA format"}
+TD_READ_MESSAGES = {1: "I/O error reading frame", 2: "CRC mismatch reading frame",
+                    5: "I/O error during frame read"}
 
 
 class ATGError(RuntimeError):
@@ -417,6 +459,39 @@ def load_library():
         lib.atg_alac_decoder_kernel_times.argtypes = [
             P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
         lib.atg_alac_decoder_kernel_times.restype = ctypes.c_int
+        KT = [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
+        lib.atg_tta_last_error.restype = ctypes.c_char_p
+        lib.atg_tta_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_tta_encoder_create.restype = ctypes.c_int
+        lib.atg_tta_encoder_destroy.argtypes = [P]
+        lib.atg_tta_encoder_destroy.restype = None
+        for fn in (lib.atg_tta_encode_device, lib.atg_tta_encode_host):
+            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32,
+                           c_u32, P, c_u64, ctypes.POINTER(TtaTrackResult), P, c_u64,
+                           ctypes.POINTER(c_u64)]
+            fn.restype = ctypes.c_int
+        lib.atg_tta_encoder_kernel_times.argtypes = KT
+        lib.atg_tta_encoder_kernel_times.restype = ctypes.c_int
+        lib.atg_tta_decoder_last_error.restype = ctypes.c_char_p
+        lib.atg_tta_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(TtaInfo), P,
+                                          c_u32, ctypes.POINTER(c_u32)]
+        lib.atg_tta_read_info.restype = ctypes.c_int
+        lib.atg_tta_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_tta_decoder_create.restype = ctypes.c_int
+        lib.atg_tta_decoder_destroy.argtypes = [P]
+        lib.atg_tta_decoder_destroy.restype = None
+        lib.atg_tta_decode_host.argtypes = [
+            P, P, c_u64, ctypes.POINTER(TtaDecTrack), c_u32, ctypes.POINTER(TtaDecResult),
+            ctypes.POINTER(c_u64)]
+        lib.atg_tta_decode_host.restype = ctypes.c_int
+        lib.atg_tta_decode_fetch.argtypes = [P, P, c_u64]
+        lib.atg_tta_decode_fetch.restype = ctypes.c_int
+        lib.atg_tta_decode_device.argtypes = [
+            P, P, c_u64, ctypes.POINTER(TtaDecTrack), c_u32, ctypes.POINTER(TtaDecResult),
+            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
+        lib.atg_tta_decode_device.restype = ctypes.c_int
+        lib.atg_tta_decoder_kernel_times.argtypes = KT
+        lib.atg_tta_decoder_kernel_times.restype = ctypes.c_int
         lib.atg_resample_last_error.restype = ctypes.c_char_p
         lib.atg_resample_output_frames.argtypes = [c_u64, c_u32, c_u32, c_u32]
         lib.atg_resample_output_frames.restype = c_u64
@@ -1160,8 +1235,201 @@ class AlacDecoder(object):
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class TtaEncoder(object):
+    """one libatgpu True Audio encoder (HIP stream + workspace) on one device"""
+
+    def __init__(self, device=0):
+        self.lib = load_library()
+        self.device = device
+        h = ctypes.c_void_p()
+        self._check(self.lib.atg_tta_encoder_create(int(device), ctypes.byref(h)))
+        self.handle = h
+        _track_handle(self)
+
+    def _check(self, status):
+        if status != ATG_OK:
+            raise ATGError(status, self.lib.atg_tta_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        if self.handle:
+            self.lib.atg_tta_encoder_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def frame_count(tracks, sample_rate):
+        block = (int(sample_rate) * 256) // 245
+        return sum(len(t[2]) if len(t) > 2 and t[2] is not None
+                   else (int(t[1]) + block - 1) // block for t in tracks)
+
+    def encode(self, pcm, tracks, channels, bits_per_sample, sample_rate, out_cap=None):
+        """host PCM (int16 up to 16 bits, int32 otherwise) -> (out bytes array,
+        [TtaTrackResult], frame byte sizes uint32 array).  A TTA frame has no
+        size bound, so the first call offers the raw PCM size and a call
+        that reports ATG_ERR_CAPACITY is repeated with the size it asks for."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype not in (np.int16, np.int32):
+            raise TypeError("pcm must be int16 or int32")
+        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        tracks = list(tracks)
+        arr, n, keep = _track_array(tracks)
+        nf = self.frame_count(tracks, sample_rate)
+        res = (TtaTrackResult * max(1, n))()
+        fsb = np.zeros(max(1, nf), dtype=np.uint32)
+        cap = int(out_cap) if out_cap is not None else \
+            pcm.size * ((bits_per_sample + 7) // 8) + 64 * nf + 16 * n + 64
+        need = c_u64()
+        for _ in range(2):
+            out = np.empty(max(1, cap), dtype=np.uint8)
+            st = self.lib.atg_tta_encode_host(
+                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
+                bits_per_sample, sample_rate, out.ctypes.data_as(ctypes.c_void_p), cap, res,
+                fsb.ctypes.data_as(ctypes.c_void_p), len(fsb), ctypes.byref(need))
+            if st != ATG_ERR_CAPACITY or need.value <= cap:
+                break
+            cap = need.value
+        self._check(st)
+        return out, [res[i] for i in range(n)], fsb[:nf]
+
+    def encode_device(self, d_pcm, fmt, tracks, channels, bits_per_sample, sample_rate, d_out,
+                      out_cap, frame_bytes=None):
+        """-> ([TtaTrackResult], bytes needed); raises ATGError with status
+        ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
+        if isinstance(tracks, TrackTable):
+            arr, n = tracks.arr, tracks.n
+        else:
+            arr, n, keep = _track_array(tracks)
+        res = (TtaTrackResult * max(1, n))()
+        need = c_u64()
+        st = self.lib.atg_tta_encode_device(
+            self.handle, ctypes.c_void_p(d_pcm), fmt, arr, n, channels, bits_per_sample,
+            sample_rate, ctypes.c_void_p(d_out), out_cap, res,
+            frame_bytes.ctypes.data_as(ctypes.c_void_p) if frame_bytes is not None else None,
+            len(frame_bytes) if frame_bytes is not None else 0, ctypes.byref(need))
+        if st != ATG_OK:
+            err = ATGError(st, self.lib.atg_tta_last_error().decode("utf-8", "replace"))
+            err.needed = need.value
+            raise err
+        return [res[i] for i in range(n)], need.value
+
+    def kernel_times(self):
+        names = (ctypes.c_char_p * 16)()
+        ms = (ctypes.c_float * 16)()
+        k = self.lib.atg_tta_encoder_kernel_times(self.handle, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+def tta_read_info(data):
+    """header + seektable of a .tta image (host C in libatgpu), an ID3v2
+    prefix skipped -> (ATG_TD_* status, TtaInfo, frame sizes uint32 array)"""
+    lib = load_library()
+    data = bytes(data)
+    info = TtaInfo()
+    nf = c_u32()
+    lib.atg_tta_read_info(data, len(data), ctypes.byref(info), None, 0, ctypes.byref(nf))
+    sizes = np.zeros(max(1, nf.value), dtype=np.uint32)
+    st = lib.atg_tta_read_info(data, len(data), ctypes.byref(info),
+                               sizes.ctypes.data_as(ctypes.c_void_p), len(sizes),
+                               ctypes.byref(nf))
+    return st, info, sizes[:nf.value]
+
+
+def tta_dec_track(offset, nbytes, info, frame_bytes, first_frame=0):
+    """TtaDecTrack for an image at `offset` of the batch buffer, reading from
+    its frame `first_frame`; keeps the size array alive on the returned object"""
+    t = TtaDecTrack()
+    sizes = np.ascontiguousarray(frame_bytes, dtype=np.uint32)
+    t.data_offset = offset
+    t.data_bytes = nbytes
+    t.start = int(info.frames_offset) + int(sizes[:first_frame].astype(np.uint64).sum())
+    t.remaining = max(0, int(info.total_pcm_frames) - first_frame * int(info.block_size))
+    t.channels = info.channels
+    t.bits_per_sample = info.bits_per_sample
+    t.block_size = info.block_size
+    rest = np.ascontiguousarray(sizes[first_frame:])
+    t._sizes = rest
+    t.frame_bytes = rest.ctypes.data_as(ctypes.POINTER(c_u32)) if len(rest) else None
+    t.n_frame_bytes = len(rest)
+    return t
+
+
+class TtaDecoder(object):
+    """one libatgpu True Audio decoder (HIP stream + workspace) on one device"""
+
+    def __init__(self, device=0):
+        self.lib = load_library()
+        self.device = device
+        h = ctypes.c_void_p()
+        self._check(self.lib.atg_tta_decoder_create(int(device), ctypes.byref(h)))
+        self.handle = h
+        _track_handle(self)
+
+    def _check(self, status):
+        if status != ATG_OK:
+            raise ATGError(status, self.lib.atg_tta_decoder_last_error().decode(
+                "utf-8", "replace"))
+
+    def close(self):
+        if self.handle:
+            self.lib.atg_tta_decoder_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode(self, data, tracks):
+        """decode a batch in host memory (images 4-byte aligned in data)
+        -> (pcm int32, [TtaDecResult])"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = len(tracks)
+        arr = (TtaDecTrack * max(1, n))(*tracks)
+        res = (TtaDecResult * max(1, n))()
+        ns = c_u64()
+        self._check(self.lib.atg_tta_decode_host(
+            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
+            ctypes.byref(ns)))
+        pcm = np.empty(max(1, ns.value), dtype=np.int32)
+        self._check(self.lib.atg_tta_decode_fetch(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns.value))
+        return pcm[:ns.value], [res[i] for i in range(n)]
+
+    def decode_device(self, d_data, nbytes, tracks):
+        n = len(tracks)
+        arr = (TtaDecTrack * max(1, n))(*tracks)
+        res = (TtaDecResult * max(1, n))()
+        dp = ctypes.c_void_p()
+        ns = c_u64()
+        self._check(self.lib.atg_tta_decode_device(
+            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
+            ctypes.byref(ns)))
+        return [res[i] for i in range(n)], dp.value, ns.value
+
+    def fetch(self, n_samples):
+        """the last decode's PCM (n_samples int32) to host memory"""
+        pcm = np.empty(max(1, n_samples), dtype=np.int32)
+        self._check(self.lib.atg_tta_decode_fetch(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
+        return pcm[:n_samples]
+
+    def kernel_times(self):
+        names = (ctypes.c_char_p * 16)()
+        ms = (ctypes.c_float * 16)()
+        k = self.lib.atg_tta_decoder_kernel_times(self.handle, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 _engine = None
 _engine_lock = threading.Lock()
+_tta_encoder = None
+_tta_decoder = None
 _alac_decoder = None
 _decoder = None
 _alac_encoder = None
@@ -1213,6 +1481,24 @@ def alac_encoder():
         if _alac_encoder is None:
             _alac_encoder = AlacEncoder(default_device())
         return _alac_encoder
+
+
+def tta_encoder():
+    """process-wide True Audio encoder on ATG_DEVICE / LOCAL_RANK / device 0"""
+    global _tta_encoder
+    with _engine_lock:
+        if _tta_encoder is None:
+            _tta_encoder = TtaEncoder(default_device())
+        return _tta_encoder
+
+
+def tta_decoder():
+    """process-wide True Audio decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
+    global _tta_decoder
+    with _engine_lock:
+        if _tta_decoder is None:
+            _tta_decoder = TtaDecoder(default_device())
+        return _tta_decoder
 
 
 # ---- batches sharded over the node's GPUs (SURVEY 8(e)) ---------------------

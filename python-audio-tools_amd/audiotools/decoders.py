@@ -28,6 +28,8 @@ raises the decode status at the frame where the reference would.
 `decode_flac_batch` is the batch entry trackverify-style callers use.
 `ALACDecoder` / `decode_alac_batch` do the same for ALAC in M4A
 (reference src/decoders/alac.c; GPU kernels alac_decode.hip).
+`TTADecoder` / `decode_tta_batch` do the same for True Audio (reference
+src/decoders/tta.c; GPU kernels tta_decode.hip).
 There is no CPU decoding path.
 """
 
@@ -232,4 +234,137 @@ def decode_alac_batch(images):
     for info, r in zip(infos, res):
         out.append((r.status, info,
                     pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels]))
+    return out
+
+
+# ------------------------------------------------------------ True Audio
+def _tta_init_error(status, stage):
+    table = _atgpu.TD_HEADER_MESSAGES if stage == 0 else _atgpu.TD_SEEKTABLE_MESSAGES
+    msg = table.get(status, "no error")
+    return IOError(msg) if status == _atgpu.TD_IO_ERROR else ValueError(msg)
+
+
+def _tta_read_error(status):
+    msg = _atgpu.TD_READ_MESSAGES.get(status, "no error")
+    return IOError(msg) if status == _atgpu.TD_IO_ERROR else ValueError(msg)
+
+
+class TTADecoder(object):
+    """reference src/decoders/tta.c TTADecoder(file), decoded on the GPU
+    (tta_decode.hip):
+
+      TTADecoder(file)   file object positioned at "TTA1" (or at an ID3v2
+                         comment in front of it), or bytes; ValueError /
+                         IOError from the header and seektable readers
+                         (:79-122)
+      .sample_rate .bits_per_sample .channels .channel_mask
+      .read(n)           one TTA frame per call; an empty FrameList once
+                         every PCM frame is out (:194-262)
+      .seek(offset)      the frame boundary the reference's loop stops at
+                         (:264-321)
+      .close()
+    """
+
+    def __init__(self, file):
+        if isinstance(file, (bytes, bytearray, memoryview)):
+            data = bytes(file)
+        elif hasattr(file, "read"):
+            data = file.read()
+        else:
+            raise TypeError("file must be a file object or bytes")
+        st, info, sizes = _atgpu.tta_read_info(data)
+        if st:
+            raise _tta_init_error(st, info.stage)
+        self._data = data
+        self._info = info
+        self._sizes = sizes
+        self.sample_rate = info.sample_rate
+        self.bits_per_sample = info.bits_per_sample
+        self.channels = info.channels
+        self.channel_mask = {1: 0x4, 2: 0x3}.get(info.channels, 0)  # :181-192
+        self.total_frames = info.total_pcm_frames
+        self.block_size = info.block_size
+        self._frame = 0          # current_tta_frame
+        self._remaining = info.total_pcm_frames
+        self._closed = False
+        self._decoded_from = None
+
+    def _decode(self):
+        """the frames from the current one on, in one GPU call"""
+        if self._decoded_from is not None and self._decoded_from <= self._frame:
+            return
+        pad = (-len(self._data)) % 4
+        track = _atgpu.tta_dec_track(0, len(self._data), self._info, self._sizes, self._frame)
+        pcm_i32, res = _atgpu.tta_decoder().decode(self._data + b"\0" * pad, [track])
+        r = res[0]
+        self._pcm = pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * self.channels]
+        self._good = r.n_frames
+        self._status = r.status
+        self._decoded_from = self._frame
+
+    def read(self, pcm_frames):
+        if self._closed:
+            raise ValueError("cannot read closed stream")
+        if self._remaining == 0:
+            return pcm.empty_framelist(self.channels, self.bits_per_sample)
+        self._decode()
+        k = self._frame - self._decoded_from
+        if k >= self._good:
+            raise _tta_read_error(self._status)
+        n = min(self._remaining, self.block_size)
+        a = k * self.block_size * self.channels
+        self._frame += 1
+        self._remaining -= n
+        return pcm.FrameList._wrap(self._pcm[a:a + n * self.channels].copy(), self.channels,
+                                   self.bits_per_sample)
+
+    def seek(self, pcm_frame_offset):
+        if self._closed:
+            raise ValueError("cannot seek closed stream")
+        pcm_frame_offset = int(pcm_frame_offset)
+        if pcm_frame_offset < 0:
+            raise ValueError("cannot seek to negative value")
+        # skip whole frames while the next boundary is still short of the
+        # offset (the reference compares with <, so an offset on a boundary
+        # stops one frame early)
+        current, frame, remaining = 0, 0, self.total_frames
+        while current + self.block_size < pcm_frame_offset:
+            n = min(remaining, self.block_size)
+            if n == 0:
+                break
+            current += n
+            frame += 1
+            remaining -= n
+        self._frame = frame
+        self._remaining = remaining
+        if self._decoded_from is not None and frame < self._decoded_from:
+            self._decoded_from = None
+        return current
+
+    def close(self):
+        self._closed = True
+
+
+def decode_tta_batch(images):
+    """decode a list of .tta images (bytes) in one GPU batch
+    -> list of (status, TtaInfo, int32 interleaved PCM, first bad frame or
+    None); status is an ATG_TD_* code (0 = every frame decoded), the PCM ends
+    before the first bad frame"""
+    parts, tracks, infos, pos = [], [], [], 0
+    for img in images:
+        st, info, sizes = _atgpu.tta_read_info(img)
+        if st:
+            raise _tta_init_error(st, info.stage)
+        img = bytes(img)
+        pad = (-len(img)) % 4
+        tracks.append(_atgpu.tta_dec_track(pos, len(img), info, sizes))
+        parts.append(img + b"\0" * pad)
+        infos.append(info)
+        pos += len(img) + pad
+    pcm_i32, res = _atgpu.tta_decoder().decode(b"".join(parts), tracks)
+    out = []
+    for info, r in zip(infos, res):
+        out.append((r.status, info,
+                    pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
+                    None if r.status == 0 else int(r.n_frames)))
     return out

@@ -35,6 +35,9 @@ chains on the GPU, the tracks sharded over the node's GPUs.
 
 `encode_alac` / `encode_alac_batch` do the same for ALAC (reference
 src/encoders/alac.c:30-189; GPU kernels alac_encode.hip).
+
+`encode_tta` / `encode_tta_batch` do the same for True Audio (reference
+src/encoders/tta.c:31-114; GPU kernels tta_encode.hip).
 """
 
 import numpy as np
@@ -212,3 +215,62 @@ def encode_alac(file, pcmreader, block_size, initial_history, history_multiplier
     return encode_alac_batch([file], [pcmreader], block_size, initial_history,
                              history_multiplier, maximum_k, minimum_interlacing_leftweight,
                              maximum_interlacing_leftweight)[0]
+
+
+def tta_block_size(sample_rate):
+    """PCM frames per TTA frame (src/encoders/tta.c:62)"""
+    return (int(sample_rate) * 256) // 245
+
+
+def encode_tta_batch(files, pcmreaders):
+    """several PCMReaders (same channels / bits / rate) -> the TTA frames of
+    each written to its file object in one GPU batch (no header, no
+    seektable); one list of frame byte sizes per file"""
+    files = list(files)
+    pcmreaders = list(pcmreaders)
+    if len(files) != len(pcmreaders):
+        raise ValueError("files and pcmreaders differ in length")
+    if not pcmreaders:
+        return []
+    r0 = pcmreaders[0]
+    channels, bps, rate = r0.channels, r0.bits_per_sample, r0.sample_rate
+    if bps not in (8, 16, 24):
+        raise ValueError("bits per sample must be 8, 16 or 24")
+    for r in pcmreaders:
+        if (r.channels, r.bits_per_sample, r.sample_rate) != (channels, bps, rate):
+            raise ValueError("all pcmreaders of a batch must share channels, "
+                             "bits-per-sample and sample rate")
+    block_size = tta_block_size(rate)
+    if block_size < 1:
+        raise ValueError("sample rate too low for a TTA frame")
+    parts, tracks, start = [], [], 0
+    for r in pcmreaders:
+        # every read is one TTA frame, a short read a short frame
+        # (tta.c:70-82)
+        samples, sizes = _collect(r, block_size)
+        frames = len(samples) // channels
+        tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
+        parts.append(samples)
+        start += frames
+    pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    pcm = pcm.astype(np.int16 if bps <= 16 else np.int32)
+    out, results, fsb = _atgpu.tta_encoder().encode(pcm, tracks, channels, bps, rate)
+    logs = []
+    for f, res in zip(files, results):
+        f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+        lo = res.first_frame
+        logs.append([int(x) for x in fsb[lo:lo + res.n_frames]])
+    for r in pcmreaders:
+        r.close()
+    return logs
+
+
+def encode_tta(file, pcmreader):
+    """encode_tta(file, pcmreader) -> [frame byte sizes]
+
+    writes the TTA frames to the file object at its position, as the
+    reference does (src/encoders/tta.c:31-114); header and seektable are
+    the caller's (audiotools.tta.TrueAudio.from_pcm)"""
+    if not hasattr(file, "write"):
+        raise TypeError("file must by a concrete file object")
+    return encode_tta_batch([file], [pcmreader])[0]
