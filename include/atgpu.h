@@ -922,6 +922,132 @@ int atg_tta_decoder_kernel_times(atg_tta_decoder *dec, const char **names, float
                                  int cap);
 
 /* ------------------------------------------------------------------ */
+/* WavPack decoder.  Replaces the reference's                           */
+/* audiotools.decoders.WavPackDecoder (src/decoders/wavpack.c) for a    */
+/* batch of images.  Lossless integer streams (no hybrid, no float).   */
+/* ------------------------------------------------------------------ */
+/* status values: the reference's status enum (decoders/wavpack.h) with its
+   message strings (wavpack_strerror), then what its callers report on their
+   own, then the layout check the reference does not make */
+enum {
+    ATG_WVD_OK = 0,
+    ATG_WVD_IO_ERROR = 1,                        /* IOError "I/O error" */
+    ATG_WVD_SUB_BLOCK_NOT_FOUND = 2,             /* internal */
+    ATG_WVD_INVALID_BLOCK_ID = 3,                /* "invalid block header ID" */
+    ATG_WVD_INVALID_RESERVED_BIT = 4,            /* "invalid reserved bit" */
+    ATG_WVD_EXCESSIVE_DECORRELATION_PASSES = 5,  /* "excessive decorrelation passes" */
+    ATG_WVD_INVALID_DECORRELATION_TERM = 6,      /* "invalid decorrelation term" */
+    ATG_WVD_DECORRELATION_TERMS_MISSING = 7,     /* "missing decorrelation terms sub block" */
+    ATG_WVD_DECORRELATION_WEIGHTS_MISSING = 8,   /* "missing decorrelation weights sub block" */
+    ATG_WVD_DECORRELATION_SAMPLES_MISSING = 9,   /* "missing decorrelation samples sub block" */
+    ATG_WVD_ENTROPY_VARIABLES_MISSING = 10,      /* "missing entropy variables sub block" */
+    ATG_WVD_RESIDUALS_MISSING = 11,              /* "missing bitstream sub block" */
+    ATG_WVD_EXTENDED_INTEGERS_MISSING = 12,      /* "missing extended integers sub block" */
+    ATG_WVD_EXCESSIVE_DECORRELATION_WEIGHTS = 13, /* "excessive decorrelation weight values" */
+    ATG_WVD_INVALID_ENTROPY_VARIABLE_COUNT = 14, /* "invalid entropy variable count" */
+    ATG_WVD_BLOCK_DATA_CRC_MISMATCH = 15,        /* "block data CRC mismatch" */
+    ATG_WVD_BLOCK_DATA_IO = 16,      /* IOError "I/O error reading block data": the file
+                                        ends inside a block */
+    ATG_WVD_INCONSISTENT_BLOCK = 17, /* ValueError "inconsistent block header": a set's
+                                        blocks do not add up to the channel count, disagree
+                                        on block_samples, do not continue the set before,
+                                        claim more than the stream has left or more
+                                        than 2^31 - 1 frames (the reference trusts
+                                        the headers here) */
+    ATG_WVD_MD5_MISMATCH = 18,       /* ValueError "MD5 mismatch at end of stream" */
+    ATG_WVD_SAMPLE_RATE_UNDEFINED = 19, /* ValueError "sample rate undefined" */
+    ATG_WVD_CHANNELS_UNDEFINED = 20     /* ValueError "channel count/mask undefined":
+                                           no channel-info sub-block, or one that
+                                           declares 0 channels */
+};
+
+typedef struct {
+    uint32_t sample_rate, bits_per_sample, channels, channel_mask;
+    uint32_t total_pcm_frames;
+    uint32_t n_sets;      /* complete, consistent block sets in the table */
+    uint32_t n_blocks;    /* blocks in the table: those of the sets, then tail_blocks */
+    uint32_t tail_blocks; /* readable blocks of the set a bad header or the end of the
+                             file stopped in: decoded for their status only */
+    int32_t end_status;   /* what ends the stream after the sets (0: the declared total) */
+    uint32_t has_md5;     /* a 16-byte MD5 sub-block follows the audio */
+    uint8_t md5[16];
+    uint64_t end_offset;  /* byte after the last set */
+} atg_wv_info;
+
+/* one audio block: the 32-byte header is at `offset` of the image, `size`
+   bytes of sub-blocks follow it */
+typedef struct {
+    uint64_t offset;
+    uint32_t size;
+    uint32_t block_index, block_samples;
+    uint32_t flags; /* the header's flag word: mono 1<<2, joint stereo 1<<4, extended
+                       integers 1<<8, initial 1<<11, final 1<<12, false stereo 1<<30 */
+    uint32_t crc;
+    uint32_t set;           /* the set (PCM frame range over all channels) it belongs to */
+    uint32_t first_channel; /* its first channel within the set */
+    uint32_t reserved;
+} atg_wv_block;
+
+/* WavPackDecoder_init and the header walk of the read loop over an
+   in-memory image (host).  Returns an ATG_WVD_* status: non-zero where the
+   reference fails to initialise.  The table ends before the first set that
+   a header error, the end of the file or a layout check stops
+   (info->end_status).  Up to cap blocks are written (blocks may be NULL);
+   *n_blocks receives their number. */
+int atg_wv_read_info(const uint8_t *data, uint64_t len, atg_wv_info *info,
+                     atg_wv_block *blocks, uint32_t cap, uint32_t *n_blocks);
+
+/* One stream of a decode batch: the image at data[data_offset, data_offset +
+   data_bytes) (4-byte aligned) and its table from atg_wv_read_info, or the
+   part of it from a later set on.  The table is checked again: a table that
+   contradicts itself is ATG_ERR_INVALID. */
+typedef struct {
+    uint64_t data_offset, data_bytes;
+    const atg_wv_block *blocks;
+    uint32_t n_blocks, tail_blocks;
+    uint32_t channels, bits_per_sample;
+    int32_t end_status;
+    /* compare the MD5 of the PCM's file byte form (clamped to the width, little
+       endian) with md5 when every set decoded: 1 signed at every width, as the
+       reference's standalone decoder hashes; 2 with 8-bit samples unsigned, as
+       WavPackDecoder_update_md5sum and the reference's encoder do; 0 no check */
+    uint32_t check_md5;
+    uint8_t md5[16];
+} atg_wv_dec_track;
+
+/* n_sets sets = pcm_frames PCM frames (interleaved int32 at sample index
+   sample_offset of the batch output) decoded, then `status` ends the
+   stream: 0, or the status of the track's set number n_sets (the first bad
+   one), or ATG_WVD_MD5_MISMATCH with all PCM delivered. */
+typedef struct {
+    uint64_t sample_offset;
+    uint64_t pcm_frames;
+    uint32_t n_sets;
+    int32_t status;
+    uint32_t channels;
+    uint32_t reserved;
+} atg_wv_dec_result;
+
+typedef struct atg_wv_decoder atg_wv_decoder;
+
+const char *atg_wv_decoder_last_error(void);
+atg_status atg_wv_decoder_create(int device, atg_wv_decoder **out);
+void atg_wv_decoder_destroy(atg_wv_decoder *dec);
+atg_status atg_wv_decode_host(atg_wv_decoder *dec, const uint8_t *data, uint64_t len,
+                              const atg_wv_dec_track *tracks, uint32_t n_tracks,
+                              atg_wv_dec_result *results, uint64_t *total_samples);
+/* the last decode's PCM (total_samples int32) */
+atg_status atg_wv_decode_fetch(atg_wv_decoder *dec, int32_t *pcm, uint64_t pcm_cap);
+/* images in device memory (4-byte aligned); *d_pcm is the decoder's own
+   buffer, valid until its next call */
+atg_status atg_wv_decode_device(atg_wv_decoder *dec, const void *d_data, uint64_t len,
+                                const atg_wv_dec_track *tracks, uint32_t n_tracks,
+                                atg_wv_dec_result *results, const int32_t **d_pcm,
+                                uint64_t *total_samples);
+/* "wvd_parse", "wvd_decorr", "wvd_out", "wvd_total" */
+int atg_wv_decoder_kernel_times(atg_wv_decoder *dec, const char **names, float *ms, int cap);
+
+/* ------------------------------------------------------------------ */
 /* Sinc resampler (R1-R3, track2track --sample-rate).  Replaces the     */
 /* reference's audiotools.pcmconverter.Resampler (src/pcmconverter.c    */
 /* :370-495: src_new(SRC_SINC_BEST_QUALITY) + src_process per 4096-frame */

@@ -596,3 +596,4 @@ from .flac import FlacAudio, InvalidFLAC  # noqa: E402,F401
 from .wav import WaveAudio, InvalidWave  # noqa: E402,F401
 from .m4a import ALACAudio, InvalidALAC  # noqa: E402,F401
 from .tta import TrueAudio, InvalidTTA  # noqa: E402,F401
+from .wavpack import WavPackAudio, InvalidWavPack  # noqa: E402,F401

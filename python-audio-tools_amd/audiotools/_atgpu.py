@@ -64,6 +64,9 @@ EXPORTS = (
     "atg_tta_decoder_last_error", "atg_tta_read_info", "atg_tta_decoder_create",
     "atg_tta_decoder_destroy", "atg_tta_decode_host", "atg_tta_decode_fetch",
     "atg_tta_decode_device", "atg_tta_decoder_kernel_times",
+    "atg_wv_decoder_last_error", "atg_wv_read_info", "atg_wv_decoder_create",
+    "atg_wv_decoder_destroy", "atg_wv_decode_host", "atg_wv_decode_fetch",
+    "atg_wv_decode_device", "atg_wv_decoder_kernel_times",
     "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
 )
@@ -232,6 +235,31 @@ class TtaDecResult(ctypes.Structure):
                 ("n_frames", c_u32), ("status", c_i32), ("channels", c_u32)]
 
 
+class WvInfo(ctypes.Structure):
+    _fields_ = [("sample_rate", c_u32), ("bits_per_sample", c_u32), ("channels", c_u32),
+                ("channel_mask", c_u32), ("total_pcm_frames", c_u32), ("n_sets", c_u32),
+                ("n_blocks", c_u32), ("tail_blocks", c_u32), ("end_status", c_i32),
+                ("has_md5", c_u32), ("md5", ctypes.c_uint8 * 16), ("end_offset", c_u64)]
+
+
+class WvBlock(ctypes.Structure):
+    _fields_ = [("offset", c_u64), ("size", c_u32), ("block_index", c_u32),
+                ("block_samples", c_u32), ("flags", c_u32), ("crc", c_u32), ("set", c_u32),
+                ("first_channel", c_u32), ("reserved", c_u32)]
+
+
+class WvDecTrack(ctypes.Structure):
+    _fields_ = [("data_offset", c_u64), ("data_bytes", c_u64),
+                ("blocks", ctypes.POINTER(WvBlock)), ("n_blocks", c_u32),
+                ("tail_blocks", c_u32), ("channels", c_u32), ("bits_per_sample", c_u32),
+                ("end_status", c_i32), ("check_md5", c_u32), ("md5", ctypes.c_uint8 * 16)]
+
+
+class WvDecResult(ctypes.Structure):
+    _fields_ = [("sample_offset", c_u64), ("pcm_frames", c_u64), ("n_sets", c_u32),
+                ("status", c_i32), ("channels", c_u32), ("reserved", c_u32)]
+
+
 class RsTrack(ctypes.Structure):
     _fields_ = [("pcm_offset", c_u64), ("pcm_frames", c_u64), ("in_rate", c_u32),
                 ("out_rate", c_u32), ("reads", ctypes.POINTER(c_u32)), ("n_reads", c_u64)]
@@ -260,6 +288,26 @@ TD_SEEKTABLE_MESSAGES = {1: "I/O error reading seektable", 2: "CRC error reading
                          4: "unsupported TTA format"}
 TD_READ_MESSAGES = {1: "I/O error reading frame", 2: "CRC mismatch reading frame",
                     5: "I/O error during frame read"}
+
+
+# WavPack decoder status (include/atgpu.h ATG_WVD_*) and the messages the
+# reference raises (src/decoders/wavpack.c wavpack_strerror,
+# WavPackDecoder_init, WavPackDecoder_read); IOError for 1 and 16
+WVD_OK, WVD_IO_ERROR = 0, 1
+WVD_BLOCK_DATA_IO, WVD_INCONSISTENT_BLOCK, WVD_MD5_MISMATCH = 16, 17, 18
+WVD_MESSAGES = {1: "I/O error", 3: "invalid block header ID", 4: "invalid reserved bit",
+                5: "excessive decorrelation passes", 6: "invalid decorrelation term",
+                7: "missing decorrelation terms sub block",
+                8: "missing decorrelation weights sub block",
+                9: "missing decorrelation samples sub block",
+                10: "missing entropy variables sub block", 11: "missing bitstream sub block",
+                12: "missing extended integers sub block",
+                13: "excessive decorrelation weight values",
+                14: "invalid entropy variable count", 15: "block data CRC mismatch",
+                16: "I/O error reading block data", 17: "inconsistent block header",
+                18: "MD5 mismatch at end of stream", 19: "sample rate undefined",
+                20: "channel count/mask undefined"}
+WV_INITIAL, WV_FINAL = 1 << 11, 1 << 12
 
 
 class ATGError(RuntimeError):
@@ -492,6 +540,23 @@ def load_library():
         lib.atg_tta_decode_device.restype = ctypes.c_int
         lib.atg_tta_decoder_kernel_times.argtypes = KT
         lib.atg_tta_decoder_kernel_times.restype = ctypes.c_int
+        lib.atg_wv_decoder_last_error.restype = ctypes.c_char_p
+        lib.atg_wv_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(WvInfo), P,
+                                         c_u32, ctypes.POINTER(c_u32)]
+        lib.atg_wv_read_info.restype = ctypes.c_int
+        lib.atg_wv_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_wv_decoder_create.restype = ctypes.c_int
+        lib.atg_wv_decoder_destroy.argtypes = [P]
+        lib.atg_wv_decoder_destroy.restype = None
+        lib.atg_wv_decode_host.argtypes = [P, P, c_u64, P, c_u32, P, ctypes.POINTER(c_u64)]
+        lib.atg_wv_decode_host.restype = ctypes.c_int
+        lib.atg_wv_decode_fetch.argtypes = [P, P, c_u64]
+        lib.atg_wv_decode_fetch.restype = ctypes.c_int
+        lib.atg_wv_decode_device.argtypes = [P, P, c_u64, P, c_u32, P, ctypes.POINTER(P),
+                                             ctypes.POINTER(c_u64)]
+        lib.atg_wv_decode_device.restype = ctypes.c_int
+        lib.atg_wv_decoder_kernel_times.argtypes = KT
+        lib.atg_wv_decoder_kernel_times.restype = ctypes.c_int
         lib.atg_resample_last_error.restype = ctypes.c_char_p
         lib.atg_resample_output_frames.argtypes = [c_u64, c_u32, c_u32, c_u32]
         lib.atg_resample_output_frames.restype = c_u64
@@ -1426,8 +1491,126 @@ class TtaDecoder(object):
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+def wv_read_info(data):
+    """WavPackDecoder_init and the block table of a .wv image (host C in
+    libatgpu) -> (ATG_WVD_* status, WvInfo, WvBlock array)"""
+    lib = load_library()
+    data = bytes(data)
+    info = WvInfo()
+    nb = c_u32()
+    st = lib.atg_wv_read_info(data, len(data), ctypes.byref(info), None, 0, ctypes.byref(nb))
+    blocks = (WvBlock * max(1, nb.value))()
+    if st == 0 and nb.value:
+        st = lib.atg_wv_read_info(data, len(data), ctypes.byref(info), blocks, nb.value,
+                                  ctypes.byref(nb))
+    return st, info, blocks
+
+
+def wv_dec_track(offset, nbytes, info, blocks, first_set=0, check_md5=None):
+    """WvDecTrack for an image at `offset` of the batch buffer, decoding from
+    its set `first_set`; keeps the table alive on the returned object.  The
+    MD5 is checked when the whole stream is decoded, unless told otherwise
+    (check_md5: 0 no, 1 signed bytes at every width, 2 8-bit unsigned)."""
+    t = WvDecTrack()
+    skip = 0
+    while skip < info.n_blocks - info.tail_blocks and blocks[skip].set < first_set:
+        skip += 1
+    n = info.n_blocks - skip
+    rest = (WvBlock * max(1, n))(*[blocks[skip + k] for k in range(n)])
+    t._blocks = rest
+    t.data_offset = offset
+    t.data_bytes = nbytes
+    t.blocks = rest if n else None
+    t.n_blocks = n
+    t.tail_blocks = info.tail_blocks
+    t.channels = info.channels
+    t.bits_per_sample = info.bits_per_sample
+    t.end_status = info.end_status
+    if check_md5 is None:
+        check_md5 = 1 if first_set == 0 else 0
+    t.check_md5 = int(check_md5) if info.has_md5 else 0
+    ctypes.memmove(t.md5, info.md5, 16)
+    return t
+
+
+class WvDecoder(object):
+    """one libatgpu WavPack decoder (HIP stream + workspace) on one device"""
+
+    def __init__(self, device=0):
+        self.lib = load_library()
+        self.device = device
+        h = ctypes.c_void_p()
+        self._check(self.lib.atg_wv_decoder_create(int(device), ctypes.byref(h)))
+        self.handle = h
+        # a decode and the fetch of its PCM are two calls: held across the
+        # pair, so that threads sharing the process-wide decoder do not
+        # fetch each other's batch
+        self._pair = threading.Lock()
+        _track_handle(self)
+
+    def _check(self, status):
+        if status != ATG_OK:
+            raise ATGError(status, self.lib.atg_wv_decoder_last_error().decode(
+                "utf-8", "replace"))
+
+    def close(self):
+        if self.handle:
+            self.lib.atg_wv_decoder_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode(self, data, tracks, pcm_out=None):
+        """decode a batch in host memory (images 4-byte aligned in data)
+        -> (pcm int32, [WvDecResult]); pcm_out: an int32 array to fetch into"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = len(tracks)
+        arr = (WvDecTrack * max(1, n))(*tracks)
+        res = (WvDecResult * max(1, n))()
+        ns = c_u64()
+        with self._pair:
+            self._check(self.lib.atg_wv_decode_host(
+                self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
+                ctypes.byref(ns)))
+            pcm = np.empty(max(1, ns.value), dtype=np.int32) if pcm_out is None else pcm_out
+            self._check(self.lib.atg_wv_decode_fetch(
+                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns.value))
+        return pcm[:ns.value], [res[i] for i in range(n)]
+
+    def decode_device(self, d_data, nbytes, tracks):
+        """images in device memory; the PCM stays in the decoder's buffer until
+        its next call (fetch() copies it out): one thread at a time"""
+        n = len(tracks)
+        arr = (WvDecTrack * max(1, n))(*tracks)
+        res = (WvDecResult * max(1, n))()
+        dp = ctypes.c_void_p()
+        ns = c_u64()
+        self._check(self.lib.atg_wv_decode_device(
+            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
+            ctypes.byref(ns)))
+        return [res[i] for i in range(n)], dp.value, ns.value
+
+    def fetch(self, n_samples):
+        """the last decode's PCM (n_samples int32) to host memory"""
+        pcm = np.empty(max(1, n_samples), dtype=np.int32)
+        self._check(self.lib.atg_wv_decode_fetch(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
+        return pcm[:n_samples]
+
+    def kernel_times(self):
+        names = (ctypes.c_char_p * 16)()
+        ms = (ctypes.c_float * 16)()
+        k = self.lib.atg_wv_decoder_kernel_times(self.handle, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 _engine = None
 _engine_lock = threading.Lock()
+_wv_decoder = None
 _tta_encoder = None
 _tta_decoder = None
 _alac_decoder = None
@@ -1499,6 +1682,15 @@ def tta_decoder():
         if _tta_decoder is None:
             _tta_decoder = TtaDecoder(default_device())
         return _tta_decoder
+
+
+def wv_decoder():
+    """process-wide WavPack decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
+    global _wv_decoder
+    with _engine_lock:
+        if _wv_decoder is None:
+            _wv_decoder = WvDecoder(default_device())
+        return _wv_decoder
 
 
 # ---- batches sharded over the node's GPUs (SURVEY 8(e)) ---------------------

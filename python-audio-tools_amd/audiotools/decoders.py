@@ -29,7 +29,9 @@ raises the decode status at the frame where the reference would.
 `ALACDecoder` / `decode_alac_batch` do the same for ALAC in M4A
 (reference src/decoders/alac.c; GPU kernels alac_decode.hip).
 `TTADecoder` / `decode_tta_batch` do the same for True Audio (reference
-src/decoders/tta.c; GPU kernels tta_decode.hip).
+src/decoders/tta.c; GPU kernels tta_decode.hip), `WavPackDecoder` /
+`decode_wavpack_batch` for WavPack (reference src/decoders/wavpack.c; GPU
+kernels wavpack_decode.hip).
 There is no CPU decoding path.
 """
 
@@ -367,4 +369,164 @@ def decode_tta_batch(images):
         out.append((r.status, info,
                     pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
                     None if r.status == 0 else int(r.n_frames)))
+    return out
+
+
+# --------------------------------------------------------------- WavPack
+def _wv_error(status):
+    msg = _atgpu.WVD_MESSAGES.get(status, "unspecified error")
+    if status in (_atgpu.WVD_IO_ERROR, _atgpu.WVD_BLOCK_DATA_IO):
+        return IOError(msg)
+    return ValueError(msg)
+
+
+class WavPackDecoder(object):
+    """reference src/decoders/wavpack.c WavPackDecoder(file), decoded on the
+    GPU (wavpack_decode.hip):
+
+      WavPackDecoder(file)  file object positioned at the first "wvpk" block,
+                            or bytes; ValueError / IOError as
+                            WavPackDecoder_init raises them (:24-187)
+      .sample_rate .bits_per_sample .channels .channel_mask
+      .read(n)              one block set per call (a set: one block per
+                            channel pair, all of the same PCM frames); an
+                            empty FrameList once every PCM frame is out.  The
+                            error of a bad set is raised by the call that
+                            reaches it, an MD5 mismatch once, by the first
+                            call after the last set (:261-361)
+      .seek(offset)         the latest initial block with samples whose index
+                            is not beyond the offset (:363-447); the MD5 is
+                            checked again only after a seek to the start
+      .close()
+    """
+
+    def __init__(self, file):
+        if isinstance(file, (bytes, bytearray, memoryview)):
+            data = bytes(file)
+        elif hasattr(file, "read"):
+            data = file.read()
+        else:
+            raise TypeError("file must be a file object or bytes")
+        st, info, blocks = _atgpu.wv_read_info(data)
+        if st:
+            raise _wv_error(st)
+        self._data = data
+        self._info = info
+        self._blocks = blocks
+        self.sample_rate = info.sample_rate
+        self.bits_per_sample = info.bits_per_sample
+        self.channels = info.channels
+        self.channel_mask = info.channel_mask
+        self.total_frames = info.total_pcm_frames
+        # the first block of every set: (block_index, block_samples, initial)
+        self._sets = []
+        for k in range(info.n_blocks - info.tail_blocks):
+            b = blocks[k]
+            if b.set == len(self._sets):
+                self._sets.append((b.block_index, b.block_samples,
+                                   bool(b.flags & _atgpu.WV_INITIAL)))
+        self._set = 0
+        self._remaining = info.total_pcm_frames
+        self._check_md5 = True
+        self._md5_failed = False
+        self._closed = False
+        self._decoded_from = None
+
+    def _decode(self):
+        """the sets from the current one on, in one GPU call"""
+        if self._decoded_from is not None and self._decoded_from <= self._set:
+            return
+        pad = (-len(self._data)) % 4
+        # 8-bit samples are hashed as unsigned bytes (WavPackDecoder_update_md5sum)
+        check = 2 if (self._check_md5 and self._set == 0) else 0
+        track = _atgpu.wv_dec_track(0, len(self._data), self._info, self._blocks, self._set,
+                                    check_md5=check)
+        pcm_i32, res = _atgpu.wv_decoder().decode(self._data + b"\0" * pad, [track])
+        r = res[0]
+        self._pcm = pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * self.channels]
+        self._good = r.n_sets
+        self._status = r.status
+        self._decoded_from = self._set
+        self._md5_failed = bool(check) and r.status == _atgpu.WVD_MD5_MISMATCH
+        # sample index of every decoded set in self._pcm
+        self._starts = [0]
+        for k in range(self._set, self._set + r.n_sets):
+            self._starts.append(self._starts[-1] + self._sets[k][1] * self.channels)
+
+    def read(self, pcm_frames):
+        if self._closed:
+            raise ValueError("cannot read closed stream")
+        if self._remaining == 0:
+            if self._check_md5 and self._info.has_md5:
+                self._check_md5 = False
+                if self._decoded_from is None and self.total_frames == 0:
+                    self._decode()
+                if self._md5_failed:
+                    raise _wv_error(_atgpu.WVD_MD5_MISMATCH)
+            return pcm.empty_framelist(self.channels, self.bits_per_sample)
+        self._decode()
+        k = self._set - self._decoded_from
+        if k >= self._good:
+            raise _wv_error(self._status)
+        a, b = self._starts[k], self._starts[k + 1]
+        self._remaining -= min(self._remaining, self._sets[self._set][1])
+        self._set += 1
+        return pcm.FrameList._wrap(self._pcm[a:b].copy(), self.channels, self.bits_per_sample)
+
+    def seek(self, pcm_frame_offset):
+        if self._closed:
+            raise ValueError("cannot seek closed stream")
+        pcm_frame_offset = int(pcm_frame_offset)
+        if pcm_frame_offset < 0:
+            raise ValueError("cannot seek to negative value")
+        best, best_set = 0, 0
+        for k, (index, samples, initial) in enumerate(self._sets):
+            if initial and samples:
+                if index > pcm_frame_offset:
+                    break
+                best, best_set = index, k
+        self._set = best_set
+        self._remaining = self.total_frames - min(best, self.total_frames)
+        self._check_md5 = best == 0
+        if self._decoded_from is not None and best_set < self._decoded_from:
+            self._decoded_from = None
+        return best
+
+    def close(self):
+        self._closed = True
+
+
+def decode_wavpack_batch(images, md5_mode=1):
+    """decode a list of .wv images (bytes) in one GPU batch; md5_mode 1 hashes
+    signed bytes at every width, as the reference's standalone decoder does,
+    2 hashes 8-bit samples unsigned, as WavPackDecoder does, 0 skips the MD5
+    -> list of (status, WvInfo, int32 interleaved PCM, first bad set or
+    None); status is an ATG_WVD_* code (0 = every set decoded and the MD5,
+    where there is one, agrees), the PCM ends before the first bad set.  An
+    image the reference's decoder would not open has its status, no info
+    (None) and no PCM."""
+    parts, tracks, infos, pos = [], [], [], 0
+    for img in images:
+        img = bytes(img)
+        st, info, blocks = _atgpu.wv_read_info(img)
+        if st:
+            infos.append((st, None))
+            continue
+        pad = (-len(img)) % 4
+        tracks.append(_atgpu.wv_dec_track(pos, len(img), info, blocks, check_md5=md5_mode))
+        parts.append(img + b"\0" * pad)
+        infos.append((0, info))
+        pos += len(img) + pad
+    pcm_i32, res = _atgpu.wv_decoder().decode(b"".join(parts), tracks)
+    out, k = [], 0
+    for st, info in infos:
+        if info is None:
+            out.append((st, None, np.zeros(0, dtype=np.int32), 0))
+            continue
+        r = res[k]
+        k += 1
+        bad = None if r.status in (0, _atgpu.WVD_MD5_MISMATCH) else int(r.n_sets)
+        out.append((r.status, info,
+                    pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
+                    bad))
     return out
