@@ -1048,6 +1048,82 @@ atg_status atg_wv_decode_device(atg_wv_decoder *dec, const void *d_data, uint64_
 int atg_wv_decoder_kernel_times(atg_wv_decoder *dec, const char **names, float *ms, int cap);
 
 /* ------------------------------------------------------------------ */
+/* WavPack encoder.  Replaces the body of the reference's               */
+/* audiotools.encoders.encode_wavpack (src/encoders/wavpack.c) for a    */
+/* batch of tracks of one format.  Every block_size PCM frames become   */
+/* one block per channel group (mono and stereo: one; more channels are */
+/* split by channel_mask as init_context does: 0x7 2+1, 0x33 2+2, 0x107 */
+/* 2+1+1, 0x37 2+1+2, 0x3F 2+1+1+2, anything else channel by channel).  */
+/* A track's output is the complete .wv image: the blocks, the RIFF     */
+/* header sub-block in the first of them, the footer block with the MD5 */
+/* of the PCM, total_samples set in every header.  bits_per_sample 8,   */
+/* 16 or 24.  No foreign RIFF chunks, tags, hybrid or float modes.      */
+/* ------------------------------------------------------------------ */
+typedef struct {
+    uint32_t block_size;         /* PCM frames per block, at least 1 */
+    uint32_t correlation_passes; /* 0, 1, 2, 5, 10 or 16 */
+    uint32_t false_stereo;       /* code a stereo block whose channels are equal as one */
+    uint32_t wasted_bits;        /* shift out low bits that are zero throughout a block */
+    uint32_t joint_stereo;       /* mid/side for two-channel blocks */
+} atg_wv_enc_options;
+
+/* Per-track result: the image is `bytes` long at out + out_offset;
+   block_bytes[first_block .. first_block + n_blocks) are the sizes of its
+   audio blocks, headers included, in file order (the footer block of 50
+   bytes follows them).  md5 is the digest of the PCM as the file's footer
+   holds it: little endian at the sample width, 8-bit samples unsigned. */
+typedef struct {
+    uint64_t out_offset;
+    uint64_t bytes;
+    uint64_t pcm_frames;
+    uint32_t first_block;
+    uint32_t n_blocks;
+    int32_t status;
+    uint32_t reserved;
+    uint8_t md5[16];
+} atg_wv_track_result;
+
+typedef struct atg_wv_encoder atg_wv_encoder;
+
+const char *atg_wv_encoder_last_error(void);
+atg_status atg_wv_encoder_create(int device, atg_wv_encoder **out);
+void atg_wv_encoder_destroy(atg_wv_encoder *enc);
+/* PCM and output in device memory.  A block has no useful size bound before
+   it is encoded, so, as for TTA, the lengths are computed first: *needed
+   (may be NULL) receives the bytes the batch takes, and when that exceeds
+   out_cap the call returns ATG_ERR_CAPACITY with nothing written to d_out.
+   block_bytes (host, block_bytes_cap entries, may be NULL) receives the
+   block sizes; fewer entries than the batch has blocks is ATG_ERR_INVALID.
+   ATG_ERR_INVALID: bits other than 8, 16, 24; 0 channels; passes outside
+   {0, 1, 2, 5, 10, 16}; block_size 0; with passes, a block_size below the
+   history depth of any stream's pass table (stereo 16: 8, 10: 5, 5: 3; mono
+   5, 10, 16: 3; 1 and 2: 2), where the reference aborts on any block but
+   the last once it is shorter than a term 1..8 -- a track no longer than
+   such a block is refused too, which the reference would encode; a track
+   of 2^32 - 1 frames or more.
+   ATG_ERR_UNSUPPORTED: tracks with explicit frame_sizes; more than 255
+   channels. */
+atg_status atg_wv_encode_device(atg_wv_encoder *enc, const void *d_pcm, atg_pcm_format format,
+                                const atg_track *tracks, uint32_t n_tracks, uint32_t channels,
+                                uint32_t channel_mask, uint32_t bits_per_sample,
+                                uint32_t sample_rate, const atg_wv_enc_options *options,
+                                void *d_out, uint64_t out_cap, atg_wv_track_result *results,
+                                uint32_t *block_bytes, uint64_t block_bytes_cap,
+                                uint64_t *needed);
+/* the same for host buffers (staged through the device) */
+atg_status atg_wv_encode_host(atg_wv_encoder *enc, const void *pcm, atg_pcm_format format,
+                              const atg_track *tracks, uint32_t n_tracks, uint32_t channels,
+                              uint32_t channel_mask, uint32_t bits_per_sample,
+                              uint32_t sample_rate, const atg_wv_enc_options *options,
+                              uint8_t *out, uint64_t out_cap, atg_wv_track_result *results,
+                              uint32_t *block_bytes, uint64_t block_bytes_cap, uint64_t *needed);
+/* the last encode: "wv_prep", "wv_chain", "wv_md5", "wv_size" (from the
+   digests' end to the pack's start: the block table copied to the host, the
+   extents, their upload), "wv_pack" (with the footers) and "wv_total", first
+   kernel to last */
+int atg_wv_encoder_kernel_times(atg_wv_encoder *enc, const char **names, float *ms, int cap);
+
+/* ------------------------------------------------------------------ */
 /* Sinc resampler (R1-R3, track2track --sample-rate).  Replaces the     */
 /* reference's audiotools.pcmconverter.Resampler (src/pcmconverter.c    */
 /* :370-495: src_new(SRC_SINC_BEST_QUALITY) + src_process per 4096-frame */

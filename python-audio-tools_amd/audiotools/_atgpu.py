@@ -67,6 +67,8 @@ EXPORTS = (
     "atg_wv_decoder_last_error", "atg_wv_read_info", "atg_wv_decoder_create",
     "atg_wv_decoder_destroy", "atg_wv_decode_host", "atg_wv_decode_fetch",
     "atg_wv_decode_device", "atg_wv_decoder_kernel_times",
+    "atg_wv_encoder_last_error", "atg_wv_encoder_create", "atg_wv_encoder_destroy",
+    "atg_wv_encode_device", "atg_wv_encode_host", "atg_wv_encoder_kernel_times",
     "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
 )
@@ -258,6 +260,17 @@ class WvDecTrack(ctypes.Structure):
 class WvDecResult(ctypes.Structure):
     _fields_ = [("sample_offset", c_u64), ("pcm_frames", c_u64), ("n_sets", c_u32),
                 ("status", c_i32), ("channels", c_u32), ("reserved", c_u32)]
+
+
+class WvEncOptions(ctypes.Structure):
+    _fields_ = [("block_size", c_u32), ("correlation_passes", c_u32), ("false_stereo", c_u32),
+                ("wasted_bits", c_u32), ("joint_stereo", c_u32)]
+
+
+class WvTrackResult(ctypes.Structure):
+    _fields_ = [("out_offset", c_u64), ("bytes", c_u64), ("pcm_frames", c_u64),
+                ("first_block", c_u32), ("n_blocks", c_u32), ("status", c_i32),
+                ("reserved", c_u32), ("md5", ctypes.c_uint8 * 16)]
 
 
 class RsTrack(ctypes.Structure):
@@ -557,6 +570,18 @@ def load_library():
         lib.atg_wv_decode_device.restype = ctypes.c_int
         lib.atg_wv_decoder_kernel_times.argtypes = KT
         lib.atg_wv_decoder_kernel_times.restype = ctypes.c_int
+        lib.atg_wv_encoder_last_error.restype = ctypes.c_char_p
+        lib.atg_wv_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_wv_encoder_create.restype = ctypes.c_int
+        lib.atg_wv_encoder_destroy.argtypes = [P]
+        lib.atg_wv_encoder_destroy.restype = None
+        for fn in (lib.atg_wv_encode_device, lib.atg_wv_encode_host):
+            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32,
+                           c_u32, c_u32, ctypes.POINTER(WvEncOptions), P, c_u64,
+                           ctypes.POINTER(WvTrackResult), P, c_u64, ctypes.POINTER(c_u64)]
+            fn.restype = ctypes.c_int
+        lib.atg_wv_encoder_kernel_times.argtypes = KT
+        lib.atg_wv_encoder_kernel_times.restype = ctypes.c_int
         lib.atg_resample_last_error.restype = ctypes.c_char_p
         lib.atg_resample_output_frames.argtypes = [c_u64, c_u32, c_u32, c_u32]
         lib.atg_resample_output_frames.restype = c_u64
@@ -1608,9 +1633,122 @@ class WvDecoder(object):
         return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
+class WvEncoder(object):
+    """one libatgpu WavPack encoder (HIP stream + workspace) on one device"""
+
+    def __init__(self, device=0):
+        self.lib = load_library()
+        self.device = device
+        h = ctypes.c_void_p()
+        self._check(self.lib.atg_wv_encoder_create(int(device), ctypes.byref(h)))
+        self.handle = h
+        _track_handle(self)
+
+    def _error(self, status):
+        return ATGError(status, self.lib.atg_wv_encoder_last_error().decode("utf-8", "replace"))
+
+    def _check(self, status):
+        if status != ATG_OK:
+            raise self._error(status)
+
+    def close(self):
+        if self.handle:
+            self.lib.atg_wv_encoder_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def options(block_size, correlation_passes=0, false_stereo=False, wasted_bits=False,
+                joint_stereo=False):
+        return WvEncOptions(int(block_size), int(correlation_passes), int(bool(false_stereo)),
+                            int(bool(wasted_bits)), int(bool(joint_stereo)))
+
+    @staticmethod
+    def block_count(tracks, channels, channel_mask, block_size):
+        """blocks of a batch: ceil(frames / block_size) sets of one block per
+        channel group"""
+        if channels <= 2:
+            per = 1
+        else:
+            per = {0x7: 2, 0x33: 2, 0x107: 3, 0x37: 3, 0x3F: 4}.get(channel_mask, channels)
+        block_size = max(1, int(block_size))
+        return sum((int(t[1]) + block_size - 1) // block_size for t in tracks) * per
+
+    def encode(self, opts, pcm, tracks, channels, channel_mask, bits_per_sample, sample_rate,
+               out=None):
+        """host PCM (int16 up to 16 bits, int32 otherwise) -> (out bytes array,
+        [WvTrackResult], block byte sizes uint32 array): complete .wv images.
+        A block has no size bound, so the first call offers the raw PCM size
+        and a call that reports ATG_ERR_CAPACITY is repeated with the size
+        it asks for.  With `out` (a uint8 array) given there is one call into
+        it; an ATGError carries .needed."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype not in (np.int16, np.int32):
+            raise TypeError("pcm must be int16 or int32")
+        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        tracks = list(tracks)
+        arr, n, keep = _track_array(tracks)
+        nb = self.block_count(tracks, channels, channel_mask, opts.block_size)
+        res = (WvTrackResult * max(1, n))()
+        bsb = np.zeros(max(1, nb), dtype=np.uint32)
+        given = out is not None
+        cap = len(out) if given else \
+            pcm.size * ((bits_per_sample + 7) // 8) + 320 * nb + 128 * n + 64
+        need = c_u64()
+        for _ in range(2):
+            if not given:
+                out = np.empty(max(1, cap), dtype=np.uint8)
+            st = self.lib.atg_wv_encode_host(
+                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
+                channel_mask, bits_per_sample, sample_rate, ctypes.byref(opts),
+                out.ctypes.data_as(ctypes.c_void_p), cap, res,
+                bsb.ctypes.data_as(ctypes.c_void_p), len(bsb), ctypes.byref(need))
+            if st != ATG_ERR_CAPACITY or need.value <= cap or given:
+                break
+            cap = need.value
+        if st != ATG_OK:
+            err = self._error(st)
+            err.needed = need.value
+            raise err
+        return out, [res[i] for i in range(n)], bsb[:nb]
+
+    def encode_device(self, opts, d_pcm, fmt, tracks, channels, channel_mask, bits_per_sample,
+                      sample_rate, d_out, out_cap, block_bytes=None):
+        """-> ([WvTrackResult], bytes needed); raises ATGError with status
+        ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
+        if isinstance(tracks, TrackTable):
+            arr, n = tracks.arr, tracks.n
+        else:
+            arr, n, keep = _track_array(tracks)
+        res = (WvTrackResult * max(1, n))()
+        need = c_u64()
+        st = self.lib.atg_wv_encode_device(
+            self.handle, ctypes.c_void_p(d_pcm), fmt, arr, n, channels, channel_mask,
+            bits_per_sample, sample_rate, ctypes.byref(opts), ctypes.c_void_p(d_out), out_cap,
+            res, block_bytes.ctypes.data_as(ctypes.c_void_p) if block_bytes is not None else None,
+            len(block_bytes) if block_bytes is not None else 0, ctypes.byref(need))
+        if st != ATG_OK:
+            err = self._error(st)
+            err.needed = need.value
+            raise err
+        return [res[i] for i in range(n)], need.value
+
+    def kernel_times(self):
+        names = (ctypes.c_char_p * 16)()
+        ms = (ctypes.c_float * 16)()
+        k = self.lib.atg_wv_encoder_kernel_times(self.handle, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 _engine = None
 _engine_lock = threading.Lock()
 _wv_decoder = None
+_wv_encoder = None
 _tta_encoder = None
 _tta_decoder = None
 _alac_decoder = None
@@ -1691,6 +1829,15 @@ def wv_decoder():
         if _wv_decoder is None:
             _wv_decoder = WvDecoder(default_device())
         return _wv_decoder
+
+
+def wv_encoder():
+    """process-wide WavPack encoder on ATG_DEVICE / LOCAL_RANK / device 0"""
+    global _wv_encoder
+    with _engine_lock:
+        if _wv_encoder is None:
+            _wv_encoder = WvEncoder(default_device())
+        return _wv_encoder
 
 
 # ---- batches sharded over the node's GPUs (SURVEY 8(e)) ---------------------

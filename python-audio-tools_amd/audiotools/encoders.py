@@ -38,6 +38,9 @@ src/encoders/alac.c:30-189; GPU kernels alac_encode.hip).
 
 `encode_tta` / `encode_tta_batch` do the same for True Audio (reference
 src/encoders/tta.c:31-114; GPU kernels tta_encode.hip).
+
+`encode_wavpack` / `encode_wavpack_batch` do the same for WavPack (reference
+src/encoders/wavpack.c; GPU kernels wavpack_encode.hip): complete .wv files.
 """
 
 import numpy as np
@@ -274,3 +277,89 @@ def encode_tta(file, pcmreader):
     if not hasattr(file, "write"):
         raise TypeError("file must by a concrete file object")
     return encode_tta_batch([file], [pcmreader])[0]
+
+
+def encode_wavpack_batch(filenames, pcmreaders, block_size, total_pcm_frames=0,
+                         false_stereo=False, wasted_bits=False, joint_stereo=False,
+                         correlation_passes=0, wave_header=None, wave_footer=None):
+    """several PCMReaders (same channels / mask / bits / rate) -> one complete
+    .wv file each, in one GPU batch.  total_pcm_frames: 0, one value for every
+    file, or a list of one per file (see encode_wavpack)"""
+    filenames = list(filenames)
+    pcmreaders = list(pcmreaders)
+    if len(filenames) != len(pcmreaders):
+        raise ValueError("filenames and pcmreaders differ in length")
+    if wave_header is not None or wave_footer is not None:
+        raise ValueError("external RIFF WAVE header / footer are not supported")
+    if not pcmreaders:
+        return
+    totals = (list(total_pcm_frames) if isinstance(total_pcm_frames, (list, tuple))
+              else [total_pcm_frames] * len(pcmreaders))
+    if len(totals) != len(pcmreaders):
+        raise ValueError("total_pcm_frames and pcmreaders differ in length")
+    r0 = pcmreaders[0]
+    fmt = (r0.channels, int(r0.channel_mask), r0.bits_per_sample, r0.sample_rate)
+    channels, mask, bps, rate = fmt
+    for r in pcmreaders:
+        if (r.channels, int(r.channel_mask), r.bits_per_sample, r.sample_rate) != fmt:
+            raise ValueError("all pcmreaders of a batch must share channels, channel mask, "
+                             "bits-per-sample and sample rate")
+    block_size = int(block_size)
+    if block_size < 1:
+        raise ValueError("block size must be at least 1")
+    files = [open(fn, "wb") for fn in filenames]
+    try:
+        parts, tracks, start = [], [], 0
+        for r in pcmreaders:
+            samples, sizes = _collect(r, block_size)
+            if _frame_sizes_or_none(sizes, block_size) is not None:
+                raise ValueError("WavPack is encoded from whole blocks: every read but the "
+                                 "last must return block_size frames")
+            frames = len(samples) // channels
+            tracks.append((start, frames))
+            parts.append(samples)
+            start += frames
+        pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+        pcm = pcm.astype(np.int16 if bps <= 16 else np.int32)
+        enc = _atgpu.wv_encoder()
+        opts = enc.options(block_size, correlation_passes, false_stereo, wasted_bits,
+                           joint_stereo)
+        try:
+            out, results, bsb = enc.encode(opts, pcm, tracks, channels, mask, bps, rate)
+        except _atgpu.ATGError as err:
+            if err.status in (_atgpu.ATG_ERR_INVALID, _atgpu.ATG_ERR_UNSUPPORTED):
+                raise ValueError(err.message)
+            raise
+        for f, res, total in zip(files, results, totals):
+            image = out[res.out_offset:res.out_offset + res.bytes]
+            if total and int(total) != res.pcm_frames:
+                # the declared total stays in every header: the reference
+                # fixes the field up only when it was given as 0
+                image = image.copy()
+                pos = 0
+                for size in list(bsb[res.first_block:res.first_block + res.n_blocks]) + [50]:
+                    image[pos + 12:pos + 16] = np.frombuffer(
+                        (int(total) & 0xFFFFFFFF).to_bytes(4, "little"), dtype=np.uint8)
+                    pos += int(size)
+            f.write(memoryview(image))
+        for r in pcmreaders:
+            r.close()
+    finally:
+        for f in files:
+            f.close()
+
+
+def encode_wavpack(filename, pcmreader, block_size, total_pcm_frames=0, false_stereo=False,
+                   wasted_bits=False, joint_stereo=False, correlation_passes=0,
+                   wave_header=None, wave_footer=None):
+    """encode_wavpack(filename, pcmreader, block_size, ...) writes the file
+    the reference's does (src/encoders/wavpack.c:31-249).
+
+    With total_pcm_frames 0, or equal to the frames read, every header holds
+    the frames read.  A different total is written as declared, which is what
+    the reference's source does; its stand-alone encoder cannot reach that
+    path, so no reference vector covers it.  wave_header / wave_footer
+    (from_wave) are not supported: anything but None raises ValueError."""
+    encode_wavpack_batch([filename], [pcmreader], block_size, total_pcm_frames, false_stereo,
+                         wasted_bits, joint_stereo, correlation_passes, wave_header,
+                         wave_footer)

@@ -12,15 +12,19 @@ path uses:
   .total_frames() .sample_rate()
   .to_pcm() -> audiotools.decoders.WavPackDecoder (GPU), or a PCMReaderError
     when the decoder refuses the stream
-  WavPackAudio.from_pcm(...) raises EncodingError: the engine has no WavPack
-    encoder yet
+  WavPackAudio.from_pcm(filename, pcmreader, compression, total_pcm_frames,
+    encoding_function=audiotools.encoders.encode_wavpack) encodes on the GPU
+    with the reference's five compression modes; with encoding_function left
+    at None it still raises EncodingError (see from_pcm)
   convert / verify are AudioFile's.
 
-Lossless integer streams only.  APEv2 tags, cuesheets and the RIFF header /
-footer sub-blocks are out of scope; the decoder steps over them.
+Lossless integer streams only.  APEv2 tags, cuesheets and foreign RIFF
+chunks (from_wave) are out of scope; the decoder steps over the RIFF header /
+footer sub-blocks, the encoder writes the header the reference generates.
 """
 
-from . import AudioFile, ChannelMask, EncodingError, InvalidFile, PCMReaderError
+from . import (AudioFile, BufferedPCMReader, ChannelMask, CounterPCMReader, EncodingError,
+               InvalidFile, PCMReaderError)
 
 
 class InvalidWavPack(InvalidFile):
@@ -28,12 +32,19 @@ class InvalidWavPack(InvalidFile):
 
 
 class WavPackAudio(AudioFile):
-    """the reference's WavPackAudio, decode slice"""
+    """the reference's WavPackAudio, transcode slice"""
 
     SUFFIX = "wv"
     NAME = SUFFIX
     DESCRIPTION = u"WavPack"
+    DEFAULT_COMPRESSION = "standard"
+    COMPRESSION_MODES = ("veryfast", "fast", "standard", "high", "veryhigh")
+    COMPRESSION_DESCRIPTIONS = {"veryfast": u"fastest encode/decode, worst compression",
+                                "veryhigh": u"slowest encode/decode, best compression"}
     BINARIES = ()
+    __options__ = {mode: {"block_size": 44100, "joint_stereo": True, "false_stereo": True,
+                          "wasted_bits": True, "correlation_passes": passes}
+                   for mode, passes in zip(COMPRESSION_MODES, (1, 2, 5, 10, 16))}
 
     def __init__(self, filename):
         from . import _atgpu
@@ -83,5 +94,36 @@ class WavPackAudio(AudioFile):
                                   bits_per_sample=self.bits_per_sample())
 
     @classmethod
-    def from_pcm(cls, filename, pcmreader, compression=None, total_pcm_frames=None):
-        raise EncodingError("WavPack encoding is not available")
+    def from_pcm(cls, filename, pcmreader, compression=None, total_pcm_frames=None,
+                 encoding_function=None):
+        """encode pcmreader to a new WavPack file with encoding_function
+        (audiotools.encoders.encode_wavpack), as the reference's from_pcm
+        does (wavpack.py:443-490): an unknown compression is "standard", the
+        frames are counted, ValueError / IOError and a total_pcm_frames
+        mismatch unlink the file and raise EncodingError.
+
+        With encoding_function left at None it raises EncodingError and
+        creates no file, as before the engine had an encoder: making
+        encode_wavpack the default is a one-line change here, together with
+        the test that pins this behaviour, so convert(..., WavPackAudio)
+        stays refused until then."""
+        if encoding_function is None:
+            raise EncodingError("WavPack encoding is not available")
+        if compression is None or compression not in cls.COMPRESSION_MODES:
+            compression = cls.DEFAULT_COMPRESSION
+        counter = CounterPCMReader(pcmreader)
+        try:
+            encoding_function(filename, BufferedPCMReader(counter),
+                              total_pcm_frames=(total_pcm_frames
+                                                if total_pcm_frames is not None else 0),
+                              **cls.__options__[compression])
+        except (ValueError, IOError) as err:
+            cls.__unlink__(filename)
+            raise EncodingError(str(err))
+        except Exception:
+            cls.__unlink__(filename)
+            raise
+        if total_pcm_frames is not None and counter.frames_written != total_pcm_frames:
+            cls.__unlink__(filename)
+            raise EncodingError("total PCM frames mismatch")
+        return cls(filename)

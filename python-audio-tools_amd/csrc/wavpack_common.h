@@ -7,6 +7,7 @@
 // wrap at 32 bits in uint32_t, shift counts are masked to five bits.
 #pragma once
 #include <cstdint>
+#include <initializer_list>
 
 #ifdef __HIPCC__
 #define WV_HD __host__ __device__ __forceinline__
@@ -88,6 +89,125 @@ WV_HD int32_t exp2_value(const uint16_t *table, int32_t value)
     else
         r = e << (((v >> 8) - 9u) & 31u);
     return value < 0 ? (int32_t)(0u - r) : (int32_t)r;
+}
+
+// ---- the forward arithmetic of the encoder (src/encoders/wavpack.c:
+// store_weight :917-929, wv_log2 :1323-1376, reset_block_parameters :363-453,
+// init_context :262-290)
+
+WV_HD int32_t store_weight(int32_t w)
+{
+    w = clamp_weight(w);
+    if (w > 0)
+        return (w - ((w + 64) >> 7) + 4) >> 3;
+    return w ? (w + 4) >> 3 : 0;
+}
+
+WV_HD uint32_t bit_length(uint32_t v)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return v ? 32u - (uint32_t)__clz(v) : 0u;
+#else
+    uint32_t n = 0;
+    while (v) {
+        ++n;
+        v >>= 1;
+    }
+    return n;
+#endif
+}
+
+// the 16-bit log form of a sample; table[i] = floor(256 * log2(1 + i/256) + 0.5).
+// |INT32_MIN| is taken in uint32_t (abs() of it is undefined in the reference)
+WV_HD int32_t log2_value(const uint8_t *table, int32_t value)
+{
+    const uint32_t m = value < 0 ? 0u - (uint32_t)value : (uint32_t)value;
+    const uint32_t a = m + (m >> 9);
+    const uint32_t c = bit_length(a);
+    const uint32_t idx = a < 256u ? (a << (9u - c)) & 0xFFu : (a >> (c - 9u)) & 0xFFu;
+    const int32_t r = (int32_t)((c << 8) + table[idx]);
+    return value < 0 ? -r : r;
+}
+
+WV_HD int32_t roundtrip_value(const uint8_t *log_table, const uint16_t *exp_table, int32_t v)
+{
+    return exp2_value(exp_table, log2_value(log_table, v));
+}
+
+constexpr int32_t kDelta = 2; // every pass of the reference encoder
+
+// the term table of a stream block: `eff` coded channels, `passes` the
+// encoder option (0, 1, 2, 5, 10, 16).  A one-channel block has the five-term
+// table for 5, 10 and 16 alike.  -> number of terms
+WV_HD int32_t term_table(uint32_t eff, uint32_t passes, int8_t term[kMaxTerms])
+{
+    if (passes == 0)
+        return 0;
+    if (passes == 1) {
+        term[0] = 18;
+        return 1;
+    }
+    if (passes == 2) {
+        term[0] = 17;
+        term[1] = 18;
+        return 2;
+    }
+    if (passes == 5 || eff == 1) {
+        term[0] = 3, term[1] = 17, term[2] = 2, term[3] = 18, term[4] = 18;
+        return 5;
+    }
+    if (passes == 10) {
+        term[0] = 4, term[1] = 17, term[2] = -1, term[3] = 5, term[4] = 3;
+        term[5] = 2, term[6] = -2, term[7] = 18, term[8] = 18, term[9] = 18;
+        return 10;
+    }
+    term[0] = 2, term[1] = 18, term[2] = -1, term[3] = 8, term[4] = 6, term[5] = 3;
+    term[6] = 5, term[7] = 7, term[8] = 4, term[9] = 2, term[10] = 18, term[11] = -2;
+    term[12] = 3, term[13] = 2, term[14] = 18, term[15] = 18;
+    return 16;
+}
+
+// history samples a term keeps per channel
+WV_HD uint32_t term_samples(int32_t term) { return term > 8 ? 2u : (term > 0 ? (uint32_t)term : 1u); }
+
+// the deepest history of a stream's own table (terms 17 and 18 keep two
+// samples): the reference aborts on a non-final block shorter than its
+// deepest term 1..8, and block sizes below this depth are refused
+inline uint32_t term_depth(uint32_t stream_channels, uint32_t passes)
+{
+    int8_t term[kMaxTerms];
+    const int32_t n = term_table(stream_channels, passes, term);
+    uint32_t d = 0;
+    for (int32_t k = 0; k < n; ++k)
+        if (term[k] > 0 && term_samples(term[k]) > d)
+            d = term_samples(term[k]);
+    return d;
+}
+
+// the channel groups of a track -> number of streams (split[] holds 1 or 2);
+// more than two channels without a known mask are coded one by one
+inline uint32_t stream_split(uint32_t channels, uint32_t mask, uint8_t *split, uint32_t cap)
+{
+    auto set = [&](std::initializer_list<int> v) {
+        uint32_t k = 0;
+        for (int c : v)
+            if (k < cap)
+                split[k++] = (uint8_t)c;
+        return (uint32_t)v.size();
+    };
+    if (channels <= 2)
+        return set({(int)channels});
+    switch (mask) {
+    case 0x7: return set({2, 1});
+    case 0x33: return set({2, 2});
+    case 0x107: return set({2, 1, 1});
+    case 0x37: return set({2, 1, 2});
+    case 0x3F: return set({2, 1, 1, 2});
+    default: break;
+    }
+    for (uint32_t k = 0; k < channels && k < cap; ++k)
+        split[k] = 1;
+    return channels;
 }
 
 } // namespace wv

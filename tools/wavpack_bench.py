@@ -16,6 +16,15 @@ block is the vector's source samples.
 
 Writes one JSON document (--out, default profiles/wavpack_bench.json) and
 prints it.
+
+--encode runs the encoder leg instead and writes profiles/wavpack_enc_bench.json:
+1024 tracks x 10 s of seeded tones and noise (every 8th track dual mono, every
+16th silent in its second half) made on the device, encoded with the
+"standard" and the "veryhigh" options of WavPackAudio, timed per kernel with
+HIP events (atg_wv_encoder_kernel_times).  Every image is decoded on the GPU
+and compared with its source (that decode, over varied content, is timed as a
+row of its own); the first 4 tracks are byte-compared with oracle/_ref/wvenc,
+and the reference time is wvenc at 16 processes, where that binary exists.
 """
 import argparse
 import concurrent.futures
@@ -71,6 +80,165 @@ def reference_run(images, n_tracks, procs):
         return time.perf_counter() - t0
 
 
+def make_tracks(torch, dev, n_tracks, n, rate):
+    """int16 stereo on the device, (n_tracks, n, 2): two tones per channel and
+    a little noise; every 8th track dual mono, every 16th silent from its
+    middle on"""
+    rng = np.random.default_rng(2024)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2024)
+    out = torch.empty((n_tracks, n, 2), dtype=torch.int16, device=dev)
+    t = torch.arange(n, device=dev, dtype=torch.float64)[None, :, None]
+    for a in range(0, n_tracks, 32):
+        b = min(n_tracks, a + 32)
+        f1 = torch.tensor(rng.uniform(100, 400, (b - a, 1, 2)), device=dev)
+        f2 = torch.tensor(rng.uniform(400, 1500, (b - a, 1, 2)), device=dev)
+        x = 9000 * torch.sin(2 * np.pi * f1 * t / rate) + 5000 * torch.sin(2 * np.pi * f2 * t / rate)
+        x = x + 2.0 * torch.randn(x.shape, generator=gen, device=dev, dtype=torch.float64)
+        out[a:b] = torch.round(x).to(torch.int16)
+    out[0::8, :, 1] = out[0::8, :, 0]
+    out[4::16, n // 2:, :] = 0
+    return out
+
+
+def reference_encode(pcm_of, n_tracks, procs, opts, keep):
+    """wvenc over the same tracks, `procs` at a time -> (seconds, the first
+    `keep` images)"""
+    enc = os.path.join(REF, "wvenc")
+    if not os.path.exists(enc):
+        return None, []
+    with tempfile.TemporaryDirectory() as tmp:
+        raw = [pcm_of(k) for k in range(n_tracks)]
+        t0 = time.perf_counter()
+        with concurrent.futures.ThreadPoolExecutor(procs) as ex:
+            list(ex.map(lambda k: subprocess.run(
+                [enc] + opts + [os.path.join(tmp, "%d.wv" % k)], input=raw[k],
+                stdout=subprocess.DEVNULL, check=True), range(n_tracks)))
+        secs = time.perf_counter() - t0
+        images = []
+        for k in range(min(keep, n_tracks)):
+            with open(os.path.join(tmp, "%d.wv" % k), "rb") as f:
+                images.append(f.read())
+        return secs, images
+
+
+def encode_leg(args):
+    import torch
+    from audiotools import WavPackAudio, _atgpu
+
+    ch, bps, rate = 2, 16, 44100
+    n = int(round(args.seconds * rate))
+    torch.cuda.init()
+    dev = torch.device("cuda:0")
+    d_pcm = make_tracks(torch, dev, args.tracks, n, rate)
+    torch.cuda.synchronize()
+    tracks = [(k * n, n) for k in range(args.tracks)]
+    enc = _atgpu.WvEncoder(0)
+    dec = _atgpu.WvDecoder(0)
+    host_pcm = d_pcm.cpu().numpy().reshape(args.tracks, -1)
+    rows = {}
+    for mode in ("standard", "veryhigh"):
+        o = dict(WavPackAudio.__options__[mode])
+        opts = enc.options(o["block_size"], o["correlation_passes"], o["false_stereo"],
+                           o["wasted_bits"], o["joint_stereo"])
+        nb = enc.block_count(tracks, ch, 3, o["block_size"])
+        cap = args.tracks * n * ch * 2
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        bsb = np.zeros(nb, dtype=np.uint32)
+        times, walls = [], []
+        for step in range(args.enc_warmup + args.enc_steps):
+            t0 = time.perf_counter()
+            try:
+                res, need = enc.encode_device(opts, d_pcm.data_ptr(), _atgpu.PCM_S16, tracks, ch, 3,
+                                              bps, rate, d_out.data_ptr(), cap, block_bytes=bsb)
+            except _atgpu.ATGError as err:
+                if err.status != _atgpu.ATG_ERR_CAPACITY:
+                    raise
+                cap = err.needed
+                d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+                res, need = enc.encode_device(opts, d_pcm.data_ptr(), _atgpu.PCM_S16, tracks, ch, 3,
+                                              bps, rate, d_out.data_ptr(), cap, block_bytes=bsb)
+            wall = time.perf_counter() - t0
+            if step >= args.enc_warmup:
+                times.append(enc.kernel_times())
+                walls.append(wall * 1e3)
+        ms = mean_times(times)
+        total = ms["wv_total"]
+        kernels = {k: v for k, v in ms.items() if k != "wv_total"}
+        # every image through the GPU decoder, against its source
+        blob = d_out[:need].cpu().numpy()
+        dtracks = []
+        for r in res:
+            img = blob[r.out_offset:r.out_offset + r.bytes].tobytes()
+            st, info, blocks = _atgpu.wv_read_info(img)
+            assert st == 0 and info.end_status == 0
+            dtracks.append(_atgpu.wv_dec_track(r.out_offset, r.bytes, info, blocks, check_md5=0))
+        drows = []
+        for step in range(1 + args.enc_steps):
+            dres, _, nsamp = dec.decode_device(d_out.data_ptr(), need, dtracks)
+            if step:
+                drows.append(dec.kernel_times())
+        dms = mean_times(drows)
+        pcm = dec.fetch(nsamp)
+        bad = 0
+        for k, r in enumerate(dres):
+            got = pcm[r.sample_offset:r.sample_offset + r.pcm_frames * ch]
+            if r.status != 0 or not np.array_equal(got, host_pcm[k]):
+                bad += 1
+        del pcm
+        wvenc_opts = ["-c", "2", "-m", "3", "-r", str(rate), "-b", "16", "-B",
+                      str(o["block_size"]), "-p", str(o["correlation_passes"]), "-j", "-f", "-w"]
+        ref_s, ref_images = (None, []) if args.no_reference else reference_encode(
+            lambda k: host_pcm[k].tobytes(), args.tracks, args.procs, wvenc_opts, 4)
+        differing = sum(
+            1 for k, img in enumerate(ref_images)
+            if blob[res[k].out_offset:res[k].out_offset + res[k].bytes].tobytes() != img)
+        row = {"options": o, "kernel_ms": ms, "wall_ms_per_batch": float(np.mean(walls)),
+               "kernel_share": {k: v / total for k, v in kernels.items()},
+               "bounding_kernel": max(kernels, key=kernels.get),
+               "chain_layout": "one wave per stream: a lane per pass as a pipeline, one lane for "
+                               "the walk",
+               "wavpack_blocks": nb, "wavpack_blocks_per_s": nb / (total * 1e-3),
+               "pcm_frames_per_s": n * args.tracks / (total * 1e-3),
+               "encoded_bytes": int(need),
+               "compression_ratio": float(need) / (n * ch * 2 * args.tracks),
+               "verify": {"tracks_decoded": len(dres), "tracks_differing_from_source": bad,
+                          "compared_with_wvenc": len(ref_images),
+                          "differing_from_wvenc": differing},
+               "decode_of_these_images": {"kernel_ms": dms, "wavpack_blocks_per_s":
+                                          nb / (dms["wvd_total"] * 1e-3)},
+               "reference": ("oracle/_ref/wvenc, %d processes at a time, same host" % args.procs)
+               if ref_s is not None else "skipped: oracle/_ref/wvenc absent"}
+        if ref_s is not None:
+            row["reference_s"] = ref_s
+            row["speedup_over_reference_kernels"] = ref_s / (total * 1e-3)
+            row["speedup_over_reference_wall"] = ref_s / (row["wall_ms_per_batch"] * 1e-3)
+        rows[mode] = row
+        del d_out
+    enc.close()
+    dec.close()
+    doc = {"shape": {"tracks": args.tracks, "seconds": n / rate, "rate": rate, "channels": ch,
+                     "bits_per_sample": bps, "warmup": args.enc_warmup, "steps": args.enc_steps,
+                     "device": torch.cuda.get_device_name(0)},
+           "input": "seeded tones and noise made on the device; every 8th track dual mono, "
+                    "every 16th silent from its middle on",
+           "encode": rows}
+    text = json.dumps(doc, indent=1, sort_keys=True)
+    print(text)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles",
+                                                                "wavpack_enc_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text + "\n")
+    failed = any(r["verify"]["tracks_differing_from_source"] or r["verify"]["differing_from_wvenc"]
+                 for r in rows.values())
+    return 1 if failed else 0
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "wavpack_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tracks", type=int, default=1024)
@@ -79,8 +247,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--procs", type=int, default=16)
     ap.add_argument("--no-reference", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wavpack_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--encode", action="store_true", help="run the encoder leg instead")
+    ap.add_argument("--enc-warmup", type=int, default=1)
+    ap.add_argument("--enc-steps", type=int, default=3)
     args = ap.parse_args()
+    if args.encode:
+        return encode_leg(args)
 
     import torch
     import wavpack_cases as cases
