@@ -670,6 +670,51 @@ def close_all():
 atexit.register(close_all)
 
 
+class _Handle(object):
+    """what every libatgpu handle class shares: a handle on one device, made
+    by the C function a subclass names in _create and given back by _destroy;
+    _last_error and _kernel_times name that component's two other accessors"""
+
+    _create = _destroy = _last_error = _kernel_times = None
+    handle = None  # so close() and __del__ are safe after a failed create
+
+    def __init__(self, device=0):
+        self.lib = load_library()
+        self.device = device
+        h = ctypes.c_void_p()
+        self._check(self._open(int(device), ctypes.byref(h)))
+        self.handle = h
+        _track_handle(self)
+
+    def _open(self, device, out):
+        return getattr(self.lib, self._create)(device, out)
+
+    def _error(self, status):
+        return ATGError(status, getattr(self.lib, self._last_error)().decode("utf-8", "replace"))
+
+    def _check(self, status):
+        if status != ATG_OK:
+            raise self._error(status)
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def kernel_times(self):
+        """{stage name: ms} of the last run, in stage order; {} before it"""
+        names = (ctypes.c_char_p * 16)()
+        ms = (ctypes.c_float * 16)()
+        k = getattr(self.lib, self._kernel_times)(self.handle, names, ms, 16)
+        return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
 class TrackTable(object):
     """a batch's atg_track array, built once (batches repeat in pipelines)"""
 
@@ -718,36 +763,29 @@ ENGINE_MD5_GPU = 2  # MD5 always on GPU chains
 ENGINE_MD5_HOST = 4  # MD5 always on host threads
 
 
-class Engine(object):
+class Engine(_Handle):
     """one libatgpu engine (streams + workspace) on one device; streaming=True
     for a process that encodes one track at a time (streams on first use,
     ATG_ENGINE_STREAMING); md5 = "auto" (the engine picks GPU chains or host
     threads per batch), "gpu" or "host" (ATG_ENGINE_MD5_GPU / _HOST)"""
 
+    _destroy, _last_error = "atg_engine_destroy", "atg_last_error"
+    _kernel_times = "atg_engine_kernel_times"
+
     def __init__(self, device=0, streaming=False, md5="auto"):
-        self.lib = load_library()
-        self.device = device
         self._inflight = {}  # host-job ticket -> the arrays the engine writes
-        flags = ENGINE_STREAMING if streaming else 0
-        flags |= {"auto": 0, "gpu": ENGINE_MD5_GPU, "host": ENGINE_MD5_HOST}[md5]
-        h = ctypes.c_void_p()
-        _check(self.lib, self.lib.atg_engine_create_ex(int(device), flags, ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
+        self._flags = ENGINE_STREAMING if streaming else 0
+        self._flags |= {"auto": 0, "gpu": ENGINE_MD5_GPU, "host": ENGINE_MD5_HOST}[md5]
+        super().__init__(device)
+
+    def _open(self, device, out):
+        return self.lib.atg_engine_create_ex(device, self._flags, out)
 
     def close(self):
-        if self.handle:
-            # atg_engine_destroy drains the device; the arrays of unwaited host
-            # jobs are released only after it
-            self.lib.atg_engine_destroy(self.handle)
-            self.handle = None
-            self._inflight.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        # atg_engine_destroy drains the device; the arrays of unwaited host
+        # jobs are released only after it
+        super().close()
+        self._inflight.clear()
 
     def bounds(self, options, tracks, channels, bits_per_sample):
         arr, n, _keep = _track_array(tracks)
@@ -905,12 +943,6 @@ class Engine(object):
         """PCM bytes per chunk of the host-memory pipeline (encode())"""
         _check(self.lib, self.lib.atg_engine_set_host_chunk_bytes(self.handle, int(nbytes)))
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_engine_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
-
     def copy_device(self, d_dst, d_src, nbytes):
         """device-to-device copy on this engine's device"""
         _check(self.lib, self.lib.atg_copy_device(self.handle, ctypes.c_void_p(d_dst),
@@ -1029,33 +1061,15 @@ def dec_track(offset, nbytes, si):
     return t
 
 
-class Decoder(object):
+class Decoder(_Handle):
     """one libatgpu FLAC decoder (HIP stream + workspace) on one device"""
 
+    _create, _destroy = "atg_decoder_create", "atg_decoder_destroy"
+    _last_error, _kernel_times = "atg_decoder_last_error", "atg_decoder_kernel_times"
+
     def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_decoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
+        super().__init__(device)
         self._pending = {}
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_decoder_last_error().decode(
-                "utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_decoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_inflight(self, n):
         """decode batches decode_device_async keeps in flight (3..16)"""
@@ -1127,38 +1141,12 @@ class Decoder(object):
                                                   ctypes.byref(ns)))
         return [res[i] for i in range(n)], dp.value, ns.value
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_decoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
-
-class AlacEncoder(object):
+class AlacEncoder(_Handle):
     """one libatgpu ALAC encoder (HIP stream + workspace) on one device"""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_alac_encoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_alac_last_error().decode("utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_alac_encoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "atg_alac_encoder_create", "atg_alac_encoder_destroy"
+    _last_error, _kernel_times = "atg_alac_last_error", "atg_alac_encoder_kernel_times"
 
     @staticmethod
     def options(block_size=4096, initial_history=10, history_multiplier=40, maximum_k=14,
@@ -1208,12 +1196,6 @@ class AlacEncoder(object):
             else None))
         return [res[i] for i in range(n)]
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_alac_encoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
-
 
 def alac_read_info(data, sp_cap=65536):
     """parse_decoding_parameters + seek_mdat (host C in libatgpu)
@@ -1261,32 +1243,11 @@ def alac_dec_track(offset, nbytes, info, start=None, remaining=None, frameset_by
     return t
 
 
-class AlacDecoder(object):
+class AlacDecoder(_Handle):
     """one libatgpu ALAC decoder (HIP stream + workspace) on one device"""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_alac_decoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_alac_decoder_last_error().decode(
-                "utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_alac_decoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "atg_alac_decoder_create", "atg_alac_decoder_destroy"
+    _last_error, _kernel_times = "atg_alac_decoder_last_error", "atg_alac_decoder_kernel_times"
 
     def decode(self, data, tracks):
         """decode a batch in host memory (images 4-byte aligned in data)
@@ -1318,38 +1279,12 @@ class AlacDecoder(object):
             ctypes.byref(ns)))
         return [res[i] for i in range(n)], dp.value, ns.value
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_alac_decoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
-
-class TtaEncoder(object):
+class TtaEncoder(_Handle):
     """one libatgpu True Audio encoder (HIP stream + workspace) on one device"""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_tta_encoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_tta_last_error().decode("utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_tta_encoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "atg_tta_encoder_create", "atg_tta_encoder_destroy"
+    _last_error, _kernel_times = "atg_tta_last_error", "atg_tta_encoder_kernel_times"
 
     @staticmethod
     def frame_count(tracks, sample_rate):
@@ -1402,16 +1337,10 @@ class TtaEncoder(object):
             frame_bytes.ctypes.data_as(ctypes.c_void_p) if frame_bytes is not None else None,
             len(frame_bytes) if frame_bytes is not None else 0, ctypes.byref(need))
         if st != ATG_OK:
-            err = ATGError(st, self.lib.atg_tta_last_error().decode("utf-8", "replace"))
+            err = self._error(st)
             err.needed = need.value
             raise err
         return [res[i] for i in range(n)], need.value
-
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_tta_encoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
 def tta_read_info(data):
@@ -1448,32 +1377,11 @@ def tta_dec_track(offset, nbytes, info, frame_bytes, first_frame=0):
     return t
 
 
-class TtaDecoder(object):
+class TtaDecoder(_Handle):
     """one libatgpu True Audio decoder (HIP stream + workspace) on one device"""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_tta_decoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_tta_decoder_last_error().decode(
-                "utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_tta_decoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "atg_tta_decoder_create", "atg_tta_decoder_destroy"
+    _last_error, _kernel_times = "atg_tta_decoder_last_error", "atg_tta_decoder_kernel_times"
 
     def decode(self, data, tracks):
         """decode a batch in host memory (images 4-byte aligned in data)
@@ -1508,12 +1416,6 @@ class TtaDecoder(object):
         self._check(self.lib.atg_tta_decode_fetch(
             self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
         return pcm[:n_samples]
-
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_tta_decoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
 def wv_read_info(data):
@@ -1558,36 +1460,18 @@ def wv_dec_track(offset, nbytes, info, blocks, first_set=0, check_md5=None):
     return t
 
 
-class WvDecoder(object):
+class WvDecoder(_Handle):
     """one libatgpu WavPack decoder (HIP stream + workspace) on one device"""
 
+    _create, _destroy = "atg_wv_decoder_create", "atg_wv_decoder_destroy"
+    _last_error, _kernel_times = "atg_wv_decoder_last_error", "atg_wv_decoder_kernel_times"
+
     def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_wv_decoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
         # a decode and the fetch of its PCM are two calls: held across the
         # pair, so that threads sharing the process-wide decoder do not
         # fetch each other's batch
         self._pair = threading.Lock()
-        _track_handle(self)
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise ATGError(status, self.lib.atg_wv_decoder_last_error().decode(
-                "utf-8", "replace"))
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_wv_decoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(device)
 
     def decode(self, data, tracks, pcm_out=None):
         """decode a batch in host memory (images 4-byte aligned in data)
@@ -1626,41 +1510,12 @@ class WvDecoder(object):
             self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
         return pcm[:n_samples]
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_wv_decoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
-
-class WvEncoder(object):
+class WvEncoder(_Handle):
     """one libatgpu WavPack encoder (HIP stream + workspace) on one device"""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device = device
-        h = ctypes.c_void_p()
-        self._check(self.lib.atg_wv_encoder_create(int(device), ctypes.byref(h)))
-        self.handle = h
-        _track_handle(self)
-
-    def _error(self, status):
-        return ATGError(status, self.lib.atg_wv_encoder_last_error().decode("utf-8", "replace"))
-
-    def _check(self, status):
-        if status != ATG_OK:
-            raise self._error(status)
-
-    def close(self):
-        if self.handle:
-            self.lib.atg_wv_encoder_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "atg_wv_encoder_create", "atg_wv_encoder_destroy"
+    _last_error, _kernel_times = "atg_wv_encoder_last_error", "atg_wv_encoder_kernel_times"
 
     @staticmethod
     def options(block_size, correlation_passes=0, false_stereo=False, wasted_bits=False,
@@ -1738,22 +1593,9 @@ class WvEncoder(object):
             raise err
         return [res[i] for i in range(n)], need.value
 
-    def kernel_times(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        k = self.lib.atg_wv_encoder_kernel_times(self.handle, names, ms, 16)
-        return {names[i].decode(): float(ms[i]) for i in range(k)}
 
-
-_engine = None
 _engine_lock = threading.Lock()
-_wv_decoder = None
-_wv_encoder = None
-_tta_encoder = None
-_tta_decoder = None
-_alac_decoder = None
-_decoder = None
-_alac_encoder = None
+_shared = {}  # handle class -> the process-wide instance (engine() ... wv_encoder())
 
 
 def default_device():
@@ -1768,76 +1610,53 @@ def visible_devices():
     return int(load_library().atg_visible_devices())
 
 
+def _shared_handle(cls):
+    """the process-wide instance of a handle class, made on first use"""
+    with _engine_lock:
+        obj = _shared.get(cls)
+        if obj is None:
+            obj = _shared[cls] = cls(default_device())
+        return obj
+
+
 def engine():
     """process-wide engine on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _engine
-    with _engine_lock:
-        if _engine is None:
-            _engine = Engine(default_device())
-        return _engine
+    return _shared_handle(Engine)
 
 
 def decoder():
     """process-wide FLAC decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _decoder
-    with _engine_lock:
-        if _decoder is None:
-            _decoder = Decoder(default_device())
-        return _decoder
+    return _shared_handle(Decoder)
 
 
 def alac_decoder():
     """process-wide ALAC decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _alac_decoder
-    with _engine_lock:
-        if _alac_decoder is None:
-            _alac_decoder = AlacDecoder(default_device())
-        return _alac_decoder
+    return _shared_handle(AlacDecoder)
 
 
 def alac_encoder():
     """process-wide ALAC encoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _alac_encoder
-    with _engine_lock:
-        if _alac_encoder is None:
-            _alac_encoder = AlacEncoder(default_device())
-        return _alac_encoder
+    return _shared_handle(AlacEncoder)
 
 
 def tta_encoder():
     """process-wide True Audio encoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _tta_encoder
-    with _engine_lock:
-        if _tta_encoder is None:
-            _tta_encoder = TtaEncoder(default_device())
-        return _tta_encoder
+    return _shared_handle(TtaEncoder)
 
 
 def tta_decoder():
     """process-wide True Audio decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _tta_decoder
-    with _engine_lock:
-        if _tta_decoder is None:
-            _tta_decoder = TtaDecoder(default_device())
-        return _tta_decoder
+    return _shared_handle(TtaDecoder)
 
 
 def wv_decoder():
     """process-wide WavPack decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _wv_decoder
-    with _engine_lock:
-        if _wv_decoder is None:
-            _wv_decoder = WvDecoder(default_device())
-        return _wv_decoder
+    return _shared_handle(WvDecoder)
 
 
 def wv_encoder():
     """process-wide WavPack encoder on ATG_DEVICE / LOCAL_RANK / device 0"""
-    global _wv_encoder
-    with _engine_lock:
-        if _wv_encoder is None:
-            _wv_encoder = WvEncoder(default_device())
-        return _wv_encoder
+    return _shared_handle(WvEncoder)
 
 
 # ---- batches sharded over the node's GPUs (SURVEY 8(e)) ---------------------

@@ -30,6 +30,7 @@
 //                      uncompressed LSBs, ALAC -> wave channel order,
 //                      interleaved int32 (the FrameList layout).
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -773,46 +774,8 @@ __global__ __launch_bounds__(256) void k_adec_interleave(const uint32_t *__restr
 }
 
 // ------------------------------------------------------------------ host
-thread_local std::string g_adec_err;
-
-atg_status adfail(atg_status s, const std::string &m)
-{
-    g_adec_err = m;
-    return s;
-}
-
-#define ADHIP(expr)                                                                         \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return adfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DBufA {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_adec_err;
+#define ADHIP(expr) ATG_HIP_TRY(g_adec_err, expr, #expr)
 
 const int kADTimed = 5;
 const char *kADNames[kADTimed] = {"adec_parse", "adec_chain", "adec_channel", "adec_interleave",
@@ -856,15 +819,9 @@ bool find_path(const uint8_t *d, uint64_t off, uint64_t end, std::initializer_li
 
 } // namespace
 
-struct atg_alac_decoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[kADTimed] = {};
-    float times[kADTimed] = {};
-    bool have_times = false;
-    DBufA data, tracks, ptrack, pstart, recs, counts, dense, jobs, planar, pcm;
-    DBufA resid; // the parse's stored residuals (k_adec_channel reads them)
+struct atg_alac_decoder : StageHandle<kADTimed> {
+    DevBuf data, tracks, ptrack, pstart, recs, counts, dense, jobs, planar, pcm;
+    DevBuf resid; // the parse's stored residuals (k_adec_channel reads them)
     std::vector<ADTrack> tr;
     std::vector<ACount> cnt;
     uint64_t total_samples = 0, total_fs = 0;
@@ -872,7 +829,7 @@ struct atg_alac_decoder {
 
 extern "C" {
 
-const char *atg_alac_decoder_last_error(void) { return g_adec_err.c_str(); }
+const char *atg_alac_decoder_last_error(void) { return g_adec_err.msg.c_str(); }
 
 int atg_alac_read_info(const uint8_t *d, uint64_t len, atg_alac_info *info,
                        atg_alac_seekpoint *sp, uint32_t sp_cap, uint32_t *frame_sizes,
@@ -994,36 +951,15 @@ int atg_alac_read_info(const uint8_t *d, uint64_t len, atg_alac_info *info,
 
 atg_status atg_alac_decoder_create(int device, atg_alac_decoder **out)
 {
-    if (!out)
-        return adfail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return adfail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return adfail(ATG_ERR_INVALID, "device index out of range");
-    ADHIP(hipSetDevice(device));
-    atg_alac_decoder *d = new atg_alac_decoder();
-    d->device = device;
-    ADHIP(hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking));
-    for (auto &e : d->ev)
-        ADHIP(hipEventCreate(&e));
-    *out = d;
-    return ATG_OK;
+    return open_handle(device, out, g_adec_err, "decoder create");
 }
 
 void atg_alac_decoder_destroy(atg_alac_decoder *d)
 {
     if (!d)
         return;
-    (void)hipSetDevice(d->device);
-    (void)hipStreamSynchronize(d->s);
-    for (DBufA *b : {&d->data, &d->tracks, &d->ptrack, &d->pstart, &d->recs, &d->counts,
-                     &d->dense, &d->jobs, &d->planar, &d->pcm, &d->resid})
-        b->release();
-    for (auto &e : d->ev)
-        (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(d->s);
+    d->close({&d->data, &d->tracks, &d->ptrack, &d->pstart, &d->recs, &d->counts, &d->dense,
+              &d->jobs, &d->planar, &d->pcm, &d->resid});
     delete d;
 }
 
@@ -1041,13 +977,13 @@ static atg_status run_adecode(atg_alac_decoder *d, const uint8_t *d_data, uint64
         const atg_alac_dec_track &a = tracks[t];
         ADTrack &b = d->tr[t];
         if (a.data_offset > len || a.data_bytes > len - a.data_offset || a.start > a.data_bytes)
-            return adfail(ATG_ERR_INVALID, "track data range outside the buffer");
+            return g_adec_err.fail(ATG_ERR_INVALID, "track data range outside the buffer");
         if (a.data_offset & 3)
-            return adfail(ATG_ERR_INVALID, "track images must start 4-byte aligned");
+            return g_adec_err.fail(ATG_ERR_INVALID, "track images must start 4-byte aligned");
         if (a.channels < 1 || a.channels > 8)
-            return adfail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
+            return g_adec_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
         if (a.bits_per_sample < 1 || a.bits_per_sample > 32)
-            return adfail(ATG_ERR_UNSUPPORTED, "bits per sample must be 1..32");
+            return g_adec_err.fail(ATG_ERR_UNSUPPORTED, "bits per sample must be 1..32");
         b.img = a.data_offset;
         b.end = a.data_offset + a.data_bytes;
         b.start = a.data_offset + a.start;
@@ -1168,10 +1104,7 @@ static atg_status run_adecode(atg_alac_decoder *d, const uint8_t *d_data, uint64
     ADHIP(hipGetLastError());
     ADHIP(hipEventRecord(d->ev[4], s));
     ADHIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kADTimed - 1; ++k)
-        (void)hipEventElapsedTime(&d->times[k], d->ev[k], d->ev[k + 1]);
-    (void)hipEventElapsedTime(&d->times[kADTimed - 1], d->ev[0], d->ev[kADTimed - 1]);
-    d->have_times = true;
+    d->finish_times();
     uint64_t fbase = 0;
     for (uint32_t t = 0; t < n; ++t) {
         atg_alac_dec_result &r = res[t];
@@ -1195,9 +1128,9 @@ atg_status atg_alac_decode_device(atg_alac_decoder *d, const void *d_data, uint6
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!d_data && len))
-        return adfail(ATG_ERR_INVALID, "NULL argument");
+        return g_adec_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_data) & 3)
-        return adfail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
+        return g_adec_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
     ADHIP(hipSetDevice(d->device));
     atg_status st = run_adecode(d, (const uint8_t *)d_data, len, tracks, n, results);
     if (st != ATG_OK)
@@ -1216,7 +1149,7 @@ atg_status atg_alac_decode_host(atg_alac_decoder *d, const uint8_t *data, uint64
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!data && len))
-        return adfail(ATG_ERR_INVALID, "NULL argument");
+        return g_adec_err.fail(ATG_ERR_INVALID, "NULL argument");
     ADHIP(hipSetDevice(d->device));
     ADHIP(d->data.ensure(len + 64));
     ADHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
@@ -1238,10 +1171,10 @@ atg_status atg_alac_decode_fetch(atg_alac_decoder *d, int32_t *pcm, uint64_t pcm
 {
     ATG_HANDLE_LOCK(d);
     if (!d)
-        return adfail(ATG_ERR_INVALID, "NULL decoder");
+        return g_adec_err.fail(ATG_ERR_INVALID, "NULL decoder");
     if ((pcm && pcm_cap < d->total_samples) ||
         ((frameset_frames || frameset_offsets) && fs_cap < d->total_fs))
-        return adfail(ATG_ERR_CAPACITY, "output buffer too small for the decoded batch");
+        return g_adec_err.fail(ATG_ERR_CAPACITY, "output buffer too small for the decoded batch");
     ADHIP(hipSetDevice(d->device));
     if (pcm && d->total_samples)
         ADHIP(hipMemcpyAsync(pcm, d->pcm.p, sizeof(int32_t) * d->total_samples,
@@ -1265,16 +1198,7 @@ atg_status atg_alac_decode_fetch(atg_alac_decoder *d, int32_t *pcm, uint64_t pcm
 int atg_alac_decoder_kernel_times(atg_alac_decoder *d, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(d);
-    if (!d || !d->have_times)
-        return 0;
-    const int k = cap < kADTimed ? cap : kADTimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kADNames[i];
-        if (ms)
-            ms[i] = d->times[i];
-    }
-    return k;
+    return d ? d->report(kADNames, names, ms, cap) : 0;
 }
 
 } // extern "C"

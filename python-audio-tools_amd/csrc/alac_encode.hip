@@ -36,6 +36,7 @@
 //                      range (whole words stored, the two shared edge words
 //                      OR-ed atomically), the frameset's trailing '111'.
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -769,46 +770,8 @@ __global__ __launch_bounds__(64) void k_alac_pack(const T *__restrict__ pcm,
 }
 
 // ------------------------------------------------------------------ host
-thread_local std::string g_alac_err;
-
-atg_status afail(atg_status s, const std::string &m)
-{
-    g_alac_err = m;
-    return s;
-}
-
-#define AHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return afail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct ABuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_alac_err;
+#define AHIP(expr) ATG_HIP_TRY(g_alac_err, expr, #expr)
 
 const int kATimed = 6;
 const char *kANames[kATimed] = {"alac_lpc", "alac_chain", "alac_decide", "alac_scan",
@@ -862,14 +825,8 @@ uint64_t fs_bound(uint32_t N, uint32_t nch, uint32_t bps)
 
 } // namespace
 
-struct atg_alac_encoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[kATimed] = {};
-    float times[kATimed] = {};
-    bool have_times = false;
-    ABuf fs, tracks, win, lpc, c4, c8, ed, fd, mdat, h_pcm, h_out;
+struct atg_alac_encoder : StageHandle<kATimed> {
+    DevBuf fs, tracks, win, lpc, c4, c8, ed, fd, mdat, h_pcm, h_out;
     std::vector<double> win_host;
     std::map<uint32_t, uint32_t> win_off;
     size_t win_uploaded = 0;
@@ -889,20 +846,21 @@ atg_status alac_plan(atg_alac_encoder *enc, const atg_alac_options *o, const atg
                      uint32_t n, uint32_t channels, uint32_t bps, APlan &P)
 {
     if (!o)
-        return afail(ATG_ERR_INVALID, "options is NULL");
+        return g_alac_err.fail(ATG_ERR_INVALID, "options is NULL");
     if (bps != 16 && bps != 24)
-        return afail(ATG_ERR_INVALID, "bits per sample must be 16 or 24");
+        return g_alac_err.fail(ATG_ERR_INVALID, "bits per sample must be 16 or 24");
     if (channels < 1 || channels > 8)
-        return afail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
+        return g_alac_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
     if (o->block_size < 1 || o->block_size > kMaxBlock)
-        return afail(ATG_ERR_UNSUPPORTED, "block_size must be 1..65535");
+        return g_alac_err.fail(ATG_ERR_UNSUPPORTED, "block_size must be 1..65535");
     if (o->maximum_k < 1 || o->maximum_k > 24)
-        return afail(ATG_ERR_UNSUPPORTED, "maximum_k must be 1..24");
+        return g_alac_err.fail(ATG_ERR_UNSUPPORTED, "maximum_k must be 1..24");
     // the reference writes the leftweight in 8 bits and, with min > max,
     // copies a stale recorder as the frame (alac.c:459-481): both refused
     if (o->minimum_interlacing_leftweight > o->maximum_interlacing_leftweight ||
         o->maximum_interlacing_leftweight > kMaxLw)
-        return afail(ATG_ERR_INVALID, "interlacing leftweights must satisfy 0 <= min <= max <= 255");
+        return g_alac_err.fail(ATG_ERR_INVALID,
+                               "interlacing leftweights must satisfy 0 <= min <= max <= 255");
     AlacParams &p = P.p;
     std::memset(&p, 0, sizeof(p));
     p.block_size = o->block_size;
@@ -969,12 +927,12 @@ atg_status alac_plan(atg_alac_encoder *enc, const atg_alac_options *o, const atg
             for (uint64_t k = 0; k < T.n_frame_sizes; ++k) {
                 const uint32_t len = T.frame_sizes[k];
                 if (len < 1 || len > kMaxBlock)
-                    return afail(ATG_ERR_INVALID, "frame sizes must be 1..65535");
+                    return g_alac_err.fail(ATG_ERR_INVALID, "frame sizes must be 1..65535");
                 add(pos, len);
                 pos += len;
             }
             if (pos != T.pcm_frames)
-                return afail(ATG_ERR_INVALID, "frame sizes must sum to pcm_frames");
+                return g_alac_err.fail(ATG_ERR_INVALID, "frame sizes must sum to pcm_frames");
         } else {
             for (uint64_t pos = 0; pos < T.pcm_frames; pos += o->block_size)
                 add(pos, (uint32_t)std::min<uint64_t>(o->block_size, T.pcm_frames - pos));
@@ -1067,10 +1025,7 @@ atg_status alac_run(atg_alac_encoder *enc, const APlan &P, const T *d_pcm, uint8
         AHIP(hipMemcpyAsync(fd.data(), enc->fd.p, sizeof(FsDesc) * nfs, hipMemcpyDeviceToHost,
                             s));
     AHIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kATimed - 1; ++k)
-        (void)hipEventElapsedTime(&enc->times[k], enc->ev[k], enc->ev[k + 1]);
-    (void)hipEventElapsedTime(&enc->times[kATimed - 1], enc->ev[0], enc->ev[kATimed - 1]);
-    enc->have_times = true;
+    enc->finish_times();
     for (uint32_t t = 0; t < n; ++t) {
         atg_alac_track_result &r = res[t];
         r.out_offset = P.tracks[t].out_base;
@@ -1093,40 +1048,19 @@ atg_status alac_run(atg_alac_encoder *enc, const APlan &P, const T *d_pcm, uint8
 
 extern "C" {
 
-const char *atg_alac_last_error(void) { return g_alac_err.c_str(); }
+const char *atg_alac_last_error(void) { return g_alac_err.msg.c_str(); }
 
 atg_status atg_alac_encoder_create(int device, atg_alac_encoder **out)
 {
-    if (!out)
-        return afail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return afail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return afail(ATG_ERR_INVALID, "device index out of range");
-    AHIP(hipSetDevice(device));
-    atg_alac_encoder *e = new atg_alac_encoder();
-    e->device = device;
-    AHIP(hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking));
-    for (auto &ev : e->ev)
-        AHIP(hipEventCreate(&ev));
-    *out = e;
-    return ATG_OK;
+    return open_handle(device, out, g_alac_err, "encoder create");
 }
 
 void atg_alac_encoder_destroy(atg_alac_encoder *e)
 {
     if (!e)
         return;
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->s);
-    for (ABuf *b : {&e->fs, &e->tracks, &e->win, &e->lpc, &e->c4, &e->c8, &e->ed, &e->fd,
-                    &e->mdat, &e->h_pcm, &e->h_out})
-        b->release();
-    for (auto &ev : e->ev)
-        (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(e->s);
+    e->close({&e->fs, &e->tracks, &e->win, &e->lpc, &e->c4, &e->c8, &e->ed, &e->fd, &e->mdat,
+              &e->h_pcm, &e->h_out});
     delete e;
 }
 
@@ -1136,7 +1070,7 @@ atg_status atg_alac_batch_bounds(atg_alac_encoder *e, const atg_alac_options *o,
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n))
-        return afail(ATG_ERR_INVALID, "NULL argument");
+        return g_alac_err.fail(ATG_ERR_INVALID, "NULL argument");
     APlan P;
     atg_status st = alac_plan(e, o, tracks, n, channels, bps, P);
     if (st != ATG_OK)
@@ -1156,18 +1090,19 @@ atg_status atg_alac_encode_device(atg_alac_encoder *e, const atg_alac_options *o
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n) || (!results && n))
-        return afail(ATG_ERR_INVALID, "NULL argument");
+        return g_alac_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_out) & 3)
-        return afail(ATG_ERR_INVALID, "d_out must be 4-byte aligned");
+        return g_alac_err.fail(ATG_ERR_INVALID, "d_out must be 4-byte aligned");
     if (fmt == ATG_PCM_S16 && bps > 16)
-        return afail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
+        return g_alac_err.fail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
     AHIP(hipSetDevice(e->device));
     APlan P;
     atg_status st = alac_plan(e, o, tracks, n, channels, bps, P);
     if (st != ATG_OK)
         return st;
     if (P.out_bytes > out_cap)
-        return afail(ATG_ERR_CAPACITY, "output buffer smaller than atg_alac_batch_bounds");
+        return g_alac_err.fail(ATG_ERR_CAPACITY,
+                               "output buffer smaller than atg_alac_batch_bounds");
     if (fmt == ATG_PCM_S16)
         return alac_run(e, P, (const int16_t *)d_pcm, (uint8_t *)d_out, results, frameset_bytes);
     return alac_run(e, P, (const int32_t *)d_pcm, (uint8_t *)d_out, results, frameset_bytes);
@@ -1180,14 +1115,15 @@ atg_status atg_alac_encode_host(atg_alac_encoder *e, const atg_alac_options *o, 
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n) || (!results && n) || (!pcm && n))
-        return afail(ATG_ERR_INVALID, "NULL argument");
+        return g_alac_err.fail(ATG_ERR_INVALID, "NULL argument");
     AHIP(hipSetDevice(e->device));
     APlan P;
     atg_status st = alac_plan(e, o, tracks, n, channels, bps, P);
     if (st != ATG_OK)
         return st;
     if (P.out_bytes > out_cap)
-        return afail(ATG_ERR_CAPACITY, "output buffer smaller than atg_alac_batch_bounds");
+        return g_alac_err.fail(ATG_ERR_CAPACITY,
+                               "output buffer smaller than atg_alac_batch_bounds");
     uint64_t frames = 0;
     for (uint32_t t = 0; t < n; ++t)
         frames = std::max<uint64_t>(frames, tracks[t].pcm_offset + tracks[t].pcm_frames);
@@ -1213,16 +1149,7 @@ atg_status atg_alac_encode_host(atg_alac_encoder *e, const atg_alac_options *o, 
 int atg_alac_encoder_kernel_times(atg_alac_encoder *e, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(e);
-    if (!e || !e->have_times)
-        return 0;
-    const int k = cap < kATimed ? cap : kATimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kANames[i];
-        if (ms)
-            ms[i] = e->times[i];
-    }
-    return k;
+    return e ? e->report(kANames, names, ms, cap) : 0;
 }
 
 } // extern "C"

@@ -6,6 +6,7 @@
 // per-track MD5 chain (a serial hash per track) runs concurrently on `aux`
 // and joins before the stream headers are written.
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <sched.h>
@@ -34,46 +35,8 @@
 
 namespace {
 
-thread_local std::string g_err;
-
-atg_status fail(atg_status s, const std::string &msg)
-{
-    g_err = msg;
-    return s;
-}
-
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_err;
+#define HIP_TRY(expr) ATG_HIP_TRY(g_err, expr, #expr)
 
 const int kNumTimed = 8;
 const char *kTimedNames[kNumTimed] = {"lpc_analyze", "subframe_search", "frame_decide",
@@ -407,23 +370,23 @@ atg_status make_plan(const atg_flac_options *o, const atg_track *tracks, uint32_
                      const uint32_t *index_bases = nullptr)
 {
     if (!o)
-        return fail(ATG_ERR_INVALID, "options is NULL");
+        return g_err.fail(ATG_ERR_INVALID, "options is NULL");
     if (channels < 1 || channels > 8)
-        return fail(ATG_ERR_INVALID, "channels must be 1..8");
+        return g_err.fail(ATG_ERR_INVALID, "channels must be 1..8");
     if (bps < 4 || bps > 24)
-        return fail(ATG_ERR_UNSUPPORTED, "bits_per_sample must be 4..24 on the GPU path");
+        return g_err.fail(ATG_ERR_UNSUPPORTED, "bits_per_sample must be 4..24 on the GPU path");
     if (o->block_size == 0)
-        return fail(ATG_ERR_INVALID, "block_size must be > 0");
+        return g_err.fail(ATG_ERR_INVALID, "block_size must be > 0");
     if (o->block_size > ATG_BIG_MAX_BLOCK)
-        return fail(ATG_ERR_UNSUPPORTED, "block_size > 65535 cannot be framed");
+        return g_err.fail(ATG_ERR_UNSUPPORTED, "block_size > 65535 cannot be framed");
     if (o->max_lpc_order > ATG_MAX_LPC)
-        return fail(ATG_ERR_INVALID, "max_lpc_order must be <= 32");
+        return g_err.fail(ATG_ERR_INVALID, "max_lpc_order must be <= 32");
     if (o->max_residual_partition_order > ATG_BIG_MAX_PORDER)
-        return fail(ATG_ERR_INVALID, "max_residual_partition_order must be <= 15");
+        return g_err.fail(ATG_ERR_INVALID, "max_residual_partition_order must be <= 15");
     if (o->padding_size > 0xFFFFFFu)
-        return fail(ATG_ERR_INVALID, "padding_size must fit in 24 bits");
+        return g_err.fail(ATG_ERR_INVALID, "padding_size must fit in 24 bits");
     if (rate == 0)
-        return fail(ATG_ERR_INVALID, "sample_rate must be > 0");
+        return g_err.fail(ATG_ERR_INVALID, "sample_rate must be > 0");
     FlacParams &p = pl.p;
     std::memset(&p, 0, sizeof(p));
     p.block_size = o->block_size;
@@ -468,14 +431,14 @@ atg_status make_plan(const atg_flac_options *o, const atg_track *tracks, uint32_
             for (uint64_t k = 0; k < tr.n_frame_sizes; ++k) {
                 const uint32_t n = tr.frame_sizes[k];
                 if (n == 0 || n > ATG_BIG_MAX_BLOCK)
-                    return fail(n ? ATG_ERR_UNSUPPORTED : ATG_ERR_INVALID,
+                    return g_err.fail(n ? ATG_ERR_UNSUPPORTED : ATG_ERR_INVALID,
                                 "explicit frame sizes must be 1..65535");
                 sum += n;
                 lens.push_back(n);
                 owner.push_back(t);
             }
             if (sum != tr.pcm_frames)
-                return fail(ATG_ERR_INVALID, "frame sizes do not sum to pcm_frames");
+                return g_err.fail(ATG_ERR_INVALID, "frame sizes do not sum to pcm_frames");
         } else {
             for (uint64_t done = 0; done < tr.pcm_frames; done += B) {
                 lens.push_back((uint32_t)std::min<uint64_t>(B, tr.pcm_frames - done));
@@ -484,7 +447,7 @@ atg_status make_plan(const atg_flac_options *o, const atg_track *tracks, uint32_
         }
         ti.n_frames = (uint32_t)(lens.size() - ti.first_pos);
         if (lens.size() > 0x7FFFFFFFull)
-            return fail(ATG_ERR_INVALID, "too many frames in one batch");
+            return g_err.fail(ATG_ERR_INVALID, "too many frames in one batch");
     }
     // frame ids: block_size-long frames first, the rest after, so LPC waves
     // over 64 frames share one window (uniform loads)
@@ -526,7 +489,7 @@ atg_status make_plan(const atg_flac_options *o, const atg_track *tracks, uint32_
     p.frame_bound = (uint32_t)fb;
     p.frame_lds_words = (uint32_t)((fb + 3) / 4 + 2);
     if (!pl.big && p.frame_lds_words * 4ull > 128 * 1024)
-        return fail(ATG_ERR_UNSUPPORTED, "frame image exceeds the pack kernel's LDS budget");
+        return g_err.fail(ATG_ERR_UNSUPPORTED, "frame image exceeds the pack kernel's LDS budget");
     if (pl.big) {
         pl.big_nmax = maxn;
         pl.big_porder = 0;
@@ -677,7 +640,7 @@ atg_status batch_end(atg_engine *e, EncSlot &sl, hipEvent_t after)
     const atg_status st = batch_end_queue(e, sl, after);
     if (st != ATG_OK) {
         sl.end_status = st;
-        sl.end_error = g_err;
+        sl.end_error = g_err.msg;
     }
     return st;
 }
@@ -937,7 +900,7 @@ atg_status enqueue_batch(atg_engine *e, EncSlot &sl, const std::shared_ptr<Plan>
     Plan &pl = *plp;
     FlacParams &p = pl.p;
     if (pl.out_bytes > out_cap)
-        return fail(ATG_ERR_CAPACITY, "output buffer too small for this batch");
+        return g_err.fail(ATG_ERR_CAPACITY, "output buffer too small for this batch");
     p.n_reg_frames = (fmt == ATG_PCM_S16 && ((uintptr_t)d_pcm & 15u) == 0) ? pl.n_reg_prefix : 0u;
     HIP_TRY(hipSetDevice(e->device));
     sl.md5_host = want_host_md5(e, pl, fmt, md5_early);
@@ -1198,7 +1161,7 @@ atg_status finish_batch(atg_engine *e, EncSlot &sl)
     if (sl.end_status != ATG_OK) {
         // ev_done was never recorded: drain the slot's streams, report the error
         drain_slot(e, sl);
-        return fail(sl.end_status, sl.end_error);
+        return g_err.fail(sl.end_status, sl.end_error);
     }
     HIP_TRY(hipEventSynchronize(sl.ev_done));
     for (int k = 0; k < kNumTimed; ++k) {
@@ -1211,11 +1174,11 @@ atg_status finish_batch(atg_engine *e, EncSlot &sl)
     e->have_times = true;
     uint32_t err_h = *sl.err_h;
     if (err_h & 1u)
-        return fail(ATG_ERR_UNSUPPORTED, "frame longer than the GPU block limit");
+        return g_err.fail(ATG_ERR_UNSUPPORTED, "frame longer than the GPU block limit");
     if (err_h & 4u)
-        return fail(ATG_ERR_CAPACITY, "a frame exceeds its track's output slot");
+        return g_err.fail(ATG_ERR_CAPACITY, "a frame exceeds its track's output slot");
     if (err_h)
-        return fail(ATG_ERR_DEVICE, "GPU consistency check failed (code " +
+        return g_err.fail(ATG_ERR_DEVICE, "GPU consistency check failed (code " +
                                         std::to_string(err_h) + ")");
     return ATG_OK;
 }
@@ -1334,8 +1297,9 @@ atg_status take_slot(atg_engine *e, EncSlot *&out, uint64_t &ticket)
 {
     EncSlot &sl = e->slot[e->next_ticket % e->depth];
     if (sl.busy)
-        return fail(ATG_ERR_INVALID, "as many encode batches in flight as the engine has slots "
-                                     "(atg_engine_set_inflight): wait for the oldest");
+        return g_err.fail(ATG_ERR_INVALID,
+                          "as many encode batches in flight as the engine has slots "
+                          "(atg_engine_set_inflight): wait for the oldest");
     ticket = e->next_ticket++;
     sl.ticket = ticket;
     sl.done = false;
@@ -1348,16 +1312,16 @@ atg_status wait_ticket(atg_engine *e, uint64_t t, EncSlot *&out)
 {
     EncSlot &sl = e->slot[t % e->depth];
     if (sl.ticket != t || (!sl.busy && !sl.done))
-        return fail(ATG_ERR_INVALID, "unknown or expired encode ticket");
+        return g_err.fail(ATG_ERR_INVALID, "unknown or expired encode ticket");
     if (sl.busy) {
         sl.status = finish_batch(e, sl);
-        sl.error = g_err;
+        sl.error = g_err.msg;
         sl.busy = false;
         sl.done = true;
     }
     out = &sl;
     if (sl.status != ATG_OK)
-        return fail(sl.status, sl.error);
+        return g_err.fail(sl.status, sl.error);
     return ATG_OK;
 }
 
@@ -1512,7 +1476,7 @@ atg_status host_collect(atg_engine *e)
 // flight (their device state is gone) and free the slots
 atg_status host_drain(atg_engine *e, atg_status err)
 {
-    const std::string msg = g_err;
+    const std::string msg = g_err.msg;
     const bool device_ok = hipDeviceSynchronize() == hipSuccess;
     // a fully collected job may still have its last chunk's images in pinned
     // staging: its D2H is complete now, so finish the copy (or fail the job
@@ -1542,7 +1506,7 @@ atg_status host_drain(atg_engine *e, atg_status err)
             jp->error = msg;
         }
     e->hflight.clear();
-    g_err = msg;
+    g_err.msg = msg;
     return err;
 }
 
@@ -1690,7 +1654,7 @@ extern "C" {
 
 int atg_abi_version(void) { return ATG_ABI_VERSION; }
 
-const char *atg_last_error(void) { return g_err.c_str(); }
+const char *atg_last_error(void) { return g_err.msg.c_str(); }
 
 atg_status atg_engine_create(int device, atg_engine **out)
 {
@@ -1700,13 +1664,13 @@ atg_status atg_engine_create(int device, atg_engine **out)
 atg_status atg_engine_create_ex(int device, uint32_t flags, atg_engine **out)
 {
     if (!out)
-        return fail(ATG_ERR_INVALID, "out is NULL");
+        return g_err.fail(ATG_ERR_INVALID, "out is NULL");
     *out = nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(ATG_ERR_DEVICE, "no HIP device available");
+        return g_err.fail(ATG_ERR_DEVICE, "no HIP device available");
     if (device < 0 || device >= n)
-        return fail(ATG_ERR_INVALID, "device index out of range");
+        return g_err.fail(ATG_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
     atg_engine *e = new atg_engine();
     e->device = device;
@@ -1840,11 +1804,11 @@ atg_status atg_flac_encode_device_async(atg_engine *e, const atg_flac_options *o
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n_tracks) || !ticket)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (format == ATG_PCM_S16 && bps > 16)
-        return fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
+        return g_err.fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
     if (!e->hflight.empty())
-        return fail(ATG_ERR_INVALID, "a host encode job is in flight: wait for it first");
+        return g_err.fail(ATG_ERR_INVALID, "a host encode job is in flight: wait for it first");
     std::shared_ptr<Plan> pl;
     atg_status st = get_plan(e, opts, tracks, n_tracks, channels, bps, rate, pl);
     if (st != ATG_OK)
@@ -1882,7 +1846,7 @@ atg_status atg_flac_encode_wait(atg_engine *e, uint64_t ticket, atg_track_result
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     EncSlot *sl = nullptr;
     atg_status st = wait_ticket(e, ticket, sl);
     if (st != ATG_OK)
@@ -1900,7 +1864,7 @@ atg_status atg_flac_encode_device(atg_engine *e, const atg_flac_options *opts,
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n_tracks) || (!results && n_tracks))
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     uint64_t t = 0;
     e->sync_call = true; // waited at once: no split MD5 chain
     atg_status st = atg_flac_encode_device_async(e, opts, d_pcm, format, tracks, n_tracks,
@@ -1921,9 +1885,9 @@ atg_status atg_flac_encode_host_async(atg_engine *e, const atg_flac_options *opt
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!tracks && n_tracks) || (!results && n_tracks) || !ticket)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (format == ATG_PCM_S16 && bps > 16)
-        return fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
+        return g_err.fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
     auto jp = std::make_unique<HostJob>();
     HostJob &j = *jp;
     // the whole job's layout (what atg_flac_batch_bounds sized)
@@ -1931,13 +1895,14 @@ atg_status atg_flac_encode_host_async(atg_engine *e, const atg_flac_options *opt
     if (st != ATG_OK)
         return st;
     if (j.whole.out_bytes > out_cap)
-        return fail(ATG_ERR_CAPACITY, "output buffer too small for this batch");
+        return g_err.fail(ATG_ERR_CAPACITY, "output buffer too small for this batch");
     HIP_TRY(hipSetDevice(e->device));
     // the slots' device state is shared: an unwaited device batch would
     // lose its results
     for (EncSlot &s2 : e->slot)
         if (s2.busy && !s2.host)
-            return fail(ATG_ERR_INVALID, "an async encode batch is in flight: wait for it first");
+            return g_err.fail(ATG_ERR_INVALID,
+                              "an async encode batch is in flight: wait for it first");
     // the host pipeline runs kEncSlots chunks on the default rotation (the
     // slots with aux streams from creation); an automatic deeper rotation a
     // device pipeline left behind is undone
@@ -1999,12 +1964,12 @@ atg_status atg_flac_encode_host_wait(atg_engine *e, uint64_t ticket)
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     size_t k = 0;
     while (k < e->hjobs.size() && e->hjobs[k]->id != ticket)
         ++k;
     if (k == e->hjobs.size())
-        return fail(ATG_ERR_INVALID, "unknown or expired host job ticket");
+        return g_err.fail(ATG_ERR_INVALID, "unknown or expired host job ticket");
     HostJob *j = e->hjobs[k].get();
     HIP_TRY(hipSetDevice(e->device));
     // chunks are collected in submission order: everything up to this job's
@@ -2025,7 +1990,7 @@ atg_status atg_flac_encode_host_wait(atg_engine *e, uint64_t ticket)
     const std::string msg = j->error;
     e->hjobs.erase(e->hjobs.begin() + (std::ptrdiff_t)k);
     if (st != ATG_OK)
-        return fail(st, msg);
+        return g_err.fail(st, msg);
     return ATG_OK;
 }
 
@@ -2107,12 +2072,13 @@ atg_status atg_flac_encode_frames_batch(atg_engine *e, const atg_flac_options *o
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (!segs && n) || (!seg_offsets && n) || (!seg_bytes && n))
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (format == ATG_PCM_S16 && bps > 16)
-        return fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
+        return g_err.fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
     for (EncSlot &s2 : e->slot)
         if (s2.busy)
-            return fail(ATG_ERR_INVALID, "an async encode batch is in flight: wait for it first");
+            return g_err.fail(ATG_ERR_INVALID,
+                              "an async encode batch is in flight: wait for it first");
     std::vector<atg_track> tr(n);
     std::vector<uint32_t> bases(n);
     uint64_t pcm_end = 0;
@@ -2125,7 +2091,7 @@ atg_status atg_flac_encode_frames_batch(atg_engine *e, const atg_flac_options *o
                                                   : 0);
         // the frame header's UTF-8 number holds 31 bits (flac.c:1531-1566)
         if (g.first_frame_number + nfr > 0x7FFFFFFFull)
-            return fail(ATG_ERR_INVALID, "frame numbers beyond 2^31 - 1");
+            return g_err.fail(ATG_ERR_INVALID, "frame numbers beyond 2^31 - 1");
         tr[k].pcm_offset = g.pcm_offset;
         tr[k].pcm_frames = g.pcm_frames;
         tr[k].frame_sizes = g.frame_sizes;
@@ -2134,7 +2100,7 @@ atg_status atg_flac_encode_frames_batch(atg_engine *e, const atg_flac_options *o
         pcm_end = std::max<uint64_t>(pcm_end, g.pcm_offset + g.pcm_frames);
     }
     if (!pcm && pcm_end)
-        return fail(ATG_ERR_INVALID, "NULL pcm");
+        return g_err.fail(ATG_ERR_INVALID, "NULL pcm");
     auto pl = std::make_shared<Plan>();
     atg_status st = make_plan(opts, tr.data(), n, channels, bps, rate, *pl, true, 0,
                               bases.data());
@@ -2185,7 +2151,7 @@ atg_status atg_flac_encode_frames_batch(atg_engine *e, const atg_flac_options *o
         pos += (sl->tout_h[k].bytes + 15u) & ~15ull;
     }
     if (pos > out_cap)
-        return fail(ATG_ERR_CAPACITY, "output buffer too small for the segments' frames");
+        return g_err.fail(ATG_ERR_CAPACITY, "output buffer too small for the segments' frames");
     if (pos) {
         HIP_TRY(h.d_off.ensure(std::max<size_t>(n, 1) * sizeof(uint64_t)));
         HIP_TRY(h.d_pack.ensure(pos));
@@ -2217,7 +2183,7 @@ atg_status atg_flac_encode_frames(atg_engine *e, const atg_flac_options *opts, c
                                   uint64_t *out_bytes, uint32_t *frame_bytes)
 {
     if (!e || (!pcm && pcm_frames) || !out_bytes)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     atg_segment g;
     g.pcm_offset = 0;
     g.pcm_frames = pcm_frames;
@@ -2236,7 +2202,7 @@ atg_status atg_flac_encode_frames(atg_engine *e, const atg_flac_options *opts, c
         if (st != ATG_OK)
             return st;
         if (*out_bytes > out_cap)
-            return fail(ATG_ERR_CAPACITY, "output buffer too small for the segment's frames");
+            return g_err.fail(ATG_ERR_CAPACITY, "output buffer too small for the segment's frames");
         std::memcpy(out, tmp.data(), *out_bytes);
         return ATG_OK;
     }
@@ -2263,9 +2229,10 @@ atg_status atg_engine_set_inflight(atg_engine *e, uint32_t n)
 {
     ATG_HANDLE_LOCK(e);
     if (!e || (n != 0 && (n < kEncSlots || n > kMaxSlots)))
-        return fail(ATG_ERR_INVALID, "in-flight batches must be 3..32 (or 0: automatic)");
+        return g_err.fail(ATG_ERR_INVALID, "in-flight batches must be 3..32 (or 0: automatic)");
     if (!engine_idle(e))
-        return fail(ATG_ERR_INVALID, "an encode batch or host job is in flight: wait for it first");
+        return g_err.fail(ATG_ERR_INVALID,
+                          "an encode batch or host job is in flight: wait for it first");
     e->depth_user = n != 0;
     if (n)
         set_depth(e, n);
@@ -2282,7 +2249,7 @@ atg_status atg_engine_set_host_chunk_bytes(atg_engine *e, uint64_t bytes)
 {
     ATG_HANDLE_LOCK(e);
     if (!e || !bytes)
-        return fail(ATG_ERR_INVALID, "NULL engine or zero chunk size");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine or zero chunk size");
     e->chunk_bytes = bytes;
     return ATG_OK;
 }
@@ -2306,7 +2273,7 @@ atg_status atg_device_alloc(atg_engine *e, uint64_t bytes, void **d_ptr)
 {
     ATG_HANDLE_LOCK(e);
     if (!e || !d_ptr)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMalloc(d_ptr, bytes ? bytes : 1));
     return ATG_OK;
@@ -2316,7 +2283,7 @@ atg_status atg_device_free(atg_engine *e, void *d_ptr)
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     HIP_TRY(hipSetDevice(e->device));
     if (d_ptr)
         HIP_TRY(hipFree(d_ptr));
@@ -2326,11 +2293,11 @@ atg_status atg_device_free(atg_engine *e, void *d_ptr)
 atg_status atg_host_alloc(uint64_t bytes, void **ptr)
 {
     if (!ptr)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     *ptr = nullptr;
     if (hipHostMalloc(ptr, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
         *ptr = nullptr;
-        return fail(ATG_ERR_NOMEM, "hipHostMalloc failed");
+        return g_err.fail(ATG_ERR_NOMEM, "hipHostMalloc failed");
     }
     return ATG_OK;
 }
@@ -2345,7 +2312,7 @@ atg_status atg_copy_to_device(atg_engine *e, void *d_dst, const void *src, uint6
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
     return ATG_OK;
@@ -2355,7 +2322,7 @@ atg_status atg_copy_device(atg_engine *e, void *d_dst, const void *d_src, uint64
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice));
     return ATG_OK;
@@ -2365,7 +2332,7 @@ atg_status atg_host_gather(void *dst, const void *const *srcs, const uint64_t *b
                            uint64_t n, uint32_t threads)
 {
     if ((!dst || !srcs || !bytes) && n)
-        return fail(ATG_ERR_INVALID, "NULL argument");
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
     std::vector<uint64_t> off(n + 1, 0);
     for (uint64_t i = 0; i < n; ++i)
         off[i + 1] = off[i] + bytes[i];
@@ -2400,7 +2367,7 @@ atg_status atg_copy_to_host(atg_engine *e, void *dst, const void *d_src, uint64_
 {
     ATG_HANDLE_LOCK(e);
     if (!e)
-        return fail(ATG_ERR_INVALID, "NULL engine");
+        return g_err.fail(ATG_ERR_INVALID, "NULL engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
     return ATG_OK;

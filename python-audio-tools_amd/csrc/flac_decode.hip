@@ -38,6 +38,7 @@
 // the FD_* values of include/atgpu.h (the reference's flac_status plus the
 // conditions read() raises itself).
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1718,46 +1719,8 @@ const char *kDecNames[kDecTimed] = {"dec_scan",     "dec_parse", "dec_chain", "d
 
 } // namespace
 
-thread_local std::string g_dec_err;
-
-static atg_status dfail(atg_status s, const std::string &m)
-{
-    g_dec_err = m;
-    return s;
-}
-
-#define DHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return dfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_dec_err;
+#define DHIP(expr) ATG_HIP_TRY(g_dec_err, expr, #expr)
 
 // One batch in flight: its PCM / MD5 byte buffers, the MD5 stream, and the
 // host copies its results are computed from.  Three slots let batch k's
@@ -1779,8 +1742,8 @@ constexpr int kDecSlots = 3;
 constexpr uint32_t kSpecStreak = 4; // redone batches in a row before mode 0
 constexpr int kDecMaxSlots = 16;
 struct DecSlot {
-    DBuf pcm, bytes, md5, md5meta;
-    DBuf tracks, frames, jobs, warm, rows, meta; // the restore's tables and scratch
+    DevBuf pcm, bytes, md5, md5meta;
+    DevBuf tracks, frames, jobs, warm, rows, meta; // the restore's tables and scratch
     hipStream_t s_md5 = nullptr;       // the slot's stream: restore, emit, MD5
     hipEvent_t ev[kDecTimed + 1] = {}; // phase events (emit end = ev[5])
     hipEvent_t ev_chain = nullptr;     // the chain's second pass is done (decoder stream)
@@ -1811,9 +1774,9 @@ struct atg_decoder {
     hipStream_t s = nullptr;
     float times[kDecTimed] = {};
     bool have_times = false;
-    DBuf data, tracks, counts, ncand, cand_pos, cand_idx, recs, hits, segs;
-    DBuf cand_trk;    // each candidate's track (k_dec_hdr)
-    DBuf cbits, spec; // the frame-end hypothesis: candidate bitmap, lengths
+    DevBuf data, tracks, counts, ncand, cand_pos, cand_idx, recs, hits, segs;
+    DevBuf cand_trk;    // each candidate's track (k_dec_hdr)
+    DevBuf cbits, spec; // the frame-end hypothesis: candidate bitmap, lengths
     int spec_mode = 1; // atg_decoder_set_frame_hypothesis
     uint64_t spec_redos = 0; // batches redone with the full parse
     uint32_t spec_streak = 0; // consecutive batches redone
@@ -1868,7 +1831,7 @@ static const uint32_t kMasks[9] = {0, 0x4, 0x3, 0x7, 0x33, 0x37, 0x3F, 0x70F, 0x
 
 extern "C" {
 
-const char *atg_decoder_last_error(void) { return g_dec_err.c_str(); }
+const char *atg_decoder_last_error(void) { return g_dec_err.msg.c_str(); }
 
 int atg_flac_read_metadata(const uint8_t *data, uint64_t len, atg_flac_streaminfo *si,
                            atg_flac_seekpoint *sp, uint32_t sp_cap)
@@ -1998,13 +1961,13 @@ int atg_flac_read_metadata(const uint8_t *data, uint64_t len, atg_flac_streaminf
 atg_status atg_decoder_create(int device, atg_decoder **out)
 {
     if (!out)
-        return dfail(ATG_ERR_INVALID, "out is NULL");
+        return g_dec_err.fail(ATG_ERR_INVALID, "out is NULL");
     *out = nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return dfail(ATG_ERR_DEVICE, "no HIP device available");
+        return g_dec_err.fail(ATG_ERR_DEVICE, "no HIP device available");
     if (device < 0 || device >= n)
-        return dfail(ATG_ERR_INVALID, "device index out of range");
+        return g_dec_err.fail(ATG_ERR_INVALID, "device index out of range");
     DHIP(hipSetDevice(device));
     static uint8_t t8[256];
     static uint16_t t16[4][256];
@@ -2037,7 +2000,7 @@ void atg_decoder_destroy(atg_decoder *d)
         return;
     (void)hipSetDevice(d->device);
     (void)hipStreamSynchronize(d->s);
-    for (DBuf *b : {&d->data, &d->tracks, &d->counts, &d->ncand, &d->cand_pos, &d->cand_idx,
+    for (DevBuf *b : {&d->data, &d->tracks, &d->counts, &d->ncand, &d->cand_pos, &d->cand_idx,
                     &d->recs, &d->hits, &d->segs, &d->cbits, &d->spec, &d->cand_trk})
         b->release();
     if (d->s_roll)
@@ -2045,8 +2008,8 @@ void atg_decoder_destroy(atg_decoder *d)
     for (DecSlot &sl : d->slot) {
         if (sl.s_md5)
             (void)hipStreamSynchronize(sl.s_md5);
-        for (DBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames, &sl.jobs,
-                        &sl.warm, &sl.rows, &sl.meta})
+        for (DevBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames,
+                          &sl.jobs, &sl.warm, &sl.rows, &sl.meta})
             b->release();
         for (auto &e : sl.ev)
             (void)hipEventDestroy(e);
@@ -2169,11 +2132,11 @@ static atg_status enqueue_decode(atg_decoder *d, DecSlot &sl, const uint8_t *d_d
         const atg_flac_dec_track &a = tracks[t];
         DecTrack &b = tr[t];
         if (a.data_offset > len || a.data_bytes > len - a.data_offset)
-            return dfail(ATG_ERR_INVALID, "track data range outside the buffer");
+            return g_dec_err.fail(ATG_ERR_INVALID, "track data range outside the buffer");
         if (t && a.data_offset < tracks[t - 1].data_offset)
-            return dfail(ATG_ERR_INVALID, "tracks must be ordered by data_offset");
+            return g_dec_err.fail(ATG_ERR_INVALID, "tracks must be ordered by data_offset");
         if (a.channels < 1 || a.channels > 8)
-            return dfail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
+            return g_dec_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
         b.start = a.data_offset;
         b.end = a.data_offset + a.data_bytes;
         b.total = a.total_samples;
@@ -2511,7 +2474,8 @@ static atg_status take_dec_slot(atg_decoder *d, DecSlot **out)
         if (d->slot[k].ticket < sl->ticket)
             sl = &d->slot[k];
     if (sl->busy)
-        return dfail(ATG_ERR_INVALID, "every decode slot holds a batch in flight: wait for one");
+        return g_dec_err.fail(ATG_ERR_INVALID,
+                              "every decode slot holds a batch in flight: wait for one");
     sl->ticket = d->next_ticket++;
     *out = sl;
     return ATG_OK;
@@ -2533,9 +2497,9 @@ atg_status atg_flac_decode_device_async(atg_decoder *d, const void *d_data, uint
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || !ticket || (!d_data && len))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_data) & 3)
-        return dfail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
+        return g_dec_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
     DHIP(hipSetDevice(d->device));
     DecSlot *sl = nullptr;
     atg_status st = take_dec_slot(d, &sl);
@@ -2556,12 +2520,12 @@ atg_status atg_flac_decode_wait(atg_decoder *d, uint64_t ticket, atg_flac_dec_re
 {
     ATG_HANDLE_LOCK(d);
     if (!d)
-        return dfail(ATG_ERR_INVALID, "NULL decoder");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL decoder");
     DecSlot *sl = find_dec_ticket(d, ticket);
     if (!sl)
-        return dfail(ATG_ERR_INVALID, "unknown or already waited decode ticket");
+        return g_dec_err.fail(ATG_ERR_INVALID, "unknown or already waited decode ticket");
     if (!results && !sl->tr.empty())
-        return dfail(ATG_ERR_INVALID, "NULL results");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL results");
     DHIP(hipSetDevice(d->device));
     atg_status st = finish_decode(d, *sl, results);
     if (st != ATG_OK)
@@ -2580,7 +2544,7 @@ atg_status atg_flac_decode_device(atg_decoder *d, const void *d_data, uint64_t l
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!d_data && len))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
     uint64_t ticket = 0;
     atg_status st = atg_flac_decode_device_async(d, d_data, len, tracks, n, &ticket);
     if (st != ATG_OK)
@@ -2595,12 +2559,13 @@ atg_status atg_flac_decode_host(atg_decoder *d, const uint8_t *data, uint64_t le
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!data && len))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
     DHIP(hipSetDevice(d->device));
     // the staging buffer is read by the decoder stream: no batch in flight
     for (DecSlot &sl : d->slot)
         if (sl.busy)
-            return dfail(ATG_ERR_INVALID, "a device decode is in flight: wait for it first");
+            return g_dec_err.fail(ATG_ERR_INVALID,
+                                  "a device decode is in flight: wait for it first");
     DHIP(d->data.ensure(len + 64));
     DHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
     if (len)
@@ -2626,18 +2591,19 @@ atg_status atg_flac_decode_fetch(atg_decoder *d, int32_t *pcm, uint64_t pcm_cap,
 {
     ATG_HANDLE_LOCK(d);
     if (!d)
-        return dfail(ATG_ERR_INVALID, "NULL decoder");
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL decoder");
     if (d->last < 0)
-        return dfail(ATG_ERR_INVALID, "no decoded batch");
+        return g_dec_err.fail(ATG_ERR_INVALID, "no decoded batch");
     DecSlot &sl = d->slot[d->last];
     const bool want_frames = frame_offsets || frame_block_sizes;
     // the slot's buffers hold the last waited batch until a newer batch takes
     // the slot
     if (sl.busy)
-        return dfail(ATG_ERR_INVALID, "the last waited batch's slot holds a newer batch: fetch "
-                                      "before enqueueing three more");
+        return g_dec_err.fail(ATG_ERR_INVALID,
+                              "the last waited batch's slot holds a newer batch: fetch "
+                              "before enqueueing three more");
     if ((pcm && pcm_cap < sl.total_samples) || (want_frames && frame_cap < sl.total_frames))
-        return dfail(ATG_ERR_CAPACITY, "output buffer too small for the decoded batch");
+        return g_dec_err.fail(ATG_ERR_CAPACITY, "output buffer too small for the decoded batch");
     DHIP(hipSetDevice(d->device));
     if (pcm && sl.total_samples)
         DHIP(hipMemcpyAsync(pcm, sl.pcm.p, sizeof(int32_t) * sl.total_samples,
@@ -2663,18 +2629,19 @@ atg_status atg_decoder_set_inflight(atg_decoder *d, uint32_t n)
 {
     ATG_HANDLE_LOCK(d);
     if (!d || n < (uint32_t)kDecSlots || n > (uint32_t)kDecMaxSlots)
-        return dfail(ATG_ERR_INVALID, "decode batches in flight must be 3..16");
+        return g_dec_err.fail(ATG_ERR_INVALID, "decode batches in flight must be 3..16");
     for (DecSlot &sl : d->slot)
         if (sl.busy)
-            return dfail(ATG_ERR_INVALID, "a decode batch is in flight: wait for it first");
+            return g_dec_err.fail(ATG_ERR_INVALID,
+                                  "a decode batch is in flight: wait for it first");
     // a lower depth gives the workspaces of the slots past it back (a
     // config-2 slot holds ~5 GB: PCM, rows, byte image)
     for (int k = (int)n; k < kDecMaxSlots; ++k) {
         DecSlot &sl = d->slot[k];
         if (sl.s_md5)
             (void)hipStreamSynchronize(sl.s_md5);
-        for (DBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames, &sl.jobs,
-                        &sl.warm, &sl.rows, &sl.meta})
+        for (DevBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames,
+                          &sl.jobs, &sl.warm, &sl.rows, &sl.meta})
             b->release();
     }
     d->depth = (int)n;
@@ -2686,7 +2653,7 @@ atg_status atg_decoder_set_frame_hypothesis(atg_decoder *d, int mode)
 {
     ATG_HANDLE_LOCK(d);
     if (!d || mode < 0 || mode > 2)
-        return dfail(ATG_ERR_INVALID, "frame hypothesis mode must be 0, 1 or 2");
+        return g_dec_err.fail(ATG_ERR_INVALID, "frame hypothesis mode must be 0, 1 or 2");
     d->spec_mode = mode;
     d->spec_streak = 0;
     return ATG_OK;

@@ -23,25 +23,14 @@
 #include <string>
 
 #include "../../include/atgpu.h"
+#include "host_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-thread_local std::string g_conv_err;
-
-atg_status cfail(atg_status s, const std::string &m)
-{
-    g_conv_err = m;
-    return s;
-}
-
-#define CHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return cfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
+thread_local ErrSlot g_conv_err;
+#define CHIP(expr) ATG_HIP_TRY(g_conv_err, expr, #expr)
 
 __device__ __forceinline__ int32_t bps_one(int32_t x, uint64_t f, uint32_t c, uint64_t frames,
                                            uint32_t ch, uint32_t in_bps, uint32_t out_bps,
@@ -194,7 +183,7 @@ uint32_t default_mask(uint32_t ch)
 
 extern "C" {
 
-const char *atg_pcm_convert_last_error(void) { return g_conv_err.c_str(); }
+const char *atg_pcm_convert_last_error(void) { return g_conv_err.msg.c_str(); }
 
 uint32_t atg_pcm_convert_out_channels(int kind, uint32_t in_channels)
 {
@@ -207,9 +196,9 @@ atg_status atg_pcm_convert_device(int kind, const int32_t *d_in, int32_t *d_out,
                                   uint64_t dither_bit0, void *stream)
 {
     if ((!d_in || !d_out) && frames)
-        return cfail(ATG_ERR_INVALID, "NULL buffer");
+        return g_conv_err.fail(ATG_ERR_INVALID, "NULL buffer");
     if (channels < 1 || in_bps < 1 || in_bps > 32)
-        return cfail(ATG_ERR_INVALID, "bad channels / bits per sample");
+        return g_conv_err.fail(ATG_ERR_INVALID, "bad channels / bits per sample");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((frames + 255) / 256)), blk(256);
     if (!frames)
@@ -217,11 +206,12 @@ atg_status atg_pcm_convert_device(int kind, const int32_t *d_in, int32_t *d_out,
     switch (kind) {
     case ATG_CONV_BPS:
         if (out_bps < 1 || out_bps > 32)
-            return cfail(ATG_ERR_INVALID, "bad output bits per sample");
+            return g_conv_err.fail(ATG_ERR_INVALID, "bad output bits per sample");
         if (out_bps < in_bps && !d_dither)
-            return cfail(ATG_ERR_INVALID, "dither bytes required to reduce bits per sample");
+            return g_conv_err.fail(ATG_ERR_INVALID,
+                                   "dither bytes required to reduce bits per sample");
         if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
-            return cfail(ATG_ERR_INVALID, "PCM buffers must be 16-byte aligned");
+            return g_conv_err.fail(ATG_ERR_INVALID, "PCM buffers must be 16-byte aligned");
         hipLaunchKernelGGL(k_pcm_bps,
                            dim3((unsigned)((frames * channels + 1024 * kBpsGroups - 1) /
                                            (1024 * kBpsGroups))),
@@ -235,7 +225,8 @@ atg_status atg_pcm_convert_device(int kind, const int32_t *d_in, int32_t *d_out,
         for (uint32_t m = mask & 0x3F; m; m >>= 1)
             bits += m & 1u;
         if (bits > channels)
-            return cfail(ATG_ERR_INVALID, "channel mask names more channels than present");
+            return g_conv_err.fail(ATG_ERR_INVALID,
+                                   "channel mask names more channels than present");
         hipLaunchKernelGGL(k_pcm_downmix, grid, blk, 0, s, d_in, d_out, frames, channels,
                            mask & 0x3Fu, in_bps);
         break;
@@ -244,7 +235,7 @@ atg_status atg_pcm_convert_device(int kind, const int32_t *d_in, int32_t *d_out,
         hipLaunchKernelGGL(k_pcm_average, grid, blk, 0, s, d_in, d_out, frames, channels);
         break;
     default:
-        return cfail(ATG_ERR_INVALID, "unknown conversion");
+        return g_conv_err.fail(ATG_ERR_INVALID, "unknown conversion");
     }
     CHIP(hipGetLastError());
     return ATG_OK;
@@ -257,14 +248,14 @@ atg_status atg_pcm_convert_host(int device, int kind, const int32_t *in, int32_t
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return cfail(ATG_ERR_DEVICE, "no HIP device available");
+        return g_conv_err.fail(ATG_ERR_DEVICE, "no HIP device available");
     if (device < 0 || device >= n)
-        return cfail(ATG_ERR_INVALID, "device index out of range");
+        return g_conv_err.fail(ATG_ERR_INVALID, "device index out of range");
     CHIP(hipSetDevice(device));
     const uint32_t oc = atg_pcm_convert_out_channels(kind, channels);
     const uint64_t need_bits = frames * channels;
     if (kind == ATG_CONV_BPS && out_bps < in_bps && dither_bytes * 8 < need_bits + dither_bit0)
-        return cfail(ATG_ERR_INVALID, "not enough dither bytes");
+        return g_conv_err.fail(ATG_ERR_INVALID, "not enough dither bytes");
     void *di = nullptr, *dout = nullptr, *dd = nullptr;
     const size_t ib = sizeof(int32_t) * (frames * channels ? frames * channels : 1);
     const size_t ob = sizeof(int32_t) * (frames * oc ? frames * oc : 1);
@@ -273,13 +264,13 @@ atg_status atg_pcm_convert_host(int device, int kind, const int32_t *in, int32_t
         (void)hipFree(di);
         (void)hipFree(dout);
         (void)hipFree(dd);
-        return cfail(ATG_ERR_NOMEM, "device allocation failed");
+        return g_conv_err.fail(ATG_ERR_NOMEM, "device allocation failed");
     }
     atg_status st = ATG_OK;
     if (hipMemcpy(di, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
             hipSuccess ||
         (dither_bytes && hipMemcpy(dd, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
-        st = cfail(ATG_ERR_DEVICE, "copy to device failed");
+        st = g_conv_err.fail(ATG_ERR_DEVICE, "copy to device failed");
     if (st == ATG_OK)
         st = atg_pcm_convert_device(kind, (const int32_t *)di, (int32_t *)dout, frames, channels,
                                     channel_mask, in_bps, out_bps,
@@ -288,7 +279,7 @@ atg_status atg_pcm_convert_host(int device, int kind, const int32_t *in, int32_t
     if (st == ATG_OK &&
         (hipDeviceSynchronize() != hipSuccess ||
          hipMemcpy(out, dout, sizeof(int32_t) * frames * oc, hipMemcpyDeviceToHost) != hipSuccess))
-        st = cfail(ATG_ERR_DEVICE, "conversion failed on the device");
+        st = g_conv_err.fail(ATG_ERR_DEVICE, "conversion failed on the device");
     (void)hipFree(di);
     (void)hipFree(dout);
     (void)hipFree(dd);
@@ -311,9 +302,9 @@ atg_status atg_pcm_apply_gain_device(const int32_t *d_in, int32_t *d_out, uint64
                                      uint64_t dither_bit0, void *stream)
 {
     if (((!d_in || !d_out) && frames) || !d_dither)
-        return cfail(ATG_ERR_INVALID, "NULL buffer");
+        return g_conv_err.fail(ATG_ERR_INVALID, "NULL buffer");
     if (channels < 1 || bps < 1 || bps > 32 || chunk_frames < 1)
-        return cfail(ATG_ERR_INVALID, "bad channels / bits per sample / chunk");
+        return g_conv_err.fail(ATG_ERR_INVALID, "bad channels / bits per sample / chunk");
     if (!frames)
         return ATG_OK;
     hipLaunchKernelGGL(k_pcm_gain, dim3((unsigned)((frames * channels + 1023) / 1024)),
@@ -330,12 +321,12 @@ atg_status atg_pcm_apply_gain_host(int device, const int32_t *in, int32_t *out, 
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return cfail(ATG_ERR_DEVICE, "no HIP device available");
+        return g_conv_err.fail(ATG_ERR_DEVICE, "no HIP device available");
     if (device < 0 || device >= n)
-        return cfail(ATG_ERR_INVALID, "device index out of range");
+        return g_conv_err.fail(ATG_ERR_INVALID, "device index out of range");
     CHIP(hipSetDevice(device));
     if (dither_bytes * 8 < frames * channels + dither_bit0)
-        return cfail(ATG_ERR_INVALID, "not enough dither bytes");
+        return g_conv_err.fail(ATG_ERR_INVALID, "not enough dither bytes");
     void *di = nullptr, *dout = nullptr, *dd = nullptr;
     const size_t nb = sizeof(int32_t) * (frames * channels ? frames * channels : 1);
     if (hipMalloc(&di, nb) != hipSuccess || hipMalloc(&dout, nb) != hipSuccess ||
@@ -343,13 +334,13 @@ atg_status atg_pcm_apply_gain_host(int device, const int32_t *in, int32_t *out, 
         (void)hipFree(di);
         (void)hipFree(dout);
         (void)hipFree(dd);
-        return cfail(ATG_ERR_NOMEM, "device allocation failed");
+        return g_conv_err.fail(ATG_ERR_NOMEM, "device allocation failed");
     }
     atg_status st = ATG_OK;
     if (hipMemcpy(di, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
             hipSuccess ||
         (dither_bytes && hipMemcpy(dd, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
-        st = cfail(ATG_ERR_DEVICE, "copy to device failed");
+        st = g_conv_err.fail(ATG_ERR_DEVICE, "copy to device failed");
     if (st == ATG_OK)
         st = atg_pcm_apply_gain_device((const int32_t *)di, (int32_t *)dout, frames, channels,
                                        bps, multiplier, chunk_frames, (const uint8_t *)dd,
@@ -358,7 +349,7 @@ atg_status atg_pcm_apply_gain_host(int device, const int32_t *in, int32_t *out, 
         (hipDeviceSynchronize() != hipSuccess ||
          hipMemcpy(out, dout, sizeof(int32_t) * frames * channels, hipMemcpyDeviceToHost) !=
              hipSuccess))
-        st = cfail(ATG_ERR_DEVICE, "gain application failed on the device");
+        st = g_conv_err.fail(ATG_ERR_DEVICE, "gain application failed on the device");
     (void)hipFree(di);
     (void)hipFree(dout);
     (void)hipFree(dd);

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "host_common.h"
 #include "rg_coeffs.h"
 
 #pragma clang fp contract(off)
@@ -43,20 +44,8 @@ constexpr int kBins = 12000;
 __constant__ double c_yule[20][21];
 __constant__ double c_butter[20][5];
 
-thread_local std::string g_rg_err;
-
-atg_status rfail(atg_status s, const std::string &m)
-{
-    g_rg_err = m;
-    return s;
-}
-
-#define RHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return rfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
+thread_local ErrSlot g_rg_err;
+#define RHIP(expr) ATG_HIP_TRY(g_rg_err, expr, #expr)
 
 int freq_index(unsigned rate)
 {
@@ -523,30 +512,12 @@ __global__ __launch_bounds__(256) void k_rg_gain(const uint32_t *__restrict__ hi
 }
 
 // a device buffer that grows on demand
-struct RBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (p && bytes <= cap)
-            return hipSuccess;
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-};
-
 // device buffers of one device (kept across calls; a batch pipeline calls
 // this once per album batch)
 struct RgCtx {
     std::mutex mu;
     bool coeffs = false;
-    RBuf tracks, hist, peaks, gains, alb, meta, wsum, wbase, chunks, segs, seam_in, seam_out,
+    DevBuf tracks, hist, peaks, gains, alb, meta, wsum, wbase, chunks, segs, seam_in, seam_out,
         amax, dmax, warm, flag, tlist, amb, namb, mag;
 };
 constexpr int kMaxDevices = 64;
@@ -926,7 +897,7 @@ atg_status fetch_ambiguous(RgCtx &c, hipStream_t s, uint64_t cap, std::vector<ui
     RHIP(hipMemcpyAsync(&cnt, c.namb.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     RHIP(hipStreamSynchronize(s));
     if (cnt > cap)
-        return rfail(ATG_ERR_DEVICE, "ambiguous-window list overflow");
+        return g_rg_err.fail(ATG_ERR_DEVICE, "ambiguous-window list overflow");
     out.resize(cnt);
     if (cnt) {
         RHIP(hipMemcpyAsync(out.data(), c.amb.p, sizeof(uint4) * cnt, hipMemcpyDeviceToHost, s));
@@ -984,7 +955,7 @@ atg_status atg_replaygain_bound(uint32_t sample_rate, double *out)
 {
     const int fi = freq_index(sample_rate);
     if (fi < 0 || !out)
-        return rfail(ATG_ERR_INVALID, "unsupported sample rate");
+        return g_rg_err.fail(ATG_ERR_INVALID, "unsupported sample rate");
     const uint64_t L = rg_seg_len((uint32_t)std::ceil(sample_rate * 0.050));
     const RgBound b = rg_bound(fi, L);
     out[0] = b.gmax;
@@ -997,19 +968,19 @@ atg_status atg_replaygain_bound(uint32_t sample_rate, double *out)
 }
 
 
-const char *atg_replaygain_last_error(void) { return g_rg_err.c_str(); }
+const char *atg_replaygain_last_error(void) { return g_rg_err.msg.c_str(); }
 
 atg_status atg_replaygain_device(const int32_t *d_pcm, const atg_rg_track *tracks, uint32_t n,
                                  uint32_t n_albums, atg_rg_result *results,
                                  uint32_t *d_album_hist, double *album_peaks, void *stream)
 {
     if ((!tracks || !results) && n)
-        return rfail(ATG_ERR_INVALID, "NULL argument");
+        return g_rg_err.fail(ATG_ERR_INVALID, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
     int dev = 0;
     RHIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= kMaxDevices)
-        return rfail(ATG_ERR_UNSUPPORTED, "device index too large");
+        return g_rg_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
     RgCtx &g_ctx = g_ctxs[dev];
     std::lock_guard<std::mutex> lock(g_ctx.mu);
     if (!g_ctx.coeffs) {
@@ -1025,25 +996,26 @@ atg_status atg_replaygain_device(const int32_t *d_pcm, const atg_rg_track *track
         const atg_rg_track &a = tracks[t];
         const int fi = freq_index(a.sample_rate);
         if (fi < 0)
-            return rfail(ATG_ERR_INVALID, "unsupported sample rate");
+            return g_rg_err.fail(ATG_ERR_INVALID, "unsupported sample rate");
         if (a.channels != 1 && a.channels != 2)
-            return rfail(ATG_ERR_INVALID, "FrameList must contain only 1 or 2 channels");
+            return g_rg_err.fail(ATG_ERR_INVALID, "FrameList must contain only 1 or 2 channels");
         if (a.bits_per_sample != 8 && a.bits_per_sample != 16 && a.bits_per_sample != 24)
-            return rfail(ATG_ERR_INVALID, "unsupported bits per sample");
+            return g_rg_err.fail(ATG_ERR_INVALID, "unsupported bits per sample");
         if (n_albums && a.album >= n_albums)
-            return rfail(ATG_ERR_INVALID, "album index out of range");
+            return g_rg_err.fail(ATG_ERR_INVALID, "album index out of range");
         if (n_albums && t && a.album < tracks[t - 1].album)
-            return rfail(ATG_ERR_INVALID, "tracks must be grouped by album");
+            return g_rg_err.fail(ATG_ERR_INVALID, "tracks must be grouped by album");
         uint64_t cbase = ~0ull;
         if (a.chunk_frames) {
             uint64_t tot = 0;
             for (uint64_t i = 0; i < a.n_chunks; ++i) {
                 if (!a.chunk_frames[i])
-                    return rfail(ATG_ERR_INVALID, "read() chunk sizes must be positive");
+                    return g_rg_err.fail(ATG_ERR_INVALID, "read() chunk sizes must be positive");
                 tot += a.chunk_frames[i];
             }
             if (tot != a.pcm_frames)
-                return rfail(ATG_ERR_INVALID, "read() chunk sizes must add up to pcm_frames");
+                return g_rg_err.fail(ATG_ERR_INVALID,
+                                     "read() chunk sizes must add up to pcm_frames");
             cbase = chunks.size();
             chunks.insert(chunks.end(), a.chunk_frames, a.chunk_frames + a.n_chunks);
         }
@@ -1272,7 +1244,7 @@ atg_status atg_replaygain_hist_gain(const uint32_t *d_hist, uint32_t n, double *
         e = hipStreamSynchronize(s);
     (void)hipFree(d_g);
     if (e != hipSuccess)
-        return rfail(ATG_ERR_DEVICE, hipGetErrorString(e));
+        return g_rg_err.fail(ATG_ERR_DEVICE, hipGetErrorString(e));
     return ATG_OK;
 }
 

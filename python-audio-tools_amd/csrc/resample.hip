@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "host_common.h"
 #include "src_coeffs.h"
 
 #pragma clang fp contract(off)
@@ -666,20 +667,8 @@ template <int CH>
 constexpr int phase_m() { return CH <= 2 ? 5 : 2; }
 
 // ------------------------------------------------------------------ host
-thread_local std::string g_rs_err;
-
-atg_status rsfail(atg_status s, const std::string &m)
-{
-    g_rs_err = m;
-    return s;
-}
-
-#define RSHIP(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return rsfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
+thread_local ErrSlot g_rs_err;
+#define RSHIP(expr) ATG_HIP_TRY(g_rs_err, expr, #expr)
 
 double fmod_one(double x)
 {
@@ -999,10 +988,8 @@ hipError_t set_lds_attr()
 }
 
 struct RsCtx {
-    void *tracks = nullptr, *chunk_track = nullptr, *pos = nullptr, *table = nullptr,
-         *ids = nullptr, *ptasks = nullptr, *ctrack = nullptr, *tabs = nullptr;
-    size_t cap_tracks = 0, cap_chunks = 0, cap_pos = 0, cap_ids = 0, cap_ptasks = 0,
-           cap_ctrack = 0, cap_tabs = 0;
+    DevBuf tracks, chunk_track, pos, ids, ptasks, ctrack, tabs;
+    void *table = nullptr;
     bool table_up = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     float ms[2] = {0.0f, 0.0f};
@@ -1010,26 +997,11 @@ struct RsCtx {
 constexpr int kMaxDev = 64;
 RsCtx g_rs[kMaxDev];
 
-hipError_t grow(void *&p, size_t &cap, size_t bytes)
-{
-    if (p && bytes <= cap)
-        return hipSuccess;
-    if (p)
-        (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes, 256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess)
-        cap = want;
-    return e;
-}
-
 } // namespace
 
 extern "C" {
 
-const char *atg_resample_last_error(void) { return g_rs_err.c_str(); }
+const char *atg_resample_last_error(void) { return g_rs_err.msg.c_str(); }
 
 uint64_t atg_resample_output_frames(uint64_t in_frames, uint32_t channels, uint32_t in_rate,
                                     uint32_t out_rate)
@@ -1045,16 +1017,16 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
                                uint64_t *out_frames, void *stream)
 {
     if ((!tracks && n) || !out_offsets || !out_frames)
-        return rsfail(ATG_ERR_INVALID, "NULL argument");
+        return g_rs_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (channels < 1 || channels > 8)
-        return rsfail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
+        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
     if (bits_per_sample < 1 || bits_per_sample > 24)
-        return rsfail(ATG_ERR_UNSUPPORTED, "bits per sample must be 1..24");
+        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "bits per sample must be 1..24");
     hipStream_t s = (hipStream_t)stream;
     int dev = 0;
     RSHIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= kMaxDev)
-        return rsfail(ATG_ERR_UNSUPPORTED, "device index too large");
+        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
     RsCtx &X = g_rs[dev];
     std::vector<RsTrack> tr(n);
     std::vector<uint32_t> chunk_track, serial;
@@ -1064,10 +1036,10 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
     for (uint32_t t = 0; t < n; ++t) {
         const atg_rs_track &a = tracks[t];
         if (!a.in_rate || !a.out_rate)
-            return rsfail(ATG_ERR_INVALID, "sample rates must be positive");
+            return g_rs_err.fail(ATG_ERR_INVALID, "sample rates must be positive");
         conv[t] = make_conv(a.in_rate, a.out_rate);
         if (conv[t].ratio > 256.0 || conv[t].ratio < 1.0 / 256.0) // is_bad_src_ratio
-            return rsfail(ATG_ERR_INVALID, "SRC ratio outside [1/256, 256]");
+            return g_rs_err.fail(ATG_ERR_INVALID, "SRC ratio outside [1/256, 256]");
     }
     // Phase-sharing plan (k_rs_phase): a track whose rational ratio repeats
     // its phases every `period` outputs goes there when a task of 64 x lspan
@@ -1153,7 +1125,7 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
         }
     }
     if (!chunk)
-        return rsfail(ATG_ERR_UNSUPPORTED, "resampling ratio too low for the LDS window");
+        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "resampling ratio too low for the LDS window");
     std::vector<uint2> ptasks;
     size_t lds_phase = 0;
     // ratio classes of the phase tracks (one table set each)
@@ -1218,7 +1190,8 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
         out += T.out_frames;
     }
     if (out * channels > out_cap_samples)
-        return rsfail(ATG_ERR_CAPACITY, "output buffer too small (atg_resample_output_frames)");
+        return g_rs_err.fail(ATG_ERR_CAPACITY,
+                             "output buffer too small (atg_resample_output_frames)");
     if (!X.table_up) {
         RSHIP(hipMalloc(&X.table, sizeof(SRC_MEDIUM_BITS)));
         RSHIP(hipMemcpy(X.table, SRC_MEDIUM_BITS, sizeof(SRC_MEDIUM_BITS), hipMemcpyHostToDevice));
@@ -1234,33 +1207,33 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
         RSHIP(set_lds_attr<8>());
         X.table_up = true;
     }
-    RSHIP(grow(X.tracks, X.cap_tracks, sizeof(RsTrack) * std::max<uint32_t>(n, 1)));
-    RSHIP(grow(X.chunk_track, X.cap_chunks, sizeof(uint32_t) * std::max<size_t>(chunk_track.size(), 1)));
-    RSHIP(grow(X.pos, X.cap_pos, sizeof(int2) * std::max<uint64_t>(posn, 1)));
-    RSHIP(grow(X.ids, X.cap_ids, sizeof(uint32_t) * std::max<size_t>(serial.size(), 1)));
-    RSHIP(grow(X.ptasks, X.cap_ptasks, sizeof(uint2) * std::max<size_t>(ptasks.size(), 1)));
+    RSHIP(X.tracks.ensure(sizeof(RsTrack) * std::max<uint32_t>(n, 1)));
+    RSHIP(X.chunk_track.ensure(sizeof(uint32_t) * std::max<size_t>(chunk_track.size(), 1)));
+    RSHIP(X.pos.ensure(sizeof(int2) * std::max<uint64_t>(posn, 1)));
+    RSHIP(X.ids.ensure(sizeof(uint32_t) * std::max<size_t>(serial.size(), 1)));
+    RSHIP(X.ptasks.ensure(sizeof(uint2) * std::max<size_t>(ptasks.size(), 1)));
     const uint64_t tab_stride = kTabHdr + 2ull * pm * wmax;
-    RSHIP(grow(X.ctrack, X.cap_ctrack, sizeof(uint32_t) * std::max<size_t>(class_track.size(), 1)));
-    RSHIP(grow(X.tabs, X.cap_tabs,
-               sizeof(double) * std::max<uint64_t>(tab_stride * tab_G * class_track.size(), 1)));
+    RSHIP(X.ctrack.ensure(sizeof(uint32_t) * std::max<size_t>(class_track.size(), 1)));
+    RSHIP(X.tabs.ensure(sizeof(double) *
+                        std::max<uint64_t>(tab_stride * tab_G * class_track.size(), 1)));
     if (!class_track.empty())
-        RSHIP(hipMemcpyAsync(X.ctrack, class_track.data(), sizeof(uint32_t) * class_track.size(),
+        RSHIP(hipMemcpyAsync(X.ctrack.p, class_track.data(), sizeof(uint32_t) * class_track.size(),
                              hipMemcpyHostToDevice, s));
     if (!ptasks.empty())
-        RSHIP(hipMemcpyAsync(X.ptasks, ptasks.data(), sizeof(uint2) * ptasks.size(),
+        RSHIP(hipMemcpyAsync(X.ptasks.p, ptasks.data(), sizeof(uint2) * ptasks.size(),
                              hipMemcpyHostToDevice, s));
     if (n)
-        RSHIP(hipMemcpyAsync(X.tracks, tr.data(), sizeof(RsTrack) * n, hipMemcpyHostToDevice, s));
+        RSHIP(hipMemcpyAsync(X.tracks.p, tr.data(), sizeof(RsTrack) * n, hipMemcpyHostToDevice, s));
     if (!chunk_track.empty())
-        RSHIP(hipMemcpyAsync(X.chunk_track, chunk_track.data(),
+        RSHIP(hipMemcpyAsync(X.chunk_track.p, chunk_track.data(),
                              sizeof(uint32_t) * chunk_track.size(), hipMemcpyHostToDevice, s));
     RSHIP(hipEventRecord(X.ev[0], s));
     if (!serial.empty()) {
-        RSHIP(hipMemcpyAsync(X.ids, serial.data(), sizeof(uint32_t) * serial.size(),
+        RSHIP(hipMemcpyAsync(X.ids.p, serial.data(), sizeof(uint32_t) * serial.size(),
                              hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_rs_positions, dim3((unsigned)((serial.size() + 63) / 64)),
-                           dim3(64), 0, s, (const RsTrack *)X.tracks,
-                           (const uint32_t *)X.ids, (uint32_t)serial.size(), (int2 *)X.pos);
+                           dim3(64), 0, s, (const RsTrack *)X.tracks.p,
+                           (const uint32_t *)X.ids.p, (uint32_t)serial.size(), (int2 *)X.pos.p);
         RSHIP(hipGetLastError());
     }
     RsParams P;
@@ -1276,8 +1249,8 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
     RSHIP(hipEventRecord(X.ev[1], s));
     if (P.n_chunks) {
         const unsigned grid = std::min<uint32_t>(P.n_chunks, 256u);
-        const FilterArgs A{P, (const RsTrack *)X.tracks, (const uint32_t *)X.chunk_track,
-                           (const int2 *)X.pos, (const uint32_t *)X.table, d_in, d_out};
+        const FilterArgs A{P, (const RsTrack *)X.tracks.p, (const uint32_t *)X.chunk_track.p,
+                           (const int2 *)X.pos.p, (const uint32_t *)X.table, d_in, d_out};
         switch (channels) {
         case 1: launch_filter<1>(A, hoist, xd, grid, chunk, lds, s); break;
         case 2: launch_filter<2>(A, hoist, xd, grid, chunk, lds, s); break;
@@ -1291,14 +1264,14 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
         RSHIP(hipGetLastError());
     }
     if (!ptasks.empty()) {
-        const FilterArgs A{P, (const RsTrack *)X.tracks, (const uint32_t *)X.chunk_track,
-                           (const int2 *)X.pos, (const uint32_t *)X.table, d_in, d_out};
+        const FilterArgs A{P, (const RsTrack *)X.tracks.p, (const uint32_t *)X.chunk_track.p,
+                           (const int2 *)X.pos.p, (const uint32_t *)X.table, d_in, d_out};
         const unsigned per_cu = lds_phase <= kLds / 2 ? 2u : 1u;
         const unsigned grid = (unsigned)std::min<size_t>(ptasks.size(), 256u * per_cu);
-        const uint2 *tk = (const uint2 *)X.ptasks;
+        const uint2 *tk = (const uint2 *)X.ptasks.p;
         const uint32_t nt = (uint32_t)ptasks.size();
-        const PhaseTabs pt{(const uint32_t *)X.ctrack, (uint32_t)class_track.size(), tab_G,
-                           (double *)X.tabs, tab_stride};
+        const PhaseTabs pt{(const uint32_t *)X.ctrack.p, (uint32_t)class_track.size(), tab_G,
+                           (double *)X.tabs.p, tab_stride};
         switch (channels) {
         case 1: launch_phase<1>(A, tk, nt, wmax, grid, lds_phase, pt, s); break;
         case 2: launch_phase<2>(A, tk, nt, wmax, grid, lds_phase, pt, s); break;
@@ -1341,32 +1314,33 @@ atg_status atg_resample_host(int device, const atg_rs_track *tracks, uint32_t n,
 {
     RSHIP(hipSetDevice(device));
     if (channels < 1 || channels > 8)
-        return rsfail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
+        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
     uint64_t total = 0;
     for (uint32_t t = 0; t < n; ++t) {
         if (!tracks[t].in_rate || !tracks[t].out_rate)
-            return rsfail(ATG_ERR_INVALID, "sample rates must be positive");
+            return g_rs_err.fail(ATG_ERR_INVALID, "sample rates must be positive");
         total += output_frames(make_conv(tracks[t].in_rate, tracks[t].out_rate), channels,
                                tracks[t].pcm_frames, tracks[t].reads, tracks[t].n_reads);
     }
     if (total * channels > out_cap_samples)
-        return rsfail(ATG_ERR_CAPACITY, "output buffer too small (atg_resample_output_frames)");
+        return g_rs_err.fail(ATG_ERR_CAPACITY,
+                             "output buffer too small (atg_resample_output_frames)");
     int32_t *d_in = nullptr, *d_out = nullptr;
     RSHIP(hipMalloc(&d_in, std::max<uint64_t>(in_samples, 1) * 4));
     hipError_t e = hipMalloc(&d_out, std::max<uint64_t>(total * channels, 1) * 4);
     if (e != hipSuccess) {
         (void)hipFree(d_in);
-        return rsfail(ATG_ERR_NOMEM, hipGetErrorString(e));
+        return g_rs_err.fail(ATG_ERR_NOMEM, hipGetErrorString(e));
     }
     atg_status st = ATG_OK;
     if (in_samples && hipMemcpy(d_in, in, in_samples * 4, hipMemcpyHostToDevice) != hipSuccess)
-        st = rsfail(ATG_ERR_DEVICE, "hipMemcpy input");
+        st = g_rs_err.fail(ATG_ERR_DEVICE, "hipMemcpy input");
     if (st == ATG_OK)
         st = atg_resample_device(tracks, n, channels, bits_per_sample, d_in, d_out,
                                  total * channels, out_offsets, out_frames, nullptr);
     if (st == ATG_OK && total &&
         hipMemcpy(out, d_out, total * channels * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        st = rsfail(ATG_ERR_DEVICE, "hipMemcpy output");
+        st = g_rs_err.fail(ATG_ERR_DEVICE, "hipMemcpy output");
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return st;

@@ -26,6 +26,7 @@
 //
 // A track's PCM ends before its first bad frame.
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -255,46 +256,8 @@ __global__ __launch_bounds__(256) void k_ttad_out(const Frame *__restrict__ fram
 }
 
 // ------------------------------------------------------------------- host
-thread_local std::string g_ttad_err;
-
-atg_status dfail(atg_status s, const std::string &m)
-{
-    g_ttad_err = m;
-    return s;
-}
-
-#define DHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return dfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_ttad_err;
+#define DHIP(expr) ATG_HIP_TRY(g_ttad_err, expr, #expr)
 
 const int kDTimed = 5;
 const char *kDNames[kDTimed] = {"ttad_crc", "ttad_parse", "ttad_chain", "ttad_out",
@@ -313,14 +276,8 @@ uint32_t host_crc32(const uint8_t *p, uint64_t n)
 
 } // namespace
 
-struct atg_tta_decoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[kDTimed] = {};
-    float times[kDTimed] = {};
-    bool have_times = false;
-    DBuf frames, chain_frame, status, resid, pcm, wide, h_data;
+struct atg_tta_decoder : StageHandle<kDTimed> {
+    DevBuf frames, chain_frame, status, resid, pcm, wide, h_data;
     uint64_t last_samples = 0;
 };
 
@@ -342,15 +299,15 @@ atg_status ttad_run(atg_tta_decoder *dec, const uint8_t *d_data, uint64_t len,
     for (uint32_t t = 0; t < n; ++t) {
         const atg_tta_dec_track &T = tracks[t];
         if (T.channels < 1 || T.channels > 65535)
-            return dfail(ATG_ERR_INVALID, "channels must be 1..65535");
+            return g_ttad_err.fail(ATG_ERR_INVALID, "channels must be 1..65535");
         if (T.bits_per_sample != 8 && T.bits_per_sample != 16 && T.bits_per_sample != 24)
-            return dfail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
+            return g_ttad_err.fail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
         if (T.block_size < 1)
-            return dfail(ATG_ERR_INVALID, "block_size must be at least 1");
+            return g_ttad_err.fail(ATG_ERR_INVALID, "block_size must be at least 1");
         if (T.data_offset > len || T.data_bytes > len - T.data_offset)
-            return dfail(ATG_ERR_INVALID, "track data outside the buffer");
+            return g_ttad_err.fail(ATG_ERR_INVALID, "track data outside the buffer");
         if (T.n_frame_bytes && !T.frame_bytes)
-            return dfail(ATG_ERR_INVALID, "frame_bytes is NULL");
+            return g_ttad_err.fail(ATG_ERR_INVALID, "frame_bytes is NULL");
         wide = wide || T.channels > kMaxCh;
         if (T.channels != uniform || T.channels > 2)
             uniform = 0;
@@ -381,7 +338,7 @@ atg_status ttad_run(atg_tta_decoder *dec, const uint8_t *d_data, uint64_t len,
                 chain_frame.push_back((uint32_t)frames.size());
             frames.push_back(f);
             if (frames.size() > 0x7FFFFFFFull)
-                return dfail(ATG_ERR_UNSUPPORTED, "too many TTA frames in one batch");
+                return g_ttad_err.fail(ATG_ERR_UNSUPPORTED, "too many TTA frames in one batch");
             samples += (uint64_t)nf * T.channels;
             out_samples += (uint64_t)nf * T.channels;
             max_n = std::max(max_n, nf);
@@ -431,7 +388,7 @@ atg_status ttad_run(atg_tta_decoder *dec, const uint8_t *d_data, uint64_t len,
     if (nfr) {
         const uint64_t per = ((uint64_t)max_n + 255) / 256;
         if (per * nfr > 0x7FFFFFFFull)
-            return dfail(ATG_ERR_UNSUPPORTED, "batch too large for one launch");
+            return g_ttad_err.fail(ATG_ERR_UNSUPPORTED, "batch too large for one launch");
         hipLaunchKernelGGL(k_ttad_out, dim3((unsigned)(per * nfr)), dim3(256), 0, s, dfr,
                            (uint32_t)per, (const int32_t *)dst, (const int32_t *)dec->resid.p,
                            (int32_t *)dec->pcm.p);
@@ -442,10 +399,7 @@ atg_status ttad_run(atg_tta_decoder *dec, const uint8_t *d_data, uint64_t len,
     if (nfr)
         DHIP(hipMemcpyAsync(st.data(), dst, sizeof(int32_t) * nfr, hipMemcpyDeviceToHost, s));
     DHIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kDTimed - 1; ++k)
-        (void)hipEventElapsedTime(&dec->times[k], dec->ev[k], dec->ev[k + 1]);
-    (void)hipEventElapsedTime(&dec->times[kDTimed - 1], dec->ev[0], dec->ev[kDTimed - 1]);
-    dec->have_times = true;
+    dec->finish_times();
     dec->last_samples = out_samples;
     for (uint32_t t = 0; t < n; ++t) {
         atg_tta_dec_result &r = res[t];
@@ -474,7 +428,7 @@ atg_status ttad_run(atg_tta_decoder *dec, const uint8_t *d_data, uint64_t len,
 
 extern "C" {
 
-const char *atg_tta_decoder_last_error(void) { return g_ttad_err.c_str(); }
+const char *atg_tta_decoder_last_error(void) { return g_ttad_err.msg.c_str(); }
 
 int atg_tta_read_info(const uint8_t *data, uint64_t len, atg_tta_info *info,
                       uint32_t *frame_bytes, uint32_t cap, uint32_t *n_frame_bytes)
@@ -544,44 +498,14 @@ int atg_tta_read_info(const uint8_t *data, uint64_t len, atg_tta_info *info,
 
 atg_status atg_tta_decoder_create(int device, atg_tta_decoder **out)
 {
-    if (!out)
-        return dfail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return dfail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return dfail(ATG_ERR_INVALID, "device index out of range");
-    DHIP(hipSetDevice(device));
-    atg_tta_decoder *d = new atg_tta_decoder();
-    d->device = device;
-    hipError_t err = hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking);
-    for (auto &ev : d->ev)
-        if (err == hipSuccess)
-            err = hipEventCreate(&ev);
-    if (err != hipSuccess) { // give back what was made: events and stream may be null
-        atg_tta_decoder_destroy(d);
-        return dfail(ATG_ERR_DEVICE, std::string("decoder create: ") + hipGetErrorString(err));
-    }
-    *out = d;
-    return ATG_OK;
+    return open_handle(device, out, g_ttad_err, "decoder create");
 }
 
 void atg_tta_decoder_destroy(atg_tta_decoder *d)
 {
     if (!d)
         return;
-    (void)hipSetDevice(d->device);
-    if (d->s)
-        (void)hipStreamSynchronize(d->s);
-    for (DBuf *b : {&d->frames, &d->chain_frame, &d->status, &d->resid, &d->pcm, &d->wide,
-                    &d->h_data})
-        b->release();
-    for (auto &ev : d->ev)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    if (d->s)
-        (void)hipStreamDestroy(d->s);
+    d->close({&d->frames, &d->chain_frame, &d->status, &d->resid, &d->pcm, &d->wide, &d->h_data});
     delete d;
 }
 
@@ -592,9 +516,9 @@ atg_status atg_tta_decode_device(atg_tta_decoder *d, const void *d_data, uint64_
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!d_data && len))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_ttad_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_data) & 3)
-        return dfail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
+        return g_ttad_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
     DHIP(hipSetDevice(d->device));
     atg_status st = ttad_run(d, (const uint8_t *)d_data, len, tracks, n, results, total_samples);
     if (st == ATG_OK && d_pcm)
@@ -608,7 +532,7 @@ atg_status atg_tta_decode_host(atg_tta_decoder *d, const uint8_t *data, uint64_t
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!data && len))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_ttad_err.fail(ATG_ERR_INVALID, "NULL argument");
     DHIP(hipSetDevice(d->device));
     DHIP(d->h_data.ensure(std::max<uint64_t>(len, 4)));
     if (len)
@@ -620,9 +544,9 @@ atg_status atg_tta_decode_fetch(atg_tta_decoder *d, int32_t *pcm, uint64_t pcm_c
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!pcm && pcm_cap))
-        return dfail(ATG_ERR_INVALID, "NULL argument");
+        return g_ttad_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (pcm_cap < d->last_samples)
-        return dfail(ATG_ERR_CAPACITY, "pcm buffer smaller than the decoded batch");
+        return g_ttad_err.fail(ATG_ERR_CAPACITY, "pcm buffer smaller than the decoded batch");
     DHIP(hipSetDevice(d->device));
     if (d->last_samples)
         DHIP(hipMemcpyAsync(pcm, d->pcm.p, sizeof(int32_t) * d->last_samples,
@@ -634,16 +558,7 @@ atg_status atg_tta_decode_fetch(atg_tta_decoder *d, int32_t *pcm, uint64_t pcm_c
 int atg_tta_decoder_kernel_times(atg_tta_decoder *d, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(d);
-    if (!d || !d->have_times)
-        return 0;
-    const int k = cap < kDTimed ? cap : kDTimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kDNames[i];
-        if (ms)
-            ms[i] = d->times[i];
-    }
-    return k;
+    return d ? d->report(kDNames, names, ms, cap) : 0;
 }
 
 } // extern "C"

@@ -30,6 +30,7 @@
 //   k_tta_crc     one workgroup per frame: CRC-32 over the payload in 256
 //                 pieces combined by polynomial arithmetic (tta_common.h).
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -224,46 +225,8 @@ __global__ __launch_bounds__(256) void k_tta_crc(const Frame *__restrict__ frame
 }
 
 // ------------------------------------------------------------------- host
-thread_local std::string g_tta_err;
-
-atg_status tfail(atg_status s, const std::string &m)
-{
-    g_tta_err = m;
-    return s;
-}
-
-#define THIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return tfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct TBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_tta_err;
+#define THIP(expr) ATG_HIP_TRY(g_tta_err, expr, #expr)
 
 // "tta_size" is everything between the chain and the pack: the copy of the
 // chains' totals, the host's extents, the frame table's second upload and the
@@ -273,14 +236,8 @@ const char *kTNames[kTTimed] = {"tta_chain", "tta_size", "tta_pack", "tta_crc", 
 
 } // namespace
 
-struct atg_tta_encoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[5] = {};
-    float times[kTTimed] = {};
-    bool have_times = false;
-    TBuf frames, chain_frame, pre, tail, chain_bits, h_pcm, h_out;
+struct atg_tta_encoder : StageHandle<kTTimed> {
+    DevBuf frames, chain_frame, pre, tail, chain_bits, h_pcm, h_out;
 };
 
 namespace {
@@ -297,12 +254,12 @@ atg_status tta_plan(const atg_track *tracks, uint32_t n, uint32_t channels, uint
                     uint32_t sample_rate, TPlan &P)
 {
     if (bps != 8 && bps != 16 && bps != 24)
-        return tfail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
+        return g_tta_err.fail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
     if (channels < 1 || channels > 65535)
-        return tfail(ATG_ERR_INVALID, "channels must be 1..65535");
+        return g_tta_err.fail(ATG_ERR_INVALID, "channels must be 1..65535");
     const uint64_t block = ((uint64_t)sample_rate * 256u) / 245u;
     if (block < 1 || block > 0xFFFFFFFFull)
-        return tfail(ATG_ERR_INVALID, "sample rate gives no usable TTA block size");
+        return g_tta_err.fail(ATG_ERR_INVALID, "sample rate gives no usable TTA block size");
     P.first.assign(n, 0);
     P.count.assign(n, 0);
     for (uint32_t t = 0; t < n; ++t) {
@@ -329,25 +286,25 @@ atg_status tta_plan(const atg_track *tracks, uint32_t n, uint32_t channels, uint
             for (uint64_t k = 0; k < T.n_frame_sizes; ++k) {
                 const uint32_t len = T.frame_sizes[k];
                 if (len < 1)
-                    return tfail(ATG_ERR_INVALID, "frame sizes must be at least 1");
+                    return g_tta_err.fail(ATG_ERR_INVALID, "frame sizes must be at least 1");
                 add(pos, len);
                 pos += len;
             }
             if (pos != T.pcm_frames)
-                return tfail(ATG_ERR_INVALID, "frame sizes must sum to pcm_frames");
+                return g_tta_err.fail(ATG_ERR_INVALID, "frame sizes must sum to pcm_frames");
         } else {
             for (uint64_t pos = 0; pos < T.pcm_frames; pos += block)
                 add(pos, (uint32_t)std::min<uint64_t>(block, T.pcm_frames - pos));
         }
         if (P.frames.size() > 0x7FFFFFFFull)
-            return tfail(ATG_ERR_UNSUPPORTED, "too many TTA frames in one batch");
+            return g_tta_err.fail(ATG_ERR_UNSUPPORTED, "too many TTA frames in one batch");
         P.count[t] = (uint32_t)P.frames.size() - P.first[t];
     }
     return ATG_OK;
 }
 
 template <typename T>
-atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_out, TBuf *stage,
+atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_out, DevBuf *stage,
                    uint64_t out_cap, uint32_t n, atg_tta_track_result *res,
                    uint32_t *frame_bytes, uint64_t *needed, uint64_t *out_bytes)
 {
@@ -397,7 +354,7 @@ atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_ou
             const uint64_t payload = (bits + 7) / 8;
             // the running lengths are 32-bit, and the seektable entry too
             if (bits > 0xFFFFFFFFull || payload + 4 > 0xFFFFFFFFull)
-                return tfail(ATG_ERR_UNSUPPORTED, "a TTA frame longer than 2^32 bits");
+                return g_tta_err.fail(ATG_ERR_UNSUPPORTED, "a TTA frame longer than 2^32 bits");
             f.byte_off = pos;
             f.payload = (uint32_t)payload;
             if (frame_bytes)
@@ -412,7 +369,7 @@ atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_ou
     if (out_bytes)
         *out_bytes = pos;
     if (pos > out_cap)
-        return tfail(ATG_ERR_CAPACITY, "output buffer smaller than the encoded batch");
+        return g_tta_err.fail(ATG_ERR_CAPACITY, "output buffer smaller than the encoded batch");
     if (stage) { // host call: the device image is sized from the length pass
         THIP(stage->ensure(std::max<uint64_t>(pos, 4)));
         d_out = (uint8_t *)stage->p;
@@ -429,7 +386,7 @@ atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_ou
                              kPackThreads;
         const uint64_t blocks = per * nfr;
         if (per > 0xFFFFFFFFull || blocks > 0x7FFFFFFFull)
-            return tfail(ATG_ERR_UNSUPPORTED, "batch too large for one pack launch");
+            return g_tta_err.fail(ATG_ERR_UNSUPPORTED, "batch too large for one pack launch");
         hipLaunchKernelGGL(k_tta_pack, dim3((unsigned)blocks), dim3(kPackThreads), 0, s,
                            (const Frame *)enc->frames.p, (uint32_t)per,
                            (const uint32_t *)enc->pre.p, (const uint32_t *)enc->tail.p,
@@ -443,10 +400,7 @@ atg_status tta_run(atg_tta_encoder *enc, TPlan &P, const T *d_pcm, uint8_t *d_ou
     THIP(hipGetLastError());
     THIP(hipEventRecord(enc->ev[4], s));
     THIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kTTimed - 1; ++k)
-        (void)hipEventElapsedTime(&enc->times[k], enc->ev[k], enc->ev[k + 1]);
-    (void)hipEventElapsedTime(&enc->times[kTTimed - 1], enc->ev[0], enc->ev[kTTimed - 1]);
-    enc->have_times = true;
+    enc->finish_times();
     return ATG_OK;
 }
 
@@ -454,11 +408,11 @@ atg_status tta_check(atg_tta_encoder *e, const atg_track *tracks, uint32_t n,
                      atg_tta_track_result *results, atg_pcm_format fmt, uint32_t bps)
 {
     if (!e || (!tracks && n) || (!results && n))
-        return tfail(ATG_ERR_INVALID, "NULL argument");
+        return g_tta_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (fmt != ATG_PCM_S16 && fmt != ATG_PCM_S32)
-        return tfail(ATG_ERR_INVALID, "unknown PCM format");
+        return g_tta_err.fail(ATG_ERR_INVALID, "unknown PCM format");
     if (fmt == ATG_PCM_S16 && bps > 16)
-        return tfail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
+        return g_tta_err.fail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
     return ATG_OK;
 }
 
@@ -466,48 +420,19 @@ atg_status tta_check(atg_tta_encoder *e, const atg_track *tracks, uint32_t n,
 
 extern "C" {
 
-const char *atg_tta_last_error(void) { return g_tta_err.c_str(); }
+const char *atg_tta_last_error(void) { return g_tta_err.msg.c_str(); }
 
 atg_status atg_tta_encoder_create(int device, atg_tta_encoder **out)
 {
-    if (!out)
-        return tfail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return tfail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return tfail(ATG_ERR_INVALID, "device index out of range");
-    THIP(hipSetDevice(device));
-    atg_tta_encoder *e = new atg_tta_encoder();
-    e->device = device;
-    hipError_t err = hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking);
-    for (auto &ev : e->ev)
-        if (err == hipSuccess)
-            err = hipEventCreate(&ev);
-    if (err != hipSuccess) { // give back what was made: events and stream may be null
-        atg_tta_encoder_destroy(e);
-        return tfail(ATG_ERR_DEVICE, std::string("encoder create: ") + hipGetErrorString(err));
-    }
-    *out = e;
-    return ATG_OK;
+    return open_handle(device, out, g_tta_err, "encoder create");
 }
 
 void atg_tta_encoder_destroy(atg_tta_encoder *e)
 {
     if (!e)
         return;
-    (void)hipSetDevice(e->device);
-    if (e->s)
-        (void)hipStreamSynchronize(e->s);
-    for (TBuf *b : {&e->frames, &e->chain_frame, &e->pre, &e->tail, &e->chain_bits, &e->h_pcm,
-                    &e->h_out})
-        b->release();
-    for (auto &ev : e->ev)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    if (e->s)
-        (void)hipStreamDestroy(e->s);
+    e->close({&e->frames, &e->chain_frame, &e->pre, &e->tail, &e->chain_bits, &e->h_pcm,
+              &e->h_out});
     delete e;
 }
 
@@ -523,14 +448,15 @@ atg_status atg_tta_encode_device(atg_tta_encoder *e, const void *d_pcm, atg_pcm_
     if (st != ATG_OK)
         return st;
     if (((uintptr_t)d_out) & 3)
-        return tfail(ATG_ERR_INVALID, "d_out must be 4-byte aligned");
+        return g_tta_err.fail(ATG_ERR_INVALID, "d_out must be 4-byte aligned");
     THIP(hipSetDevice(e->device));
     TPlan P;
     st = tta_plan(tracks, n, channels, bps, sample_rate, P);
     if (st != ATG_OK)
         return st;
     if (frame_bytes && frame_bytes_cap < P.frames.size())
-        return tfail(ATG_ERR_INVALID, "frame_bytes holds fewer entries than the batch has frames");
+        return g_tta_err.fail(ATG_ERR_INVALID,
+                              "frame_bytes holds fewer entries than the batch has frames");
     if (fmt == ATG_PCM_S16)
         return tta_run(e, P, (const int16_t *)d_pcm, (uint8_t *)d_out, nullptr, out_cap, n, results,
                        frame_bytes, needed, nullptr);
@@ -550,14 +476,15 @@ atg_status atg_tta_encode_host(atg_tta_encoder *e, const void *pcm, atg_pcm_form
     if (st != ATG_OK)
         return st;
     if (!pcm && n)
-        return tfail(ATG_ERR_INVALID, "NULL argument");
+        return g_tta_err.fail(ATG_ERR_INVALID, "NULL argument");
     THIP(hipSetDevice(e->device));
     TPlan P;
     st = tta_plan(tracks, n, channels, bps, sample_rate, P);
     if (st != ATG_OK)
         return st;
     if (frame_bytes && frame_bytes_cap < P.frames.size())
-        return tfail(ATG_ERR_INVALID, "frame_bytes holds fewer entries than the batch has frames");
+        return g_tta_err.fail(ATG_ERR_INVALID,
+                              "frame_bytes holds fewer entries than the batch has frames");
     uint64_t frames = 0;
     for (uint32_t t = 0; t < n; ++t)
         frames = std::max<uint64_t>(frames, tracks[t].pcm_offset + tracks[t].pcm_frames);
@@ -583,16 +510,7 @@ atg_status atg_tta_encode_host(atg_tta_encoder *e, const void *pcm, atg_pcm_form
 int atg_tta_encoder_kernel_times(atg_tta_encoder *e, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(e);
-    if (!e || !e->have_times)
-        return 0;
-    const int k = cap < kTTimed ? cap : kTTimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kTNames[i];
-        if (ms)
-            ms[i] = e->times[i];
-    }
-    return k;
+    return e ? e->report(kTNames, names, ms, cap) : 0;
 }
 
 } // extern "C"

@@ -29,6 +29,7 @@
 // where there is one, is checked on the host (md5_cpu.h) over the PCM in its
 // file byte form.
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -587,46 +588,8 @@ __global__ __launch_bounds__(256) void k_wvd_out(const Block *__restrict__ block
 }
 
 // ------------------------------------------------------------------- host
-thread_local std::string g_wvd_err;
-
-atg_status wfail(atg_status s, const std::string &m)
-{
-    g_wvd_err = m;
-    return s;
-}
-
-#define WHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return wfail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct WBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_wvd_err;
+#define WHIP(expr) ATG_HIP_TRY(g_wvd_err, expr, #expr)
 
 const int kWTimed = 4;
 const char *kWNames[kWTimed] = {"wvd_parse", "wvd_decorr", "wvd_out", "wvd_total"};
@@ -703,14 +666,8 @@ uint32_t rd_le(const uint8_t *p, uint32_t n)
 
 } // namespace
 
-struct atg_wv_decoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[kWTimed] = {};
-    float times[kWTimed] = {};
-    bool have_times = false;
-    WBuf blocks, params, status, resid, pcm, table, h_data;
+struct atg_wv_decoder : StageHandle<kWTimed> {
+    DevBuf blocks, params, status, resid, pcm, table, h_data;
     uint64_t last_samples = 0;
 };
 
@@ -729,16 +686,17 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
     for (uint32_t t = 0; t < n; ++t) {
         const atg_wv_dec_track &T = tracks[t];
         if (T.channels < 1 || T.channels > 256)
-            return wfail(ATG_ERR_INVALID, "channels must be 1..256");
+            return g_wvd_err.fail(ATG_ERR_INVALID, "channels must be 1..256");
         if (T.bits_per_sample != 8 && T.bits_per_sample != 16 && T.bits_per_sample != 24 &&
             T.bits_per_sample != 32)
-            return wfail(ATG_ERR_INVALID, "bits per sample must be 8, 16, 24 or 32");
+            return g_wvd_err.fail(ATG_ERR_INVALID, "bits per sample must be 8, 16, 24 or 32");
         if (T.data_offset > len || T.data_bytes > len - T.data_offset || (T.data_offset & 3))
-            return wfail(ATG_ERR_INVALID, "track data outside the buffer or not 4-byte aligned");
+            return g_wvd_err.fail(ATG_ERR_INVALID,
+                                  "track data outside the buffer or not 4-byte aligned");
         if (T.n_blocks && !T.blocks)
-            return wfail(ATG_ERR_INVALID, "blocks is NULL");
+            return g_wvd_err.fail(ATG_ERR_INVALID, "blocks is NULL");
         if (T.tail_blocks > T.n_blocks)
-            return wfail(ATG_ERR_INVALID, "tail_blocks exceeds n_blocks");
+            return g_wvd_err.fail(ATG_ERR_INVALID, "tail_blocks exceeds n_blocks");
         first[t] = (uint32_t)blocks.size();
         first_set[t] = (uint32_t)set_blocks.size();
         res[t].sample_offset = out_samples;
@@ -752,24 +710,26 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
             const bool tail = k >= body;
             if (S.offset > T.data_bytes || T.data_bytes - S.offset < 32 ||
                 T.data_bytes - S.offset - 32 < S.size)
-                return wfail(ATG_ERR_INVALID, "block outside its image");
+                return g_wvd_err.fail(ATG_ERR_INVALID, "block outside its image");
             if (k == body && in_set)
-                return wfail(ATG_ERR_INVALID, "the last set has no final block");
+                return g_wvd_err.fail(ATG_ERR_INVALID, "the last set has no final block");
             if (tail && (S.flags & wv::kFinal))
-                return wfail(ATG_ERR_INVALID, "a tail block cannot be a set's final block");
+                return g_wvd_err.fail(ATG_ERR_INVALID,
+                                      "a tail block cannot be a set's final block");
             if (in_set == 0) {
                 set_n = S.block_samples;
                 chans = 0;
                 set_base = out_samples;
             } else if (S.block_samples != set_n) {
-                return wfail(ATG_ERR_INVALID, "blocks of a set disagree on block_samples");
+                return g_wvd_err.fail(ATG_ERR_INVALID, "blocks of a set disagree on block_samples");
             }
             const uint32_t oc = wv::out_channels(S.flags);
             if (chans + oc > T.channels)
-                return wfail(ATG_ERR_INVALID, "a set has more channels than its track");
+                return g_wvd_err.fail(ATG_ERR_INVALID, "a set has more channels than its track");
             frames += in_set == 0 && !tail ? set_n : 0;
             if (frames > 0xFFFFFFFFull || set_n > 0x7FFFFFFFu)
-                return wfail(ATG_ERR_INVALID, "track longer than a WavPack stream can declare");
+                return g_wvd_err.fail(ATG_ERR_INVALID,
+                                      "track longer than a WavPack stream can declare");
             Block b;
             std::memset(&b, 0, sizeof(b));
             b.byte_off = T.data_offset + S.offset + 32;
@@ -784,21 +744,22 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
             b.scratch = tail ? 1u : 0u;
             blocks.push_back(b);
             if (blocks.size() > 0x7FFFFFFFull)
-                return wfail(ATG_ERR_UNSUPPORTED, "too many WavPack blocks in one batch");
+                return g_wvd_err.fail(ATG_ERR_UNSUPPORTED, "too many WavPack blocks in one batch");
             slots += (uint64_t)set_n * wv::coded_channels(S.flags);
             max_n = std::max(max_n, set_n);
             chans += oc;
             ++in_set;
             if (!tail && (S.flags & wv::kFinal)) {
                 if (chans != T.channels)
-                    return wfail(ATG_ERR_INVALID, "a set does not add up to the channel count");
+                    return g_wvd_err.fail(ATG_ERR_INVALID,
+                                          "a set does not add up to the channel count");
                 set_blocks.push_back(in_set);
                 out_samples += (uint64_t)set_n * T.channels;
                 in_set = 0;
             }
         }
         if (in_set && T.tail_blocks == 0)
-            return wfail(ATG_ERR_INVALID, "the last set has no final block");
+            return g_wvd_err.fail(ATG_ERR_INVALID, "the last set has no final block");
         count[t] = (uint32_t)blocks.size() - first[t];
     }
     const uint64_t nb = blocks.size();
@@ -828,7 +789,7 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
     if (nb && max_n) {
         const uint64_t per = ((uint64_t)max_n + 255) / 256;
         if (per * nb > 0x7FFFFFFFull)
-            return wfail(ATG_ERR_UNSUPPORTED, "batch too large for one launch");
+            return g_wvd_err.fail(ATG_ERR_UNSUPPORTED, "batch too large for one launch");
         hipLaunchKernelGGL(k_wvd_out, dim3((unsigned)(per * nb)), dim3(256), 0, s, dbl,
                            (uint32_t)per, (const Params *)dec->params.p, (const int32_t *)dst,
                            (const int32_t *)dec->resid.p, (int32_t *)dec->pcm.p);
@@ -839,10 +800,7 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
     if (nb)
         WHIP(hipMemcpyAsync(st.data(), dst, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
     WHIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kWTimed - 1; ++k)
-        (void)hipEventElapsedTime(&dec->times[k], dec->ev[k], dec->ev[k + 1]);
-    (void)hipEventElapsedTime(&dec->times[kWTimed - 1], dec->ev[0], dec->ev[kWTimed - 1]);
-    dec->have_times = true;
+    dec->finish_times();
     dec->last_samples = out_samples;
     std::vector<int32_t> hashed;
     for (uint32_t t = 0; t < n; ++t) {
@@ -903,7 +861,7 @@ atg_status wvd_run(atg_wv_decoder *dec, const uint8_t *d_data, uint64_t len,
 
 extern "C" {
 
-const char *atg_wv_decoder_last_error(void) { return g_wvd_err.c_str(); }
+const char *atg_wv_decoder_last_error(void) { return g_wvd_err.msg.c_str(); }
 
 int atg_wv_read_info(const uint8_t *data, uint64_t len, atg_wv_info *info, atg_wv_block *blocks,
                      uint32_t cap, uint32_t *n_blocks)
@@ -1035,23 +993,11 @@ int atg_wv_read_info(const uint8_t *data, uint64_t len, atg_wv_info *info, atg_w
 
 atg_status atg_wv_decoder_create(int device, atg_wv_decoder **out)
 {
-    if (!out)
-        return wfail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return wfail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return wfail(ATG_ERR_INVALID, "device index out of range");
-    WHIP(hipSetDevice(device));
-    atg_wv_decoder *d = new atg_wv_decoder();
-    d->device = device;
-    hipError_t err = hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking);
-    for (auto &ev : d->ev)
-        if (err == hipSuccess)
-            err = hipEventCreate(&ev);
-    if (err == hipSuccess)
-        err = d->table.ensure(sizeof(uint16_t) * 256);
+    atg_status st = open_handle(device, out, g_wvd_err, "decoder create");
+    if (st != ATG_OK)
+        return st;
+    atg_wv_decoder *d = *out;
+    hipError_t err = d->table.ensure(sizeof(uint16_t) * 256);
     if (err == hipSuccess) {
         // the exponent table of the 16-bit log form: floor(256 * 2^(i/256) + 0.5)
         uint16_t table[256];
@@ -1060,10 +1006,11 @@ atg_status atg_wv_decoder_create(int device, atg_wv_decoder **out)
         err = hipMemcpy(d->table.p, table, sizeof(table), hipMemcpyHostToDevice);
     }
     if (err != hipSuccess) {
+        *out = nullptr;
         atg_wv_decoder_destroy(d);
-        return wfail(ATG_ERR_DEVICE, std::string("decoder create: ") + hipGetErrorString(err));
+        return g_wvd_err.fail(ATG_ERR_DEVICE,
+                              std::string("decoder create: ") + hipGetErrorString(err));
     }
-    *out = d;
     return ATG_OK;
 }
 
@@ -1071,16 +1018,7 @@ void atg_wv_decoder_destroy(atg_wv_decoder *d)
 {
     if (!d)
         return;
-    (void)hipSetDevice(d->device);
-    if (d->s)
-        (void)hipStreamSynchronize(d->s);
-    for (WBuf *b : {&d->blocks, &d->params, &d->status, &d->resid, &d->pcm, &d->table, &d->h_data})
-        b->release();
-    for (auto &ev : d->ev)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    if (d->s)
-        (void)hipStreamDestroy(d->s);
+    d->close({&d->blocks, &d->params, &d->status, &d->resid, &d->pcm, &d->table, &d->h_data});
     delete d;
 }
 
@@ -1091,9 +1029,9 @@ atg_status atg_wv_decode_device(atg_wv_decoder *d, const void *d_data, uint64_t 
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!d_data && len))
-        return wfail(ATG_ERR_INVALID, "NULL argument");
+        return g_wvd_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_data) & 3)
-        return wfail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
+        return g_wvd_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
     WHIP(hipSetDevice(d->device));
     atg_status st = wvd_run(d, (const uint8_t *)d_data, len, tracks, n, results, total_samples);
     if (st == ATG_OK && d_pcm)
@@ -1107,7 +1045,7 @@ atg_status atg_wv_decode_host(atg_wv_decoder *d, const uint8_t *data, uint64_t l
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!data && len))
-        return wfail(ATG_ERR_INVALID, "NULL argument");
+        return g_wvd_err.fail(ATG_ERR_INVALID, "NULL argument");
     WHIP(hipSetDevice(d->device));
     WHIP(d->h_data.ensure(std::max<uint64_t>(len, 4)));
     if (len)
@@ -1119,9 +1057,9 @@ atg_status atg_wv_decode_fetch(atg_wv_decoder *d, int32_t *pcm, uint64_t pcm_cap
 {
     ATG_HANDLE_LOCK(d);
     if (!d || (!pcm && pcm_cap))
-        return wfail(ATG_ERR_INVALID, "NULL argument");
+        return g_wvd_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (pcm_cap < d->last_samples)
-        return wfail(ATG_ERR_CAPACITY, "pcm buffer smaller than the decoded batch");
+        return g_wvd_err.fail(ATG_ERR_CAPACITY, "pcm buffer smaller than the decoded batch");
     WHIP(hipSetDevice(d->device));
     if (d->last_samples)
         WHIP(hipMemcpyAsync(pcm, d->pcm.p, sizeof(int32_t) * d->last_samples,
@@ -1133,16 +1071,7 @@ atg_status atg_wv_decode_fetch(atg_wv_decoder *d, int32_t *pcm, uint64_t pcm_cap
 int atg_wv_decoder_kernel_times(atg_wv_decoder *d, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(d);
-    if (!d || !d->have_times)
-        return 0;
-    const int k = cap < kWTimed ? cap : kWTimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kWNames[i];
-        if (ms)
-            ms[i] = d->times[i];
-    }
-    return k;
+    return d ? d->report(kWNames, names, ms, cap) : 0;
 }
 
 } // extern "C"

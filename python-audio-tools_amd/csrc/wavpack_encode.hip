@@ -36,6 +36,7 @@
 //                 the dummy at byte 32 (over the footer's MD5 sub-block when
 //                 the track is empty, as the reference does).
 #include "handle_lock.h"
+#include "host_common.h"
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -296,46 +297,8 @@ __global__ __launch_bounds__(256) void k_wve_md5in(const S *__restrict__ pcm,
 }
 
 // ------------------------------------------------------------------- host
-thread_local std::string g_wve_err;
-
-atg_status efail(atg_status s, const std::string &m)
-{
-    g_wve_err = m;
-    return s;
-}
-
-#define EHIP(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return efail(ATG_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct EBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap && p)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+thread_local ErrSlot g_wve_err;
+#define EHIP(expr) ATG_HIP_TRY(g_wve_err, expr, #expr)
 
 // "wv_size" is everything between the chain and the pack: the block table
 // copied to the host, the extents, the table's second upload
@@ -364,15 +327,9 @@ uint32_t walk_lanes(uint64_t n)
 
 } // namespace
 
-struct atg_wv_encoder {
-    std::recursive_mutex mu; // held by every public entry point (handle_lock.h)
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[6] = {};
-    float times[kETimed] = {};
-    bool have_times = false;
-    EBuf blocks, streams, meta, state, work, tracks, sub_bytes, tables, md5in, md5meta, md5, h_pcm,
-        h_out;
+struct atg_wv_encoder : StageHandle<kETimed> {
+    DevBuf blocks, streams, meta, state, work, tracks, sub_bytes, tables, md5in, md5meta, md5,
+        h_pcm, h_out;
 };
 
 namespace {
@@ -390,22 +347,23 @@ atg_status wve_plan(const atg_track *tracks, uint32_t n, uint32_t channels, uint
                     uint32_t bps, uint32_t rate, const atg_wv_enc_options *opt, EPlan &P)
 {
     if (bps != 8 && bps != 16 && bps != 24)
-        return efail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
+        return g_wve_err.fail(ATG_ERR_INVALID, "bits per sample must be 8, 16 or 24");
     if (channels < 1)
-        return efail(ATG_ERR_INVALID, "channels must be at least 1");
+        return g_wve_err.fail(ATG_ERR_INVALID, "channels must be at least 1");
     if (channels > 255)
-        return efail(ATG_ERR_UNSUPPORTED, "the channel-info sub-block holds at most 255 channels");
+        return g_wve_err.fail(ATG_ERR_UNSUPPORTED,
+                              "the channel-info sub-block holds at most 255 channels");
     const uint32_t passes = opt->correlation_passes;
     if (passes != 0 && passes != 1 && passes != 2 && passes != 5 && passes != 10 && passes != 16)
-        return efail(ATG_ERR_INVALID, "correlation passes must be 0, 1, 2, 5, 10 or 16");
+        return g_wve_err.fail(ATG_ERR_INVALID, "correlation passes must be 0, 1, 2, 5, 10 or 16");
     if (opt->block_size < 1)
-        return efail(ATG_ERR_INVALID, "block size must be at least 1");
+        return g_wve_err.fail(ATG_ERR_INVALID, "block size must be at least 1");
     uint8_t split[256];
     const uint32_t S = wv::stream_split(channels, mask, split, 256);
     if (passes)
         for (uint32_t k = 0; k < S; ++k)
             if (opt->block_size < wv::term_depth(split[k], passes))
-                return efail(ATG_ERR_INVALID,
+                return g_wve_err.fail(ATG_ERR_INVALID,
                              "block size below the history depth of the pass table");
     EOpts &o = P.o;
     o.channels = channels, o.mask = mask, o.bps = bps, o.rate = rate;
@@ -422,12 +380,14 @@ atg_status wve_plan(const atg_track *tracks, uint32_t n, uint32_t channels, uint
     for (uint32_t t = 0; t < n; ++t) {
         const atg_track &T = tracks[t];
         if (T.frame_sizes)
-            return efail(ATG_ERR_UNSUPPORTED, "explicit frame sizes: WavPack is fed whole blocks");
+            return g_wve_err.fail(ATG_ERR_UNSUPPORTED,
+                                  "explicit frame sizes: WavPack is fed whole blocks");
         if (T.pcm_frames >= 0xFFFFFFFFull)
-            return efail(ATG_ERR_INVALID, "a WavPack file holds fewer than 2^32 - 1 frames");
+            return g_wve_err.fail(ATG_ERR_INVALID,
+                                  "a WavPack file holds fewer than 2^32 - 1 frames");
         const uint64_t sets = (T.pcm_frames + B - 1) / B;
         if (P.blocks.size() + sets * S > 0x7FFFFFFFull)
-            return efail(ATG_ERR_UNSUPPORTED, "too many WavPack blocks in one batch");
+            return g_wve_err.fail(ATG_ERR_UNSUPPORTED, "too many WavPack blocks in one batch");
         P.first[t] = (uint32_t)P.blocks.size();
         ETrack &D = P.tracks[t];
         std::memset(&D, 0, sizeof(D));
@@ -470,7 +430,7 @@ atg_status wve_plan(const atg_track *tracks, uint32_t n, uint32_t channels, uint
 }
 
 template <typename T>
-atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out, EBuf *stage,
+atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out, DevBuf *stage,
                    uint64_t out_cap, uint32_t n, atg_wv_track_result *res, uint32_t *block_bytes,
                    uint64_t *needed, uint64_t *out_bytes)
 {
@@ -524,7 +484,8 @@ atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out
         if (P.max_samples) {
             const uint64_t gx = (P.max_samples + 1023u) / 1024u;
             if (gx > 0x7FFFFFFFull)
-                return efail(ATG_ERR_UNSUPPORTED, "track too long for one MD5 staging launch");
+                return g_wve_err.fail(ATG_ERR_UNSUPPORTED,
+                                      "track too long for one MD5 staging launch");
             hipLaunchKernelGGL(k_wve_md5in<T>, dim3((unsigned)gx, std::min<uint32_t>(n, 65535u)),
                                dim3(256), 0, s, d_pcm, (const ETrack *)enc->tracks.p, n,
                                o.channels, o.bps / 8u, (uint8_t *)enc->md5in.p);
@@ -559,7 +520,8 @@ atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out
             EBlock &b = P.blocks[P.first[t] + k];
             const uint64_t sub = wve::block_sub_bytes(b, o);
             if (sub + 24u > 0xFFFFFFFFull)
-                return efail(ATG_ERR_UNSUPPORTED, "a WavPack block longer than 2^32 bytes");
+                return g_wve_err.fail(ATG_ERR_UNSUPPORTED,
+                                      "a WavPack block longer than 2^32 bytes");
             subs[P.first[t] + k] = (uint32_t)sub;
             b.byte_off = pos;
             if (block_bytes)
@@ -576,7 +538,7 @@ atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out
     if (out_bytes)
         *out_bytes = pos;
     if (pos > out_cap)
-        return efail(ATG_ERR_CAPACITY, "output buffer smaller than the encoded batch");
+        return g_wve_err.fail(ATG_ERR_CAPACITY, "output buffer smaller than the encoded batch");
     if (stage) { // host call: the device image is sized from the length pass
         EHIP(stage->ensure(std::max<uint64_t>(pos, 4)));
         d_out = (uint8_t *)stage->p;
@@ -608,10 +570,7 @@ atg_status wve_run(atg_wv_encoder *enc, EPlan &P, const T *d_pcm, uint8_t *d_out
     EHIP(hipGetLastError());
     EHIP(hipEventRecord(enc->ev[5], s));
     EHIP(hipStreamSynchronize(s));
-    for (int k = 0; k < kETimed - 1; ++k)
-        (void)hipEventElapsedTime(&enc->times[k], enc->ev[k], enc->ev[k + 1]);
-    (void)hipEventElapsedTime(&enc->times[kETimed - 1], enc->ev[0], enc->ev[kETimed - 1]);
-    enc->have_times = true;
+    enc->finish_times();
     return ATG_OK;
 }
 
@@ -620,11 +579,11 @@ atg_status wve_check(atg_wv_encoder *e, const atg_track *tracks, uint32_t n,
                      const atg_wv_enc_options *opt)
 {
     if (!e || !opt || (!tracks && n) || (!results && n))
-        return efail(ATG_ERR_INVALID, "NULL argument");
+        return g_wve_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (fmt != ATG_PCM_S16 && fmt != ATG_PCM_S32)
-        return efail(ATG_ERR_INVALID, "unknown PCM format");
+        return g_wve_err.fail(ATG_ERR_INVALID, "unknown PCM format");
     if (fmt == ATG_PCM_S16 && bps > 16)
-        return efail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
+        return g_wve_err.fail(ATG_ERR_INVALID, "S16 PCM holds at most 16-bit samples");
     return ATG_OK;
 }
 
@@ -632,27 +591,15 @@ atg_status wve_check(atg_wv_encoder *e, const atg_track *tracks, uint32_t n,
 
 extern "C" {
 
-const char *atg_wv_encoder_last_error(void) { return g_wve_err.c_str(); }
+const char *atg_wv_encoder_last_error(void) { return g_wve_err.msg.c_str(); }
 
 atg_status atg_wv_encoder_create(int device, atg_wv_encoder **out)
 {
-    if (!out)
-        return efail(ATG_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return efail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return efail(ATG_ERR_INVALID, "device index out of range");
-    EHIP(hipSetDevice(device));
-    atg_wv_encoder *e = new atg_wv_encoder();
-    e->device = device;
-    hipError_t err = hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking);
-    for (auto &ev : e->ev)
-        if (err == hipSuccess)
-            err = hipEventCreate(&ev);
-    if (err == hipSuccess)
-        err = e->tables.ensure(256 + sizeof(uint16_t) * 256);
+    atg_status st = open_handle(device, out, g_wve_err, "encoder create");
+    if (st != ATG_OK)
+        return st;
+    atg_wv_encoder *e = *out;
+    hipError_t err = e->tables.ensure(256 + sizeof(uint16_t) * 256);
     if (err == hipSuccess) {
         // the tables of the 16-bit log form: floor(256 log2(1 + i/256) + 0.5)
         // and floor(256 2^(i/256) + 0.5)
@@ -665,11 +612,12 @@ atg_status atg_wv_encoder_create(int device, atg_wv_encoder **out)
         std::memcpy(tab + 256, ex, sizeof(ex));
         err = hipMemcpy(e->tables.p, tab, sizeof(tab), hipMemcpyHostToDevice);
     }
-    if (err != hipSuccess) { // give back what was made: events and stream may be null
+    if (err != hipSuccess) {
+        *out = nullptr;
         atg_wv_encoder_destroy(e);
-        return efail(ATG_ERR_DEVICE, std::string("encoder create: ") + hipGetErrorString(err));
+        return g_wve_err.fail(ATG_ERR_DEVICE,
+                              std::string("encoder create: ") + hipGetErrorString(err));
     }
-    *out = e;
     return ATG_OK;
 }
 
@@ -677,18 +625,8 @@ void atg_wv_encoder_destroy(atg_wv_encoder *e)
 {
     if (!e)
         return;
-    (void)hipSetDevice(e->device);
-    if (e->s)
-        (void)hipStreamSynchronize(e->s);
-    for (EBuf *b : {&e->blocks, &e->streams, &e->meta, &e->state, &e->work, &e->tracks,
-                    &e->sub_bytes, &e->tables, &e->md5in, &e->md5meta, &e->md5, &e->h_pcm,
-                    &e->h_out})
-        b->release();
-    for (auto &ev : e->ev)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    if (e->s)
-        (void)hipStreamDestroy(e->s);
+    e->close({&e->blocks, &e->streams, &e->meta, &e->state, &e->work, &e->tracks, &e->sub_bytes,
+              &e->tables, &e->md5in, &e->md5meta, &e->md5, &e->h_pcm, &e->h_out});
     delete e;
 }
 
@@ -709,7 +647,8 @@ atg_status atg_wv_encode_device(atg_wv_encoder *e, const void *d_pcm, atg_pcm_fo
     if (st != ATG_OK)
         return st;
     if (block_bytes && block_bytes_cap < P.blocks.size())
-        return efail(ATG_ERR_INVALID, "block_bytes holds fewer entries than the batch has blocks");
+        return g_wve_err.fail(ATG_ERR_INVALID,
+                              "block_bytes holds fewer entries than the batch has blocks");
     if (fmt == ATG_PCM_S16)
         return wve_run(e, P, (const int16_t *)d_pcm, (uint8_t *)d_out, nullptr, out_cap, n, results,
                        block_bytes, needed, nullptr);
@@ -734,14 +673,15 @@ atg_status atg_wv_encode_host(atg_wv_encoder *e, const void *pcm, atg_pcm_format
     if (st != ATG_OK)
         return st;
     if (block_bytes && block_bytes_cap < P.blocks.size())
-        return efail(ATG_ERR_INVALID, "block_bytes holds fewer entries than the batch has blocks");
+        return g_wve_err.fail(ATG_ERR_INVALID,
+                              "block_bytes holds fewer entries than the batch has blocks");
     uint64_t frames = 0;
     for (uint32_t t = 0; t < n; ++t)
         frames = std::max<uint64_t>(frames, tracks[t].pcm_offset + tracks[t].pcm_frames);
     if (!pcm && frames)
-        return efail(ATG_ERR_INVALID, "NULL argument");
+        return g_wve_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (!out && out_cap)
-        return efail(ATG_ERR_INVALID, "NULL argument");
+        return g_wve_err.fail(ATG_ERR_INVALID, "NULL argument");
     const size_t es = fmt == ATG_PCM_S16 ? 2 : 4;
     const uint64_t in_bytes = frames * channels * es;
     EHIP(e->h_pcm.ensure(std::max<uint64_t>(in_bytes, 4)));
@@ -764,16 +704,7 @@ atg_status atg_wv_encode_host(atg_wv_encoder *e, const void *pcm, atg_pcm_format
 int atg_wv_encoder_kernel_times(atg_wv_encoder *e, const char **names, float *ms, int cap)
 {
     ATG_HANDLE_LOCK(e);
-    if (!e || !e->have_times)
-        return 0;
-    const int k = cap < kETimed ? cap : kETimed;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kENames[i];
-        if (ms)
-            ms[i] = e->times[i];
-    }
-    return k;
+    return e ? e->report(kENames, names, ms, cap) : 0;
 }
 
 } // extern "C"

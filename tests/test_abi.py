@@ -56,6 +56,67 @@ def test_engine_create_fails_loudly_without_gpu():
     assert e.value.status == _atgpu.ATG_ERR_DEVICE
 
 
+# the eight handle classes with the C functions of their components
+HANDLES = [
+    (_atgpu.Engine, "atg_engine", "atg_last_error"),
+    (_atgpu.Decoder, "atg_decoder", "atg_decoder_last_error"),
+    (_atgpu.AlacEncoder, "atg_alac_encoder", "atg_alac_last_error"),
+    (_atgpu.AlacDecoder, "atg_alac_decoder", "atg_alac_decoder_last_error"),
+    (_atgpu.TtaEncoder, "atg_tta_encoder", "atg_tta_last_error"),
+    (_atgpu.TtaDecoder, "atg_tta_decoder", "atg_tta_decoder_last_error"),
+    (_atgpu.WvDecoder, "atg_wv_decoder", "atg_wv_decoder_last_error"),
+    (_atgpu.WvEncoder, "atg_wv_encoder", "atg_wv_encoder_last_error"),
+]
+HANDLE_IDS = [h[0].__name__ for h in HANDLES]
+
+
+@pytest.mark.skipif(gpu_visible(), reason="a GPU is visible: covered by -m gpu tests")
+@pytest.mark.parametrize("cls", [h[0] for h in HANDLES], ids=HANDLE_IDS)
+def test_handle_create_fails_loudly_without_gpu(cls):
+    with pytest.raises(_atgpu.ATGError) as e:
+        cls(0)
+    assert e.value.status == _atgpu.ATG_ERR_DEVICE
+    assert e.value.args[0] and str(e.value)
+
+
+@pytest.mark.skipif(gpu_visible(), reason="a GPU is visible: covered by -m gpu tests")
+def test_error_slots_stay_separate():
+    """a failed TTA create writes the TTA slot and no other component's"""
+    lib = _atgpu.load_library()
+    others = [err for _, _, err in HANDLES if err != "atg_tta_last_error"]
+    before = {err: getattr(lib, err)() for err in others}
+    with pytest.raises(_atgpu.ATGError):
+        _atgpu.TtaEncoder(0)
+    assert lib.atg_tta_last_error()
+    assert {err: getattr(lib, err)() for err in others} == before
+
+
+@pytest.mark.parametrize("prefix", [h[1] for h in HANDLES], ids=HANDLE_IDS)
+def test_handle_null_arguments(prefix):
+    lib = _atgpu.load_library()
+    assert getattr(lib, prefix + "_create")(0, None) == _atgpu.ATG_ERR_INVALID
+    getattr(lib, prefix + "_destroy")(None)  # no-op
+    assert getattr(lib, prefix + "_kernel_times")(None, None, None, 0) == 0
+
+
+def test_shared_handle_is_one_per_class(monkeypatch):
+    """the helper under engine() ... wv_encoder(), with stub classes"""
+    monkeypatch.setattr(_atgpu, "_shared", {})
+
+    class A(object):
+        def __init__(self, device):
+            self.device = device
+
+    class B(A):
+        pass
+
+    a = _atgpu._shared_handle(A)
+    assert _atgpu._shared_handle(A) is a
+    b = _atgpu._shared_handle(B)
+    assert b is not a and type(b) is B and _atgpu._shared_handle(B) is b
+    assert a.device == b.device == _atgpu.default_device()
+
+
 def flac8(**kw):
     d = dict(block_size=4096, max_lpc_order=12, min_residual_partition_order=0,
              max_residual_partition_order=6, mid_side=True, exhaustive_model_search=True)
