@@ -1174,6 +1174,167 @@ int64_t atg_resample_read_sizes(uint64_t in_frames, uint32_t channels, uint32_t 
    form) and "rs_filter" */
 int atg_resample_kernel_times(const char **names, float *ms, int cap);
 
+/* -------------------------------------------------------------------- */
+/* Shorten (.shn).  Replaces the reference's audiotools.encoders.       */
+/* encode_shn (src/encoders/shn.c) and audiotools.decoders.SHNDecoder   */
+/* (src/decoders/shn.c) for a batch of tracks.  A .shn file is one      */
+/* MSB-first bit stream with no frame table, block sizes, CRC or sample */
+/* count.                                                               */
+/* -------------------------------------------------------------------- */
+/* The limits.  The encoder takes block sizes (and explicit frame sizes) up
+   to ATG_SHN_MAX_ENCODE_BLOCK, where the reference's unsigned delta sums
+   cannot wrap (|delta3| < 2^19, 2^19 x 4096 = 2^31).  The decoder ends a
+   stream with ATG_SHN_UNSUPPORTED where the reference's behaviour is
+   undefined or unbounded: channels 0 or above ATG_SHN_MAX_CHANNELS, a mean
+   count above ATG_SHN_MAX_MEAN_COUNT, an audio command with block length 0
+   (shnmean divides by it), DIFF0 or QLPC with mean count 0 (the same
+   division), a block length that changes inside a set of channels, a shift
+   or an energy above 31, a "long" wider than 32 bits, an LPC count above
+   ATG_SHN_MAX_LPC_COUNT, or more than ATG_SHN_MAX_TRACK_SAMPLES decoded
+   samples (a ZERO command is 5 bits and can claim 2^32 of them). */
+#define ATG_SHN_MAX_ENCODE_BLOCK 4096u
+#define ATG_SHN_MAX_CHANNELS 256u
+#define ATG_SHN_MAX_LPC_COUNT 32u
+#define ATG_SHN_MAX_MEAN_COUNT 64u
+#define ATG_SHN_MAX_TRACK_SAMPLES (1ull << 28)
+
+/* the reference's decoder status enum (decoders/shn.h) with the messages
+   SHNDecoder raises, plus one of this library's own */
+typedef enum {
+    ATG_SHN_OK = 0,
+    ATG_SHN_END_OF_STREAM = 1,           /* the stream ended with QUIT */
+    ATG_SHN_IOERROR = 2,                 /* IOError "I/O error reading Shorten file"
+                                            (header: "I/O error reading Shorten header") */
+    ATG_SHN_UNKNOWN_COMMAND = 3,         /* ValueError "unknown command in Shorten stream" */
+    ATG_SHN_INVALID_MAGIC_NUMBER = 4,    /* ValueError "invalid magic number" */
+    ATG_SHN_INVALID_SHORTEN_VERSION = 5, /* ValueError "invalid Shorten version" */
+    ATG_SHN_UNSUPPORTED_FILE_TYPE = 6,   /* ValueError "unsupported Shorten file type" */
+    ATG_SHN_UNSUPPORTED = 7              /* outside the limits above */
+} atg_shn_status;
+
+typedef struct {
+    uint32_t block_size;     /* 1..ATG_SHN_MAX_ENCODE_BLOCK; the reference's default is 256 */
+    int32_t is_big_endian;   /* recorded in the file type only */
+    int32_t signed_samples;  /* 0: 1 << (bits - 1) is added to every sample */
+    uint32_t reserved;
+} atg_shn_options;
+
+/* the bytes of a track's VERBATIM commands: the header one is always
+   written, the footer one when footer_bytes > 0 */
+typedef struct {
+    const uint8_t *header;
+    uint64_t header_bytes;
+    const uint8_t *footer;
+    uint64_t footer_bytes;
+} atg_shn_track_data;
+
+typedef struct {
+    uint64_t out_offset; /* 4-byte aligned */
+    uint64_t bytes;      /* the whole .shn image; always 1 mod 4 */
+    uint64_t pcm_frames;
+    uint32_t n_blocks;
+    uint32_t reserved;
+} atg_shn_track_result;
+
+typedef struct atg_shn_encoder atg_shn_encoder;
+
+const char *atg_shn_encoder_last_error(void);
+atg_status atg_shn_encoder_create(int device, atg_shn_encoder **out);
+void atg_shn_encoder_destroy(atg_shn_encoder *enc);
+/* PCM and output in device memory (d_out 4-byte aligned).  Every track
+   becomes a whole .shn image at results[t].out_offset; a track's atg_track
+   frame sizes are the lengths of the reader's short reads (a BLOCKSIZE
+   command where the length changes).  `extra` holds n_tracks entries or is
+   NULL.  Sizes are known only after a length pass: *needed (may be NULL)
+   receives the bytes the batch takes, rounded up to 4, and ATG_ERR_CAPACITY
+   is returned, with nothing written, when out_cap is less.  bits_per_sample
+   other than 8 or 16 is ATG_ERR_INVALID (the reference's ValueError
+   "unsupported bits per sample"), a block size above
+   ATG_SHN_MAX_ENCODE_BLOCK ATG_ERR_UNSUPPORTED. */
+atg_status atg_shn_encode_device(atg_shn_encoder *enc, const void *d_pcm, atg_pcm_format format,
+                                 const atg_track *tracks, const atg_shn_track_data *extra,
+                                 uint32_t n_tracks, uint32_t channels, uint32_t bits_per_sample,
+                                 const atg_shn_options *options, void *d_out, uint64_t out_cap,
+                                 atg_shn_track_result *results, uint64_t *needed);
+/* Host buffers (staged through the device). */
+atg_status atg_shn_encode_host(atg_shn_encoder *enc, const void *pcm, atg_pcm_format format,
+                               const atg_track *tracks, const atg_shn_track_data *extra,
+                               uint32_t n_tracks, uint32_t channels, uint32_t bits_per_sample,
+                               const atg_shn_options *options, uint8_t *out, uint64_t out_cap,
+                               atg_shn_track_result *results, uint64_t *needed);
+/* the last encode: "shn_size", "shn_scan", "shn_layout" (the host between
+   the scan and the pack), "shn_pack", "shn_edges" and "shn_total" */
+int atg_shn_encoder_kernel_times(atg_shn_encoder *enc, const char **names, float *ms, int cap);
+
+typedef struct {
+    uint32_t file_type, channels, block_length, max_lpc, mean_count, bytes_to_skip;
+    uint32_t bits_per_sample;
+    uint32_t signed_samples;
+    uint32_t sample_rate;  /* from a RIFF/WAVE fmt or AIFF COMM chunk in a leading
+                              VERBATIM, else 44100 */
+    uint32_t channel_mask; /* likewise, else 0 */
+    uint64_t total_pcm_frames;  /* from that VERBATIM's data / SSND chunk size, as the
+                                   reference's audiotools/shn.py computes it; else 0 */
+    uint64_t first_command_bit; /* where the commands start */
+} atg_shn_info;
+
+/* read_shn_header on the host: returns an atg_shn_status (ATG_SHN_OK with
+   *info filled, or the header's error). */
+int atg_shn_read_info(const uint8_t *data, uint64_t len, atg_shn_info *info);
+
+/* one stream of a decode batch: its image in the data (4-byte aligned
+   offset) and the header fields atg_shn_read_info returned */
+typedef struct {
+    uint64_t data_offset;
+    uint64_t data_bytes;
+    uint64_t first_command_bit;
+    uint32_t file_type, channels, block_length, max_lpc, mean_count;
+    uint32_t reserved;
+} atg_shn_dec_track;
+
+/* status: ATG_SHN_END_OF_STREAM for a stream that ended with QUIT, else why
+   it stopped; its PCM then ends before the first incomplete set of channels.
+   The VERBATIM bytes (what pcm_split returns) are those in front of and
+   after the first audio command, header first, at verbatim_offset of the
+   bytes atg_shn_decode_fetch_verbatim copies. */
+typedef struct {
+    uint64_t pcm_offset; /* in samples, of the batch's int32 PCM */
+    uint64_t pcm_frames;
+    uint64_t verbatim_offset;
+    uint32_t header_bytes, footer_bytes;
+    int32_t status;
+    uint32_t reserved;
+} atg_shn_dec_result;
+
+typedef struct atg_shn_decoder atg_shn_decoder;
+
+const char *atg_shn_decoder_last_error(void);
+atg_status atg_shn_decoder_create(int device, atg_shn_decoder **out);
+void atg_shn_decoder_destroy(atg_shn_decoder *dec);
+/* the index pass walks a stream's residual codes with the whole wave
+   (cooperative != 0, the default) or with the lane-serial walker */
+atg_status atg_shn_decoder_set_index_walk(atg_shn_decoder *dec, int cooperative);
+atg_status atg_shn_decode_host(atg_shn_decoder *dec, const uint8_t *data, uint64_t len,
+                               const atg_shn_dec_track *tracks, uint32_t n_tracks,
+                               atg_shn_dec_result *results, uint64_t *total_samples);
+/* the last decode's interleaved int32 PCM / VERBATIM bytes to host memory */
+atg_status atg_shn_decode_fetch(atg_shn_decoder *dec, int32_t *pcm, uint64_t pcm_cap);
+atg_status atg_shn_decode_fetch_verbatim(atg_shn_decoder *dec, uint8_t *bytes, uint64_t cap);
+/* the frame counts of the sets of channels stream `track` of the last decode
+   gave, in order (what successive SHNDecoder.read() calls return);
+   *n_blocks receives their number, ATG_ERR_CAPACITY when cap is less */
+atg_status atg_shn_decode_fetch_blocks(atg_shn_decoder *dec, uint32_t track, uint32_t *lengths,
+                                       uint64_t cap, uint64_t *n_blocks);
+/* data in device memory (4-byte aligned); *d_pcm stays valid until the
+   decoder's next call */
+atg_status atg_shn_decode_device(atg_shn_decoder *dec, const void *d_data, uint64_t len,
+                                 const atg_shn_dec_track *tracks, uint32_t n_tracks,
+                                 atg_shn_dec_result *results, const int32_t **d_pcm,
+                                 uint64_t *total_samples);
+/* "shnd_index", "shnd_layout", "shnd_parse", "shnd_recon", "shnd_total" */
+int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float *ms,
+                                 int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -597,3 +597,4 @@ from .wav import WaveAudio, InvalidWave  # noqa: E402,F401
 from .m4a import ALACAudio, InvalidALAC  # noqa: E402,F401
 from .tta import TrueAudio, InvalidTTA  # noqa: E402,F401
 from .wavpack import WavPackAudio, InvalidWavPack  # noqa: E402,F401
+from .shn import ShortenAudio, InvalidShorten  # noqa: E402,F401

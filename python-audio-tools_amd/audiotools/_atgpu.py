@@ -69,6 +69,13 @@ EXPORTS = (
     "atg_wv_decode_device", "atg_wv_decoder_kernel_times",
     "atg_wv_encoder_last_error", "atg_wv_encoder_create", "atg_wv_encoder_destroy",
     "atg_wv_encode_device", "atg_wv_encode_host", "atg_wv_encoder_kernel_times",
+    "atg_shn_encoder_last_error", "atg_shn_encoder_create", "atg_shn_encoder_destroy",
+    "atg_shn_encode_device", "atg_shn_encode_host", "atg_shn_encoder_kernel_times",
+    "atg_shn_decoder_last_error", "atg_shn_read_info", "atg_shn_decoder_create",
+    "atg_shn_decoder_destroy", "atg_shn_decoder_set_index_walk", "atg_shn_decode_host",
+    "atg_shn_decode_fetch", "atg_shn_decode_fetch_verbatim", "atg_shn_decode_fetch_blocks",
+    "atg_shn_decode_device",
+    "atg_shn_decoder_kernel_times",
     "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
 )
@@ -271,6 +278,41 @@ class WvTrackResult(ctypes.Structure):
     _fields_ = [("out_offset", c_u64), ("bytes", c_u64), ("pcm_frames", c_u64),
                 ("first_block", c_u32), ("n_blocks", c_u32), ("status", c_i32),
                 ("reserved", c_u32), ("md5", ctypes.c_uint8 * 16)]
+
+
+class ShnOptions(ctypes.Structure):
+    _fields_ = [("block_size", c_u32), ("is_big_endian", c_i32), ("signed_samples", c_i32),
+                ("reserved", c_u32)]
+
+
+class ShnTrackData(ctypes.Structure):
+    _fields_ = [("header", ctypes.c_char_p), ("header_bytes", c_u64),
+                ("footer", ctypes.c_char_p), ("footer_bytes", c_u64)]
+
+
+class ShnTrackResult(ctypes.Structure):
+    _fields_ = [("out_offset", c_u64), ("bytes", c_u64), ("pcm_frames", c_u64),
+                ("n_blocks", c_u32), ("reserved", c_u32)]
+
+
+class ShnInfo(ctypes.Structure):
+    _fields_ = [("file_type", c_u32), ("channels", c_u32), ("block_length", c_u32),
+                ("max_lpc", c_u32), ("mean_count", c_u32), ("bytes_to_skip", c_u32),
+                ("bits_per_sample", c_u32), ("signed_samples", c_u32),
+                ("sample_rate", c_u32), ("channel_mask", c_u32),
+                ("total_pcm_frames", c_u64), ("first_command_bit", c_u64)]
+
+
+class ShnDecTrack(ctypes.Structure):
+    _fields_ = [("data_offset", c_u64), ("data_bytes", c_u64), ("first_command_bit", c_u64),
+                ("file_type", c_u32), ("channels", c_u32), ("block_length", c_u32),
+                ("max_lpc", c_u32), ("mean_count", c_u32), ("reserved", c_u32)]
+
+
+class ShnDecResult(ctypes.Structure):
+    _fields_ = [("pcm_offset", c_u64), ("pcm_frames", c_u64), ("verbatim_offset", c_u64),
+                ("header_bytes", c_u32), ("footer_bytes", c_u32), ("status", c_i32),
+                ("reserved", c_u32)]
 
 
 class RsTrack(ctypes.Structure):
@@ -582,6 +624,43 @@ def load_library():
             fn.restype = ctypes.c_int
         lib.atg_wv_encoder_kernel_times.argtypes = KT
         lib.atg_wv_encoder_kernel_times.restype = ctypes.c_int
+        lib.atg_shn_encoder_last_error.restype = ctypes.c_char_p
+        lib.atg_shn_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_shn_encoder_create.restype = ctypes.c_int
+        lib.atg_shn_encoder_destroy.argtypes = [P]
+        lib.atg_shn_encoder_destroy.restype = None
+        for fn in (lib.atg_shn_encode_device, lib.atg_shn_encode_host):
+            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), P, c_u32, c_u32, c_u32,
+                           ctypes.POINTER(ShnOptions), P, c_u64,
+                           ctypes.POINTER(ShnTrackResult), ctypes.POINTER(c_u64)]
+            fn.restype = ctypes.c_int
+        lib.atg_shn_encoder_kernel_times.argtypes = KT
+        lib.atg_shn_encoder_kernel_times.restype = ctypes.c_int
+        lib.atg_shn_decoder_last_error.restype = ctypes.c_char_p
+        lib.atg_shn_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(ShnInfo)]
+        lib.atg_shn_read_info.restype = ctypes.c_int
+        lib.atg_shn_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
+        lib.atg_shn_decoder_create.restype = ctypes.c_int
+        lib.atg_shn_decoder_destroy.argtypes = [P]
+        lib.atg_shn_decoder_destroy.restype = None
+        lib.atg_shn_decoder_set_index_walk.argtypes = [P, ctypes.c_int]
+        lib.atg_shn_decoder_set_index_walk.restype = ctypes.c_int
+        lib.atg_shn_decode_host.argtypes = [
+            P, P, c_u64, ctypes.POINTER(ShnDecTrack), c_u32, ctypes.POINTER(ShnDecResult),
+            ctypes.POINTER(c_u64)]
+        lib.atg_shn_decode_host.restype = ctypes.c_int
+        lib.atg_shn_decode_fetch.argtypes = [P, P, c_u64]
+        lib.atg_shn_decode_fetch.restype = ctypes.c_int
+        lib.atg_shn_decode_fetch_verbatim.argtypes = [P, P, c_u64]
+        lib.atg_shn_decode_fetch_verbatim.restype = ctypes.c_int
+        lib.atg_shn_decode_fetch_blocks.argtypes = [P, c_u32, P, c_u64, ctypes.POINTER(c_u64)]
+        lib.atg_shn_decode_fetch_blocks.restype = ctypes.c_int
+        lib.atg_shn_decode_device.argtypes = [
+            P, P, c_u64, ctypes.POINTER(ShnDecTrack), c_u32, ctypes.POINTER(ShnDecResult),
+            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
+        lib.atg_shn_decode_device.restype = ctypes.c_int
+        lib.atg_shn_decoder_kernel_times.argtypes = KT
+        lib.atg_shn_decoder_kernel_times.restype = ctypes.c_int
         lib.atg_resample_last_error.restype = ctypes.c_char_p
         lib.atg_resample_output_frames.argtypes = [c_u64, c_u32, c_u32, c_u32]
         lib.atg_resample_output_frames.restype = c_u64
@@ -1598,6 +1677,177 @@ _engine_lock = threading.Lock()
 _shared = {}  # handle class -> the process-wide instance (engine() ... wv_encoder())
 
 
+# Shorten decoder status (include/atgpu.h ATG_SHN_*) and the exceptions the
+# reference raises for them (src/decoders/shn.c SHNDecoder_init, SHNDecoder_read)
+(SHN_OK, SHN_END_OF_STREAM, SHN_IOERROR, SHN_UNKNOWN_COMMAND, SHN_INVALID_MAGIC_NUMBER,
+ SHN_INVALID_SHORTEN_VERSION, SHN_UNSUPPORTED_FILE_TYPE, SHN_UNSUPPORTED) = range(8)
+SHN_HEADER_ERRORS = {2: (IOError, "I/O error reading Shorten header"),
+                     4: (ValueError, "invalid magic number"),
+                     5: (ValueError, "invalid Shorten version"),
+                     6: (ValueError, "unsupported Shorten file type"),
+                     7: (ValueError, "unsupported Shorten stream")}
+SHN_READ_ERRORS = {2: (IOError, "I/O error reading Shorten file"),
+                   3: (ValueError, "unknown command in Shorten stream"),
+                   7: (ValueError, "unsupported Shorten stream")}
+
+
+def _shn_extra(n, headers, footers):
+    """the atg_shn_track_data array of a batch (None where no track has
+    header or footer bytes); the bytes objects are kept alive in the list"""
+    if headers is None and footers is None:
+        return None, []
+    arr = (ShnTrackData * max(1, n))()
+    keep = []
+    for i in range(n):
+        h = bytes(headers[i]) if headers is not None and headers[i] else b""
+        f = bytes(footers[i]) if footers is not None and footers[i] else b""
+        keep += [h, f]
+        arr[i].header, arr[i].header_bytes = (h or None), len(h)
+        arr[i].footer, arr[i].footer_bytes = (f or None), len(f)
+    return arr, keep
+
+
+class ShnEncoder(_Handle):
+    """one libatgpu Shorten encoder (HIP stream + workspace) on one device"""
+
+    _create, _destroy = "atg_shn_encoder_create", "atg_shn_encoder_destroy"
+    _last_error, _kernel_times = "atg_shn_encoder_last_error", "atg_shn_encoder_kernel_times"
+
+    def encode(self, pcm, tracks, channels, bits_per_sample, block_size=256,
+               is_big_endian=False, signed_samples=True, headers=None, footers=None,
+               out_cap=None):
+        """host PCM (int16 or int32) -> (out bytes array, [ShnTrackResult]).
+        Sizes are known only after the length pass, so the first call offers
+        the raw PCM size and a call that reports ATG_ERR_CAPACITY is repeated
+        with the size it asks for."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype not in (np.int16, np.int32):
+            raise TypeError("pcm must be int16 or int32")
+        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        arr, n, keep = _track_array(tracks)
+        extra, keep2 = _shn_extra(n, headers, footers)
+        opts = ShnOptions(int(block_size), int(bool(is_big_endian)), int(bool(signed_samples)), 0)
+        res = (ShnTrackResult * max(1, n))()
+        cap = int(out_cap) if out_cap is not None else pcm.size * 2 + 64 * n + 64
+        need = c_u64()
+        for _ in range(2):
+            out = np.empty(max(4, cap), dtype=np.uint8)
+            st = self.lib.atg_shn_encode_host(
+                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, extra, n, channels,
+                bits_per_sample, ctypes.byref(opts), out.ctypes.data_as(ctypes.c_void_p), cap,
+                res, ctypes.byref(need))
+            if st != ATG_ERR_CAPACITY or need.value <= cap or out_cap is not None:
+                break
+            cap = need.value
+        if st != ATG_OK:
+            err = self._error(st)
+            err.needed = need.value
+            raise err
+        return out, [res[i] for i in range(n)]
+
+    def encode_device(self, d_pcm, fmt, tracks, channels, bits_per_sample, d_out, out_cap,
+                      block_size=256, is_big_endian=False, signed_samples=True, headers=None,
+                      footers=None):
+        """-> ([ShnTrackResult], bytes needed); raises ATGError with status
+        ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
+        if isinstance(tracks, TrackTable):
+            arr, n = tracks.arr, tracks.n
+        else:
+            arr, n, keep = _track_array(tracks)
+        extra, keep2 = _shn_extra(n, headers, footers)
+        opts = ShnOptions(int(block_size), int(bool(is_big_endian)), int(bool(signed_samples)), 0)
+        res = (ShnTrackResult * max(1, n))()
+        need = c_u64()
+        st = self.lib.atg_shn_encode_device(
+            self.handle, ctypes.c_void_p(d_pcm), fmt, arr, extra, n, channels, bits_per_sample,
+            ctypes.byref(opts), ctypes.c_void_p(d_out), out_cap, res, ctypes.byref(need))
+        if st != ATG_OK:
+            err = self._error(st)
+            err.needed = need.value
+            raise err
+        return [res[i] for i in range(n)], need.value
+
+
+def shn_read_info(data):
+    """read_shn_header of a .shn image (host C in libatgpu)
+    -> (ATG_SHN_* status, ShnInfo)"""
+    lib = load_library()
+    data = bytes(data)
+    info = ShnInfo()
+    st = lib.atg_shn_read_info(data, len(data), ctypes.byref(info))
+    return st, info
+
+
+def shn_dec_track(offset, nbytes, info):
+    """ShnDecTrack for an image at `offset` of the batch buffer"""
+    return ShnDecTrack(offset, nbytes, info.first_command_bit, info.file_type, info.channels,
+                       info.block_length, info.max_lpc, info.mean_count, 0)
+
+
+class ShnDecoder(_Handle):
+    """one libatgpu Shorten decoder (HIP stream + workspace) on one device"""
+
+    _create, _destroy = "atg_shn_decoder_create", "atg_shn_decoder_destroy"
+    _last_error, _kernel_times = "atg_shn_decoder_last_error", "atg_shn_decoder_kernel_times"
+
+    def set_index_walk(self, cooperative):
+        """the index pass: the wave-cooperative code walk (default) or the
+        lane-serial one"""
+        self._check(self.lib.atg_shn_decoder_set_index_walk(self.handle, int(bool(cooperative))))
+
+    def decode(self, data, tracks):
+        """decode a batch in host memory (images 4-byte aligned in data)
+        -> (pcm int32, [ShnDecResult], VERBATIM bytes)"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = len(tracks)
+        arr = (ShnDecTrack * max(1, n))(*tracks)
+        res = (ShnDecResult * max(1, n))()
+        ns = c_u64()
+        self._check(self.lib.atg_shn_decode_host(
+            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
+            ctypes.byref(ns)))
+        res = [res[i] for i in range(n)]
+        return self.fetch(ns.value), res, self.fetch_verbatim(res)
+
+    def decode_device(self, d_data, nbytes, tracks):
+        n = len(tracks)
+        arr = (ShnDecTrack * max(1, n))(*tracks)
+        res = (ShnDecResult * max(1, n))()
+        dp = ctypes.c_void_p()
+        ns = c_u64()
+        self._check(self.lib.atg_shn_decode_device(
+            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
+            ctypes.byref(ns)))
+        return [res[i] for i in range(n)], dp.value, ns.value
+
+    def fetch(self, n_samples):
+        """the last decode's PCM (n_samples int32) to host memory"""
+        pcm = np.empty(max(1, n_samples), dtype=np.int32)
+        self._check(self.lib.atg_shn_decode_fetch(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
+        return pcm[:n_samples]
+
+    def fetch_blocks(self, track):
+        """the frame counts of the sets of channels stream `track` of the
+        last decode gave, in order"""
+        n = c_u64()
+        st = self.lib.atg_shn_decode_fetch_blocks(self.handle, track, None, 0, ctypes.byref(n))
+        if st not in (ATG_OK, ATG_ERR_CAPACITY):
+            self._check(st)
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._check(self.lib.atg_shn_decode_fetch_blocks(
+            self.handle, track, out.ctypes.data_as(ctypes.c_void_p), len(out), ctypes.byref(n)))
+        return out[:n.value]
+
+    def fetch_verbatim(self, results):
+        """the last decode's VERBATIM bytes (header then footer per stream)"""
+        nb = sum(r.header_bytes + r.footer_bytes for r in results)
+        out = np.empty(max(1, nb), dtype=np.uint8)
+        self._check(self.lib.atg_shn_decode_fetch_verbatim(
+            self.handle, out.ctypes.data_as(ctypes.c_void_p), nb))
+        return out[:nb]
+
+
 def default_device():
     """ATG_DEVICE, else LOCAL_RANK, else this process's turn of a node-wide
     round robin over the visible GPUs (atg_pick_device, csrc/devices.hip):
@@ -1647,6 +1897,16 @@ def tta_encoder():
 def tta_decoder():
     """process-wide True Audio decoder on ATG_DEVICE / LOCAL_RANK / device 0"""
     return _shared_handle(TtaDecoder)
+
+
+def shn_encoder():
+    """the process-wide Shorten encoder on the default device"""
+    return _shared_handle(ShnEncoder)
+
+
+def shn_decoder():
+    """the process-wide Shorten decoder on the default device"""
+    return _shared_handle(ShnDecoder)
 
 
 def wv_decoder():

@@ -29,7 +29,9 @@ raises the decode status at the frame where the reference would.
 `ALACDecoder` / `decode_alac_batch` do the same for ALAC in M4A
 (reference src/decoders/alac.c; GPU kernels alac_decode.hip).
 `TTADecoder` / `decode_tta_batch` do the same for True Audio (reference
-src/decoders/tta.c; GPU kernels tta_decode.hip), `WavPackDecoder` /
+src/decoders/tta.c; GPU kernels tta_decode.hip), `SHNDecoder` /
+`decode_shn_batch` for Shorten (src/decoders/shn.c; shn_decode.hip),
+`WavPackDecoder` /
 `decode_wavpack_batch` for WavPack (reference src/decoders/wavpack.c; GPU
 kernels wavpack_decode.hip).
 There is no CPU decoding path.
@@ -369,6 +371,110 @@ def decode_tta_batch(images):
         out.append((r.status, info,
                     pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
                     None if r.status == 0 else int(r.n_frames)))
+    return out
+
+
+# --------------------------------------------------------------- Shorten
+def _shn_error(table, status):
+    kind, msg = table.get(status, (ValueError, "unknown value from read_framelist()"))
+    return kind(msg)
+
+
+class SHNDecoder(object):
+    """reference src/decoders/shn.c SHNDecoder(file), decoded on the GPU
+    (shn_decode.hip):
+
+      SHNDecoder(file)   file object or bytes; ValueError for a wrong magic
+                         number, version or file type, IOError for a header
+                         that ends early (:37-96)
+      .sample_rate .bits_per_sample .channels .channel_mask
+      .read(n)           one set of channels (one block) per call, an empty
+                         FrameList after QUIT; ValueError for an unknown
+                         command and IOError for a stream that ends early,
+                         once the blocks before it are out (:153-191)
+      .pcm_split()       (bytes in front of the audio, bytes after it) from
+                         the VERBATIM commands (:193-294)
+      .close()
+    """
+
+    def __init__(self, file):
+        if isinstance(file, (bytes, bytearray, memoryview)):
+            data = bytes(file)
+        elif hasattr(file, "read"):
+            data = file.read()
+        else:
+            raise TypeError("file must be a file object or bytes")
+        st, info = _atgpu.shn_read_info(data)
+        if st:
+            raise _shn_error(_atgpu.SHN_HEADER_ERRORS, st)
+        self._data = data
+        self._info = info
+        self.sample_rate = info.sample_rate
+        self.bits_per_sample = info.bits_per_sample
+        self.channels = info.channels
+        self.channel_mask = info.channel_mask
+        self._closed = False
+        self._decoded = None
+        self._frame = 0    # sets of channels handed out
+        self._sample = 0   # and their samples
+
+    def _decode(self):
+        if self._decoded is None:
+            self._decoded = decode_shn_batch([self._data], details=True)[0]
+        return self._decoded
+
+    def read(self, pcm_frames=None):
+        if self._closed:
+            raise ValueError("cannot read closed stream")
+        status, _, samples, _, _, lengths = self._decode()
+        if self._frame >= len(lengths):
+            if status != _atgpu.SHN_END_OF_STREAM:
+                raise _shn_error(_atgpu.SHN_READ_ERRORS, status)
+            return pcm.empty_framelist(self.channels, self.bits_per_sample)
+        a = self._sample
+        n = lengths[self._frame]
+        self._frame += 1
+        self._sample += n * self.channels
+        return pcm.FrameList._wrap(samples[a:a + n * self.channels].copy(), self.channels,
+                                   self.bits_per_sample)
+
+    def pcm_split(self):
+        status, _, _, head, foot, _ = self._decode()
+        if status != _atgpu.SHN_END_OF_STREAM:
+            raise IOError("I/O error reading Shorten file")
+        return head, foot
+
+    def close(self):
+        self._closed = True
+
+
+def decode_shn_batch(images, details=False):
+    """decode a list of .shn images (bytes) in one GPU batch
+    -> list of (status, ShnInfo, int32 interleaved PCM, header bytes, footer
+    bytes); status is an ATG_SHN_* code (1 = the stream ended with QUIT), the
+    PCM ends before the first incomplete set of channels.  With details, each
+    tuple ends with the frame counts of the stream's sets of channels."""
+    parts, tracks, infos, pos = [], [], [], 0
+    for img in images:
+        img = bytes(img)
+        st, info = _atgpu.shn_read_info(img)
+        if st:
+            raise _shn_error(_atgpu.SHN_HEADER_ERRORS, st)
+        pad = (-len(img)) % 4
+        tracks.append(_atgpu.shn_dec_track(pos, len(img), info))
+        parts.append(img + b"\0" * pad)
+        infos.append(info)
+        pos += len(img) + pad
+    dec = _atgpu.shn_decoder()
+    pcm_i32, res, verb = dec.decode(b"".join(parts), tracks)
+    out = []
+    for k, (info, r) in enumerate(zip(infos, res)):
+        v = verb[r.verbatim_offset:r.verbatim_offset + r.header_bytes + r.footer_bytes].tobytes()
+        one = (r.status, info, pcm_i32[r.pcm_offset:r.pcm_offset + r.pcm_frames * info.channels],
+               v[:r.header_bytes], v[r.header_bytes:])
+        if details:
+            one += ([int(x) for x in dec.fetch_blocks(k)],)
+        out.append(one)
     return out
 
 

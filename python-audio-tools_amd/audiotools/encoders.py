@@ -37,7 +37,8 @@ chains on the GPU, the tracks sharded over the node's GPUs.
 src/encoders/alac.c:30-189; GPU kernels alac_encode.hip).
 
 `encode_tta` / `encode_tta_batch` do the same for True Audio (reference
-src/encoders/tta.c:31-114; GPU kernels tta_encode.hip).
+src/encoders/tta.c:31-114; GPU kernels tta_encode.hip), `encode_shn` /
+`encode_shn_batch` for Shorten (src/encoders/shn.c; shn_encode.hip).
 
 `encode_wavpack` / `encode_wavpack_batch` do the same for WavPack (reference
 src/encoders/wavpack.c; GPU kernels wavpack_encode.hip): complete .wv files.
@@ -277,6 +278,57 @@ def encode_tta(file, pcmreader):
     if not hasattr(file, "write"):
         raise TypeError("file must by a concrete file object")
     return encode_tta_batch([file], [pcmreader])[0]
+
+
+def encode_shn_batch(filenames, pcmreaders, is_big_endian, signed_samples, header_data,
+                     footer_data=None, block_size=256):
+    """several PCMReaders (same channels / bits) -> one .shn file each in one
+    GPU batch; header_data / footer_data are one bytes object per file (or
+    None for no footers)"""
+    filenames = list(filenames)
+    pcmreaders = list(pcmreaders)
+    if len(filenames) != len(pcmreaders):
+        raise ValueError("filenames and pcmreaders differ in length")
+    if not pcmreaders:
+        return
+    channels, bps = pcmreaders[0].channels, pcmreaders[0].bits_per_sample
+    if bps not in (8, 16):
+        raise ValueError("unsupported bits per sample")
+    for r in pcmreaders:
+        if (r.channels, r.bits_per_sample) != (channels, bps):
+            raise ValueError("all pcmreaders of a batch must share channels and "
+                             "bits-per-sample")
+    block_size = int(block_size)
+    parts, tracks, start = [], [], 0
+    for r in pcmreaders:
+        # a read that returns another length than the last becomes a
+        # BLOCKSIZE command (shn.c:213-218)
+        samples, sizes = _collect(r, block_size)
+        frames = len(samples) // channels
+        tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
+        parts.append(samples)
+        start += frames
+    pcm = (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)).astype(np.int16)
+    out, results = _atgpu.shn_encoder().encode(
+        pcm, tracks, channels, bps, block_size, is_big_endian, signed_samples,
+        headers=list(header_data), footers=None if footer_data is None else list(footer_data))
+    for name, res in zip(filenames, results):
+        with open(name, "wb") as f:
+            f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+    for r in pcmreaders:
+        r.close()
+
+
+def encode_shn(filename, pcmreader, is_big_endian, signed_samples, header_data,
+               footer_data=None, block_size=256):
+    """encode_shn(filename, pcmreader, is_big_endian, signed_samples,
+    header_data, footer_data=None, block_size=256)
+
+    writes the whole Shorten file, as the reference does
+    (src/encoders/shn.c:26-145): header_data goes into a leading VERBATIM
+    command, footer_data, if any, into one after the audio"""
+    encode_shn_batch([filename], [pcmreader], is_big_endian, signed_samples, [header_data],
+                     None if not footer_data else [footer_data], block_size)
 
 
 def encode_wavpack_batch(filenames, pcmreaders, block_size, total_pcm_frames=0,
