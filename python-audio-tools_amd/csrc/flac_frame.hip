@@ -347,16 +347,38 @@ __device__ __forceinline__ uint32_t crc_advq(uint32_t c, uint32_t q, int s)
 // rice-coded residual section of one lane from its kept zig-zag codes.
 // FULL (the register-staged kernel: every lane holds a whole 64-sample run,
 // hi = 64, and only lane 0 skips warm-up codes, lo <= 12): codes 12..63 are
-// written unconditionally, so no per-code lane mask is formed for them
+// written unconditionally, so no per-code lane mask is formed for them --
+// and two at a time: codes A, B (q zeros, then k + 1 bits each) are one put
+// of qA zeros and the 2 (k + 1) + qB bits valA << (qB + k + 1) | valB while
+// that length is at most 32.  A pair some lane of the wave cannot take that
+// way goes out as two puts (ballot, uniform branch): A, then B through the
+// pair's own put, so the unrolled code holds one put per code as before.
 template <bool FULL>
 __device__ __forceinline__ void emit_codes(LaneWriter &w, const uint32_t (&u)[ATG_RUN], int lo,
                                            int hi, uint32_t k)
 {
-    const uint32_t kmask = (1u << k) - 1u;
+    const uint32_t kmask = (1u << k) - 1u, kbit = 1u << k, k1 = k + 1u;
 #pragma unroll
-    for (int t = 0; t < ATG_RUN; ++t)
-        if (FULL ? (t >= ATG_FAST_ORDER || t >= lo) : (t >= lo && t < hi))
+    for (int t = 0; t < ATG_RUN; ++t) {
+        if (FULL && t >= ATG_FAST_ORDER) {
+            static_assert((ATG_RUN - ATG_FAST_ORDER) % 2 == 0, "codes past the warm-up pair up");
+            if ((t - ATG_FAST_ORDER) & 1)
+                continue; // written with its predecessor
+            const uint32_t qa = u[t] >> k, va = kbit | (u[t] & kmask);
+            const uint32_t qb = u[t + 1] >> k, vb = kbit | (u[t + 1] & kmask);
+            // (the shift reads 5 bits of its amount; v is unused past 32)
+            uint32_t z = qa, n = 2u * k1 + qb, v = (va << ((qb + k1) & 31u)) | vb;
+            if (!wave_all(n <= 32u)) {
+                w.put(qa, k1, va);
+                z = qb;
+                n = k1;
+                v = vb;
+            }
+            w.put(z, n, v);
+        } else if (FULL ? t >= lo : (t >= lo && t < hi)) {
             w.put(u[t] >> k, k + 1u, (1u << k) | (u[t] & kmask));
+        }
+    }
 }
 
 // REG = false: samples staged in LDS (any frame).  REG = true: the lane's

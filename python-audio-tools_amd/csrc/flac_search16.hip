@@ -41,6 +41,7 @@
 #include "flac_dev.h"
 #include "launch.h"
 #include "partsel.h"
+#include "pass2_swar.h"
 #include "pcm_read.h"
 #include "residual.h"
 #include "rice.h"
@@ -203,6 +204,24 @@ __device__ __forceinline__ uint32_t packed_vsum(const uint32_t (&up)[ATG_RUN / 2
         s = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, v) >> kk2, one, s, false);
     }
     return s;
+}
+
+// The same on plain 32-bit ops (pass2_swar.h) for halves that already hold
+// n (B's low half 0) and kv >= 1: v_lshrrev by kv - 1, v_bitop3 with two
+// per-lane constant words, v_sad_u16 accumulating |2m + 1| (m = n >> kv) of
+// both halves -- 3 VALU per two samples, one of them full rate.  Lane 0's
+// warm-up slots hold n = -1: |2(-1) + 1| = 1, which is 0 after (acc - 64) / 2.
+// Two accumulators: the v_sad chain is not one dependent run of 32.
+__device__ __forceinline__ uint32_t packed_vsum_swar(const uint32_t (&up)[ATG_RUN / 2], uint32_t kv)
+{
+    const SwarK c = swar_consts(kv < 15u ? kv : 15u); // v < 2^15: kv >= 15 gives 0
+    uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+    for (int t = 0; t < ATG_RUN / 2; t += 2) {
+        a0 = swar_step(up[t], c, a0);
+        a1 = swar_step(up[t + 1], c, a1);
+    }
+    return (a0 + a1 - (uint32_t)ATG_RUN) >> 1;
 }
 
 // packed int16 L - R per half word (v_pk_sub_u16): the side channel's
@@ -482,7 +501,12 @@ __device__ __forceinline__ uint32_t pass2_sum(const PkStore &st, uint32_t lane_s
                          : lane_sum < 32768u;
     if (wave_all(ok)) {
         const uint32_t s0 = loud ? 8u : 0u;
-        return packed_vsum(st.up, kv - s0, (bias >> s0) & 0xFFFFu);
+        const uint32_t kq = kv - s0, b_lo = (bias >> s0) & 0xFFFFu;
+        // the three-op form needs the halves to hold n itself and a shift
+        // kq - 1 >= 0 in every lane (wave-uniform branch)
+        if (wave_all(b_lo == 0u && kq >= 1u))
+            return packed_vsum_swar(st.up, kq);
+        return packed_vsum(st.up, kq, b_lo);
     }
     ReSum rs{kv, bias, 0u};
     redo(rs);

@@ -135,6 +135,12 @@ __global__ __launch_bounds__(256) void k_op(unsigned *out, unsigned a, unsigned 
             CHAINS8(asm volatile("v_add_i32 %0, %0, %1" : "+v"(x[k]) : "v"(x[(k + 1) & 7])))
         else if constexpr (OP == 51)
             CHAINS8(asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(*(double*)&x[k & 6]) : "v"(*(double*)&x[(k+2) & 6]), "v"(*(double*)&x[(k+4) & 6])))
+        else if constexpr (OP == 52)
+            CHAINS8(asm volatile("v_sad_u16 %0, %0, %1, %0" : "+v"(x[k]) : "v"(x[(k + 1) & 7])))
+        else if constexpr (OP == 53) // three VGPRs, the select table of pass2_swar.h
+            CHAINS8(asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x9a" : "+v"(x[k]) : "v"(x[(k + 1) & 7]), "v"(x[(k + 2) & 7])))
+        else if constexpr (OP == 54) // v_sad_u16 with a separate accumulator (pass 2's form)
+            CHAINS8(asm volatile("v_sad_u16 %0, %1, %2, %0" : "+v"(x[k]) : "v"(x[(k + 1) & 7]), "v"(x[(k + 2) & 7])))
     }
     unsigned s = 0;
 #pragma unroll
@@ -147,7 +153,8 @@ static const char *kNames[] = {"v_fma_f32",      "v_add_u32",      "v_xor_b32", 
                                "v_add3_u32",     "v_dot2_i32_i16", "v_dot2c_i32_i16", "v_alignbit_b32",
                                "v_perm_b32",     "v_mad_i32_i24",  "v_pk_add_u16",  "v_lshrrev_b32",
                                "v_cndmask_b32",  "v_max_u32",      "v_dot2_u32_u16", "v_pk_lshrrev_b16",
-                               "v_sad_u32",      "v_mov_b32",      "dep v_add_u32", "dep v_dot2", "v_ashrrev_i32 v-sh", "v_ashrrev_i32 31", "v_lshrrev_b32 s-sh", "v_add_u32 sgpr", "v_sub_u32", "v_max_i32", "v_and_b32", "v_or_b32", "v_lshlrev_b32", "v_cndmask_e64 s", "v_bfe_u32", "v_xad_u32", "v_cvt_pk_u16_u32", "v_add_u32_e64", "v_add_co_u32", "v_not_b32", "v_mul_u32_u24", "v_min3_u32", "v_lshl_add_u32", "v_bitop3_b32", "v_dot2_i32_i16 vv", "v_dot2c_i32_i16 vv", "v_lshlrev_b32 c", "v_cndmask vcc set", "v_perm vvv", "v_mad_i32_i24 vv", "v_max_i32 c", "v_min_u32", "v_mul_lo_u32", "v_dot4_i32_i8 vv", "v_add_i32 (sat?)", "v_pk_fma_f32"};
+                               "v_sad_u32",      "v_mov_b32",      "dep v_add_u32", "dep v_dot2", "v_ashrrev_i32 v-sh", "v_ashrrev_i32 31", "v_lshrrev_b32 s-sh", "v_add_u32 sgpr", "v_sub_u32", "v_max_i32", "v_and_b32", "v_or_b32", "v_lshlrev_b32", "v_cndmask_e64 s", "v_bfe_u32", "v_xad_u32", "v_cvt_pk_u16_u32", "v_add_u32_e64", "v_add_co_u32", "v_not_b32", "v_mul_u32_u24", "v_min3_u32", "v_lshl_add_u32", "v_bitop3_b32", "v_dot2_i32_i16 vv", "v_dot2c_i32_i16 vv", "v_lshlrev_b32 c", "v_cndmask vcc set", "v_perm vvv", "v_mad_i32_i24 vv", "v_max_i32 c", "v_min_u32", "v_mul_lo_u32", "v_dot4_i32_i8 vv", "v_add_i32 (sat?)", "v_pk_fma_f32",
+                               "v_sad_u16", "v_bitop3_b32 0x9a vvv", "v_sad_u16 vvv"};
 
 template <int OP>
 static void run(unsigned *d, int cus, int waves_per_simd)
@@ -188,18 +195,17 @@ int main()
     printf("CUs %d, clock %d kHz\n", cus, prop.clockRate);
     unsigned *d;
     hipMalloc(&d, (size_t)cus * 8 * 256 * sizeof(unsigned));
-    sweep<40>(d, cus);
-    sweep<41>(d, cus);
-    sweep<42>(d, cus);
-    sweep<43>(d, cus);
-    sweep<44>(d, cus);
-    sweep<45>(d, cus);
-    sweep<46>(d, cus);
-    sweep<47>(d, cus);
-    sweep<48>(d, cus);
-    sweep<49>(d, cus);
-    sweep<50>(d, cus);
-    sweep<51>(d, cus);
+    // pass 2's three-op form (pass2_swar.h) beside the ops it replaces
+    sweep<1>(d, cus);
+    sweep<11>(d, cus);
+    sweep<39>(d, cus);
+    sweep<53>(d, cus);
+    sweep<16>(d, cus);
+    sweep<52>(d, cus);
+    sweep<54>(d, cus);
+    sweep<14>(d, cus);
+    sweep<15>(d, cus);
+    sweep<10>(d, cus);
     hipFree(d);
     return 0;
 }

@@ -7,6 +7,12 @@
  * the kernel's order: FIXED always evaluated, LPC orders 12 .. 1, a job
  * pruned when its lane-sum bound exceeds (best finished LPC total - hdr).
  *
+ * k2_prune_sim [frames] orders: instead, every order's bound and exact total
+ * are formed first and the pruning is replayed with four job orders (12 .. 1
+ * as the kernel; estimate_order's pick first; the true best first; ascending
+ * lower bound) and with the threshold seeded by the VERBATIM size -- whether
+ * another order or seed would leave fewer jobs for pass 2.
+ *
  * Build: gcc -O2 -ffp-contract=off -o tools/bin/k2_prune_sim tools/k2_prune_sim.c -lm
  * (includes the CPU restatement oracle/flac_port.c for the LPC analysis).
  */
@@ -39,9 +45,31 @@ static float lb_lane(uint32_t lane_sum, uint32_t cnt)
     return l4 > 0.f ? (float)(uint32_t)l4 : 0.f;
 }
 
+/* jobs that reach pass 2 when the candidate's LPC jobs run in seq[] order
+ * from a threshold seed (0xFFFFFFFF: none) */
+static int replay(const int *seq, const uint32_t *lb, const uint32_t *hdr, const uint32_t *tot,
+                  uint32_t seed)
+{
+    uint32_t best = seed;
+    int survive = 0;
+    for (int q = 0; q < 12; ++q) {
+        const int o = seq[q];
+        const uint32_t thr = best == 0xFFFFFFFFu ? 0xFFFFFFFFu : (best > hdr[o] ? best - hdr[o] : 0);
+        if (thr != 0xFFFFFFFFu && lb[o] > thr)
+            continue;
+        survive++;
+        if (tot[o] < best)
+            best = tot[o];
+    }
+    return survive;
+}
+
 int main(int argc, char **argv)
 {
     const int n_frames = argc > 1 ? atoi(argv[1]) : 400;
+    const int orders_mode = argc > 2 && !strcmp(argv[2], "orders");
+    long st_pass2[5] = {0}, best_is_12 = 0, n_white = 0;
+    double lb_gap = 0, white_lb = 0, white_lb14 = 0, white_exact = 0;
     flacport_options o = {4096, 12, 0, 6, 1, 0, 1, 0, 0, 0, 0, 4096};
     enc_ctx *e = calloc(1, sizeof(enc_ctx));
     e->o = &o;
@@ -106,6 +134,83 @@ int main(int argc, char **argv)
             }
             uint32_t best = 0xFFFFFFFFu;
             subfr++;
+            if (orders_mode) {
+                uint32_t lbo[13], hdro[13], toto[13];
+                int truebest = 12;
+                for (int order = 12; order >= 1; --order) {
+                    int32_t cq[MAX_LPC];
+                    int sh;
+                    quantize(lp[order - 1], order, 12, cq, &sh);
+                    lpc_residual(s, 4096, order, cq, sh, res);
+                    hdro[order] = 7 + 1 + order * bps + 9 + order * 12;
+                    float lb = 0;
+                    for (int lane = 0; lane < 64; ++lane) {
+                        uint32_t sum = 0;
+                        int a = lane * 64 - order, b = a + 64;
+                        if (a < 0)
+                            a = 0;
+                        for (int i = a; i < b; ++i)
+                            sum += (uint32_t)abs(res[i]);
+                        lb += lb_lane(sum, lane ? 64 : 64 - order);
+                    }
+                    lbo[order] = (uint32_t)lb;
+                    plan_residuals(e, res, 4096 - order, 4096, order, &e->cand_res);
+                    toto[order] = hdro[order] + e->cand_res.bits;
+                    lb_gap += 1.0 - (double)lbo[order] / e->cand_res.bits;
+                    if (order == 12 || toto[order] <= toto[truebest]) /* ties: the lower order, as the encoder */
+                        truebest = order;
+                    if (white && order == 12) {
+                        /* the bound with every lane's k capped at 14 */
+                        double cap = 0;
+                        for (int lane = 0; lane < 64; ++lane) {
+                            uint64_t sum = 0;
+                            int a = lane * 64 - order, b = a + 64;
+                            if (a < 0)
+                                a = 0;
+                            for (int i = a; i < b; ++i)
+                                sum += (uint32_t)abs(res[i]);
+                            const double cnt = lane ? 64 : 64 - order, U = 2.0 * sum;
+                            double m = 1e300;
+                            for (int k = 0; k <= 14; ++k) {
+                                const double v = cnt * k + U / (double)(1u << k);
+                                m = v < m ? v : m;
+                            }
+                            cap += m;
+                        }
+                        n_white++;
+                        white_lb += (double)(lbo[12] + hdro[12]) / (bps * 4096.0);
+                        white_lb14 += (cap + hdro[12]) / (bps * 4096.0);
+                        white_exact += (double)toto[12] / (bps * 4096.0);
+                    }
+                }
+                best_is_12 += truebest == 12;
+                int seq[4][12];
+                const int est = (int)estimate_order(bps, 12, 12, 4096, err);
+                for (int q = 0, a = 0, b = 0; q < 12; ++q) {
+                    seq[0][q] = 12 - q;
+                    if (q == 0) {
+                        seq[1][a++] = est;
+                        seq[2][b++] = truebest;
+                    }
+                    if (12 - q != est)
+                        seq[1][a++] = 12 - q;
+                    if (12 - q != truebest)
+                        seq[2][b++] = 12 - q;
+                    seq[3][q] = 12 - q;
+                }
+                for (int i = 1; i < 12; ++i) /* ascending lower bound + header */
+                    for (int j = i; j > 0 && lbo[seq[3][j]] + hdro[seq[3][j]] <
+                                                 lbo[seq[3][j - 1]] + hdro[seq[3][j - 1]]; --j) {
+                        const int t = seq[3][j];
+                        seq[3][j] = seq[3][j - 1];
+                        seq[3][j - 1] = t;
+                    }
+                for (int q = 0; q < 4; ++q)
+                    st_pass2[q] += replay(seq[q], lbo, hdro, toto, 0xFFFFFFFFu);
+                st_pass2[4] += replay(seq[0], lbo, hdro, toto, bps * 4096u);
+                jobs += 12;
+                continue;
+            }
             for (int order = 12; order >= 1; --order) {
                 int32_t cq[MAX_LPC];
                 int sh;
@@ -157,6 +262,23 @@ int main(int argc, char **argv)
                     best = tot;
             }
         }
+    }
+    if (orders_mode) {
+        static const char *names[5] = {"order 12 .. 1 (the kernel's)", "estimate_order's pick first",
+                                       "the true best first", "ascending lower bound",
+                                       "12 .. 1, threshold seeded with VERBATIM"};
+        printf("subframes %ld  LPC jobs %ld\n", subfr, jobs);
+        for (int q = 0; q < 5; ++q)
+            printf("%-40s pass2 %ld (%.2f per subframe)\n", names[q], st_pass2[q],
+                   (double)st_pass2[q] / subfr);
+        printf("true best order is 12 in %.1f %% of subframes\n", 100.0 * best_is_12 / subfr);
+        printf("residual_lb below the exact residual bits by %.1f %% (mean over jobs)\n",
+               100.0 * lb_gap / jobs);
+        if (n_white)
+            printf("white-noise subframes %ld, order 12: (bound + header) / VERBATIM %.3f, with k <= 14 "
+                   "%.3f, exact / VERBATIM %.3f\n", n_white, white_lb / n_white, white_lb14 / n_white,
+                   white_exact / n_white);
+        return 0;
     }
     printf("subframes %ld  LPC jobs %ld  pass2 %ld (%.2f per subframe, %.1f %%)\n", subfr, jobs,
            pass2, (double)pass2 / subfr, 100.0 * pass2 / jobs);
