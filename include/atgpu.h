@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 4
+#define ATG_ABI_VERSION 5
 
 typedef enum {
     ATG_OK = 0,
@@ -508,8 +508,138 @@ atg_status atg_flac_decode_wait(atg_decoder *dec, uint64_t ticket,
                                 atg_flac_dec_result *results, const int32_t **d_pcm,
                                 uint64_t *total_samples);
 
-/* Per-kernel device time of the decoder's most recently waited batch. */
+/* Per-kernel device time of the decoder's most recently waited batch.  After
+   an Ogg FLAC batch the container pass's phases follow the seven of the
+   FLAC decode: ogg_walk, ogg_crc, ogg_gather. */
 int atg_decoder_kernel_times(atg_decoder *dec, const char **names, float *ms, int cap);
+
+/* ------------------------------------------------------------------ */
+/* Ogg FLAC decoder (.oga; trackverify / track2track through           */
+/* OggFlacAudio.to_pcm).  Replaces the reference's                      */
+/* audiotools.decoders.OggFlacDecoder: the page reader and packet       */
+/* iterator (src/ogg.c:24-119, 203-254), the first packet               */
+/* (src/decoders/oggflac.c:324-394) and the frame loop (:471-559), for  */
+/* a batch of images, on the atg_decoder handle.                        */
+/*                                                                      */
+/* Pages are read in file order; only the magic, the version, the       */
+/* end-of-stream flag, the lacing table and the checksum are used.  A   */
+/* page fails with the first of: invalid magic, invalid version,        */
+/* premature EOF (a read past the image anywhere in the page, a file    */
+/* that ends without an end-of-stream page included), checksum          */
+/* mismatch.  A page is checked whole before any of its segments is     */
+/* handed out; nothing is read after the end-of-stream page.  A packet  */
+/* is the segments up to the first lacing value below 255; one left     */
+/* unfinished at the end of the stream is dropped.  The first packet    */
+/* carries STREAMINFO and the number of header packets, which are       */
+/* skipped unparsed; every packet after them is decoded as one FLAC     */
+/* frame from its first byte, its reads bounded by the packet (bytes    */
+/* after the frame are ignored, total_samples is never consulted).      */
+/* Where the reference aborts -- a frame whose subframes end within the  */
+/* last two bytes of its packet -- the status is ATG_FD_EOF.             */
+/* ------------------------------------------------------------------ */
+
+/* Limits, refused with ATG_ERR_UNSUPPORTED before any launch: one image
+   (which bounds its pages, its packets and its largest packet) and the
+   batch buffer. */
+#define ATG_OGG_MAX_IMAGE_BYTES (1ull << 28)
+#define ATG_OGG_MAX_BATCH_BYTES (1ull << 32)
+/* which follow from the image size: a page is at least 27 bytes, a packet
+   takes at least one lacing byte */
+#define ATG_OGG_MAX_PAGES (ATG_OGG_MAX_IMAGE_BYTES / 27)
+#define ATG_OGG_MAX_PACKETS ATG_OGG_MAX_IMAGE_BYTES
+#define ATG_OGG_MAX_PACKET_BYTES ATG_OGG_MAX_IMAGE_BYTES
+
+/* What ended the container side of a stream: the reference's ogg_status
+   (src/ogg.h) and the first packet's errors (oggflac.c:324-394). */
+enum {
+    ATG_OGG_OK = 0,
+    ATG_OGG_MAGIC = 1,           /* ValueError "invalid magic number" */
+    ATG_OGG_VERSION = 2,         /* ValueError "invalid stream version" */
+    ATG_OGG_CHECKSUM = 3,        /* ValueError "checksum mismatch" */
+    ATG_OGG_PREMATURE_EOF = 4,   /* IOError "premature EOF reading Ogg stream" */
+    ATG_OGG_STREAM_FINISHED = 5, /* IOError "stream finished": no first packet,
+                                    or fewer header packets than stated */
+    ATG_OGG_PACKET_BYTE = 6,     /* ValueError "invalid packet byte" */
+    ATG_OGG_SIGNATURE = 7,       /* ValueError "invalid Ogg signature" */
+    ATG_OGG_MAJOR_VERSION = 8,   /* ValueError "invalid major version" */
+    ATG_OGG_MINOR_VERSION = 9,   /* ValueError "invalid minor version" */
+    ATG_OGG_FLAC_SIGNATURE = 10, /* ValueError "invalid fLaC signature" */
+    ATG_OGG_BLOCK_TYPE = 11,     /* ValueError "invalid block type" */
+    ATG_OGG_STREAMINFO_EOF = 12  /* IOError "EOF while reading STREAMINFO block" */
+};
+
+/* The first packet of an image in host memory (oggflac_read_streaminfo), read
+   through pages checked as above: STREAMINFO, the header-packet count, the
+   first page's serial number, and the channel mask a VORBIS_COMMENT header
+   packet's WAVEFORMATEXTENSIBLE_CHANNEL_MASK gives (else the default for the
+   channel count).  si.frames_offset = byte of the image where the page after
+   the first packet's last page starts. */
+typedef struct {
+    atg_flac_streaminfo si;
+    uint32_t header_packets;
+    uint32_t serial_number;
+    uint32_t has_channel_mask; /* the tag was present and matched the channels */
+    uint32_t reserved;
+} atg_oggflac_info;
+
+/* Returns ATG_OGG_OK or the ATG_OGG_* value of the failure; host code only. */
+int atg_oggflac_read_info(const uint8_t *data, uint64_t len, atg_oggflac_info *info);
+
+/* One stream of a batch: its whole image data[data_offset, +data_bytes). */
+typedef struct {
+    uint64_t data_offset;
+    uint64_t data_bytes;
+} atg_oggflac_dec_track;
+
+/* Per-stream result: the stream hands out n_frames FLAC frames = pcm_frames
+   PCM frames (interleaved int32 at PCM-frame index pcm_offset of the batch
+   output; sample_offset is the same place as an index of interleaved
+   samples, exact also in a batch of streams with different channel counts,
+   which the caller of this entry cannot sort beforehand) and then ends with
+   the first failure in stream order: `status` when
+   a frame failed (ATG_FD_*), else `ogg_status` when the container ran out or
+   failed, else status ATG_FD_MD5 or, with both 0, success.  md5 = MD5 of the
+   frames' little-endian PCM bytes.  pages = pages that passed every check
+   before the first failing one; packets = packets completed in them;
+   fail_page / fail_offset = index and image byte of the failing page
+   (0xFFFFFFFF / 0 when the stream ended by its flag).  The STREAMINFO fields
+   are zero unless the first packet parsed. */
+typedef struct {
+    uint64_t pcm_offset;
+    uint64_t pcm_frames;
+    uint32_t n_frames;
+    int32_t status;
+    int32_t ogg_status;
+    uint32_t header_packets;
+    uint8_t md5[16];
+    uint32_t pages;
+    uint32_t packets;
+    uint32_t fail_page;
+    uint32_t reserved;
+    uint64_t fail_offset;
+    uint32_t sample_rate, channels, bits_per_sample, max_block_size;
+    uint64_t total_samples;
+    uint8_t streaminfo_md5[16];
+    uint64_t sample_offset;
+} atg_oggflac_dec_result;
+
+/* As atg_flac_decode_host / _device / _fetch.  The container pass (page walk,
+   page CRC-32, packet table, gather into per-stream contiguous buffers) and
+   the frame decode run on the GPU; three host round trips for the counts.
+   frame_offsets of the fetch are relative to the stream's first audio packet
+   in the compacted stream.  Fails with ATG_ERR_INVALID while an
+   atg_flac_decode_device_async batch is unwaited. */
+atg_status atg_oggflac_decode_host(atg_decoder *dec, const uint8_t *data, uint64_t len,
+                                   const atg_oggflac_dec_track *tracks, uint32_t n_tracks,
+                                   atg_oggflac_dec_result *results, uint64_t *total_samples,
+                                   uint64_t *total_frames);
+atg_status atg_oggflac_decode_device(atg_decoder *dec, const void *d_data, uint64_t len,
+                                     const atg_oggflac_dec_track *tracks, uint32_t n_tracks,
+                                     atg_oggflac_dec_result *results, const int32_t **d_pcm,
+                                     uint64_t *total_samples);
+atg_status atg_oggflac_decode_fetch(atg_decoder *dec, int32_t *pcm, uint64_t pcm_cap,
+                                    uint64_t *frame_offsets, uint32_t *frame_block_sizes,
+                                    uint64_t frame_cap);
 
 /* ------------------------------------------------------------------ */
 /* Integer PCM converters (track2track --bits-per-sample / --channels). */

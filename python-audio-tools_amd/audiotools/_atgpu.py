@@ -48,6 +48,8 @@ EXPORTS = (
     "atg_flac_decode_device", "atg_flac_decode_device_async", "atg_flac_decode_wait",
     "atg_decoder_kernel_times", "atg_decoder_set_inflight",
     "atg_decoder_set_frame_hypothesis", "atg_decoder_frame_hypothesis_redos",
+    "atg_oggflac_read_info", "atg_oggflac_decode_host", "atg_oggflac_decode_device",
+    "atg_oggflac_decode_fetch",
     "atg_pcm_convert_last_error", "atg_pcm_convert_out_channels",
     "atg_pcm_convert_device", "atg_pcm_convert_host",
     "atg_replaygain_last_error", "atg_replaygain_device", "atg_replaygain_hist_gain",
@@ -139,6 +141,42 @@ class DecResult(ctypes.Structure):
                 ("md5", ctypes.c_uint8 * 16), ("walk_status", c_i32),
                 ("reserved", c_u32), ("walk_end", c_u64)]
 
+
+class OggFlacInfo(ctypes.Structure):
+    _fields_ = [("si", StreamInfo), ("header_packets", c_u32), ("serial_number", c_u32),
+                ("has_channel_mask", c_u32), ("reserved", c_u32)]
+
+
+class OggFlacDecTrack(ctypes.Structure):
+    _fields_ = [("data_offset", c_u64), ("data_bytes", c_u64)]
+
+
+class OggFlacDecResult(ctypes.Structure):
+    _fields_ = [("pcm_offset", c_u64), ("pcm_frames", c_u64), ("n_frames", c_u32),
+                ("status", c_i32), ("ogg_status", c_i32), ("header_packets", c_u32),
+                ("md5", ctypes.c_uint8 * 16), ("pages", c_u32), ("packets", c_u32),
+                ("fail_page", c_u32), ("reserved", c_u32), ("fail_offset", c_u64),
+                ("sample_rate", c_u32), ("channels", c_u32), ("bits_per_sample", c_u32),
+                ("max_block_size", c_u32), ("total_samples", c_u64),
+                ("streaminfo_md5", ctypes.c_uint8 * 16), ("sample_offset", c_u64)]
+
+
+# Ogg FLAC container status (include/atgpu.h ATG_OGG_*) with the reference's
+# messages (src/ogg.c ogg_strerror, src/decoders/oggflac.c:324-394); the
+# IOError ones per ogg_exception (ogg.c:277-292)
+OGG_OK, OGG_MAGIC, OGG_VERSION, OGG_CHECKSUM, OGG_PREMATURE_EOF, OGG_STREAM_FINISHED = range(6)
+OGG_PACKET_BYTE, OGG_SIGNATURE, OGG_MAJOR_VERSION, OGG_MINOR_VERSION = 6, 7, 8, 9
+OGG_FLAC_SIGNATURE, OGG_BLOCK_TYPE, OGG_STREAMINFO_EOF = 10, 11, 12
+OGG_MESSAGES = {
+    1: "invalid magic number", 2: "invalid stream version", 3: "checksum mismatch",
+    4: "premature EOF reading Ogg stream", 5: "stream finished", 6: "invalid packet byte",
+    7: "invalid Ogg signature", 8: "invalid major version", 9: "invalid minor version",
+    10: "invalid fLaC signature", 11: "invalid block type",
+    12: "EOF while reading STREAMINFO block",
+}
+OGG_IOERRORS = (4, 5, 12)
+OGG_MAX_IMAGE_BYTES = 1 << 28
+OGG_MAX_BATCH_BYTES = 1 << 32
 
 # decode status codes (include/atgpu.h ATG_FD_*) and the reference's
 # messages for them (src/decoders/flac.c FlacDecoder_strerror, read())
@@ -496,6 +534,19 @@ def load_library():
             P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),
             ctypes.c_int]
         lib.atg_decoder_kernel_times.restype = ctypes.c_int
+        lib.atg_oggflac_read_info.argtypes = [ctypes.c_char_p, c_u64,
+                                              ctypes.POINTER(OggFlacInfo)]
+        lib.atg_oggflac_read_info.restype = ctypes.c_int
+        lib.atg_oggflac_decode_host.argtypes = [
+            P, P, c_u64, ctypes.POINTER(OggFlacDecTrack), c_u32,
+            ctypes.POINTER(OggFlacDecResult), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
+        lib.atg_oggflac_decode_host.restype = ctypes.c_int
+        lib.atg_oggflac_decode_device.argtypes = [
+            P, P, c_u64, ctypes.POINTER(OggFlacDecTrack), c_u32,
+            ctypes.POINTER(OggFlacDecResult), ctypes.POINTER(P), ctypes.POINTER(c_u64)]
+        lib.atg_oggflac_decode_device.restype = ctypes.c_int
+        lib.atg_oggflac_decode_fetch.argtypes = [P, P, c_u64, P, P, c_u64]
+        lib.atg_oggflac_decode_fetch.restype = ctypes.c_int
         lib.atg_pcm_convert_last_error.restype = ctypes.c_char_p
         lib.atg_pcm_convert_out_channels.argtypes = [ctypes.c_int, c_u32]
         lib.atg_pcm_convert_out_channels.restype = c_u32
@@ -1219,6 +1270,68 @@ class Decoder(_Handle):
         self._check(self.lib.atg_flac_decode_wait(self.handle, ticket, res, ctypes.byref(dp),
                                                   ctypes.byref(ns)))
         return [res[i] for i in range(n)], dp.value, ns.value
+
+    def decode_oggflac(self, data, tracks, fetch_pcm=True):
+        """decode a batch of Ogg FLAC images in host memory.  data: bytes-like
+        holding every image; tracks: list of OggFlacDecTrack.  -> (pcm int32
+        array, [OggFlacDecResult], frame block sizes (uint32))"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = len(tracks)
+        arr = (OggFlacDecTrack * max(1, n))(*tracks)
+        res = (OggFlacDecResult * max(1, n))()
+        ns, nf = c_u64(), c_u64()
+        self._check(self.lib.atg_oggflac_decode_host(
+            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
+            ctypes.byref(ns), ctypes.byref(nf)))
+        pcm = np.empty(max(1, ns.value), dtype=np.int32) if fetch_pcm else None
+        bss = np.empty(max(1, nf.value), dtype=np.uint32)
+        self._check(self.lib.atg_oggflac_decode_fetch(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p) if fetch_pcm else None, ns.value,
+            None, bss.ctypes.data_as(ctypes.c_void_p), nf.value))
+        return (pcm[:ns.value] if fetch_pcm else None, [res[i] for i in range(n)],
+                bss[:nf.value])
+
+    def decode_oggflac_device(self, d_data, nbytes, tracks):
+        """decode a batch of Ogg FLAC images already in device memory ->
+        ([OggFlacDecResult], device pointer of the int32 PCM, interleaved samples)"""
+        n = len(tracks)
+        arr = (OggFlacDecTrack * max(1, n))(*tracks)
+        res = (OggFlacDecResult * max(1, n))()
+        dp = ctypes.c_void_p()
+        ns = c_u64()
+        self._check(self.lib.atg_oggflac_decode_device(
+            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
+            ctypes.byref(ns)))
+        return [res[i] for i in range(n)], dp.value, ns.value
+
+
+def oggflac_read_info(data):
+    """the first packet of an Ogg FLAC image (host C in libatgpu)
+    -> (ATG_OGG_* status, OggFlacInfo)"""
+    lib = load_library()
+    info = OggFlacInfo()
+    rc = lib.atg_oggflac_read_info(bytes(data), len(data), ctypes.byref(info))
+    return rc, info
+
+
+def oggflac_dec_track(offset, nbytes):
+    t = OggFlacDecTrack()
+    t.data_offset = offset
+    t.data_bytes = nbytes
+    return t
+
+
+def oggflac_pack(images):
+    """whole images -> (batch buffer with every image 4-byte aligned and room
+    to read the last word, [OggFlacDecTrack])"""
+    parts, tracks, pos = [], [], 0
+    for img in images:
+        img = bytes(img)
+        tracks.append(oggflac_dec_track(pos, len(img)))
+        pad = (-len(img)) % 4
+        parts.append(img + bytes(pad))
+        pos += len(img) + pad
+    return b"".join(parts), tracks
 
 
 class AlacEncoder(_Handle):

@@ -33,7 +33,9 @@ src/decoders/tta.c; GPU kernels tta_decode.hip), `SHNDecoder` /
 `decode_shn_batch` for Shorten (src/decoders/shn.c; shn_decode.hip),
 `WavPackDecoder` /
 `decode_wavpack_batch` for WavPack (reference src/decoders/wavpack.c; GPU
-kernels wavpack_decode.hip).
+kernels wavpack_decode.hip), `OggFlacDecoder` / `decode_oggflac_batch` for
+Ogg FLAC (src/ogg.c, src/decoders/oggflac.c; ogg_demux.hip and
+flac_decode.hip).
 There is no CPU decoding path.
 """
 
@@ -636,3 +638,118 @@ def decode_wavpack_batch(images, md5_mode=1):
                     pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
                     bad))
     return out
+
+
+# -------------------------------------------------------------- Ogg FLAC
+def _oggflac_error(r):
+    """the exception the reference raises for a result: the frame's error
+    first, then the container's, then the MD5's; None for success"""
+    if r.status not in (_atgpu.FD_OK, _atgpu.FD_MD5):
+        if r.status == _atgpu.FD_EOF:
+            return IOError("I/O error decoding FLAC frame")
+        return ValueError(_atgpu.FD_MESSAGES.get(r.status, "Error"))
+    if r.ogg_status != _atgpu.OGG_OK:
+        msg = _atgpu.OGG_MESSAGES.get(r.ogg_status, "unknown error")
+        return IOError(msg) if r.ogg_status in _atgpu.OGG_IOERRORS else ValueError(msg)
+    if r.status == _atgpu.FD_MD5:
+        return ValueError(_atgpu.FD_MESSAGES[_atgpu.FD_MD5])
+    return None
+
+
+def _oggflac_in_headers(r):
+    """the failure came before the first audio packet: the reference raises
+    it from OggFlacDecoder's constructor (oggflac.c:86-107)"""
+    if r.ogg_status == _atgpu.OGG_OK:
+        return False
+    return r.ogg_status >= _atgpu.OGG_PACKET_BYTE or r.packets < 1 + r.header_packets
+
+
+def decode_oggflac_batch(images):
+    """decode a list of Ogg FLAC (.oga) images (bytes) in one GPU batch: the
+    container (pages, page checksums, packets) and the frames.
+    -> list of (OggFlacDecResult, int32 interleaved PCM, frame block sizes);
+    the result's status / ogg_status say what ended the stream (both 0 =
+    decoded and MD5-verified), the PCM is what came before that."""
+    images = [bytes(i) for i in images]
+    devs = _atgpu.batch_devices()
+    ranges = (_atgpu.shard_ranges([max(1, len(i)) for i in images], len(devs))
+              if len(devs) > 1 else [(0, len(images))])
+
+    def shard(i):
+        t0, t1 = ranges[i]
+        data, tracks = _atgpu.oggflac_pack(images[t0:t1])
+        dec = (_atgpu.decoder() if len(ranges) == 1
+               else _atgpu.shard_object("decoder", i, devs[i]))
+        return dec.decode_oggflac(data, tracks)
+
+    out = []
+    for pcm_i32, res, bss in _atgpu.run_shards(shard, len(ranges)):
+        frame = 0
+        for r in res:
+            a = r.sample_offset
+            out.append((r, pcm_i32[a:a + r.pcm_frames * r.channels],
+                        bss[frame:frame + r.n_frames]))
+            frame += r.n_frames
+    return out
+
+
+class OggFlacDecoder(object):
+    """reference src/decoders/oggflac.c OggFlacDecoder(filename, channel_mask),
+    decoded on the GPU (ogg_demux.hip, flac_decode.hip):
+
+      OggFlacDecoder(filename, channel_mask)
+                     IOError if the file cannot be opened; the container's
+                     and the first packet's errors up to the first audio
+                     packet (ValueError, or IOError for a premature EOF, a
+                     stream that finishes among its header packets and a short
+                     STREAMINFO) (:53-123)
+      .sample_rate .bits_per_sample .channels .channel_mask
+      .read(n)       one FLAC frame per call; ValueError with the reference's
+                     message for a bad frame or page, IOError "I/O error
+                     decoding FLAC frame" for a frame cut by its packet,
+                     IOError for a premature EOF; at the end of the stream the
+                     MD5 check, then empty FrameLists (:145-273)
+      .close()       further reads raise ValueError
+    """
+
+    def __init__(self, filename, channel_mask):
+        if not isinstance(filename, str) or isinstance(channel_mask, bool) or \
+                not isinstance(channel_mask, int):
+            raise TypeError("OggFlacDecoder(filename: str, channel_mask: int)")
+        if channel_mask < 0:
+            raise ValueError("channel_mask must be >= 0")
+        with open(filename, "rb") as f:  # IOError with errno + filename
+            data = f.read()
+        r, samples, sizes = decode_oggflac_batch([data])[0]
+        if _oggflac_in_headers(r):
+            raise _oggflac_error(r)
+        self.sample_rate = r.sample_rate
+        self.bits_per_sample = r.bits_per_sample
+        self.channels = r.channels
+        self.channel_mask = channel_mask
+        self._samples = samples
+        self._sizes = [int(x) for x in sizes]
+        self._error = _oggflac_error(r)
+        self._frame = 0
+        self._at = 0
+        self._finalized = False
+        self._closed = False
+
+    def read(self, pcm_frames=None):
+        if self._closed:
+            raise ValueError("cannot read closed stream")
+        if self._finalized:
+            return pcm.empty_framelist(self.channels, self.bits_per_sample)
+        if self._frame < len(self._sizes):
+            n = self._sizes[self._frame] * self.channels
+            self._frame += 1
+            a, self._at = self._at, self._at + n
+            return pcm.FrameList._wrap(self._samples[a:a + n].copy(), self.channels,
+                                       self.bits_per_sample)
+        if self._error is not None:
+            raise self._error
+        self._finalized = True
+        return pcm.empty_framelist(self.channels, self.bits_per_sample)
+
+    def close(self):
+        self._closed = True

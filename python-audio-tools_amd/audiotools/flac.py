@@ -349,3 +349,83 @@ def _unlink(filename):
         os.unlink(filename)
     except OSError:
         pass
+
+
+# ---------------------------------------------------------------- Ogg FLAC
+# InvalidFLAC messages of OggFlacAudio.__read_streaminfo__ (reference
+# audiotools/flac.py:3163-3227, text.py:578-585); the page checks the
+# reference leaves to its decoder are reported here with the decoder's words
+_OGGFLAC_INIT_MESSAGES = {
+    _atgpu.OGG_MAGIC: "invalid Ogg magic number",
+    _atgpu.OGG_VERSION: "invalid Ogg version",
+    _atgpu.OGG_CHECKSUM: "Ogg page checksum mismatch",
+    _atgpu.OGG_PACKET_BYTE: "invalid packet byte",
+    _atgpu.OGG_SIGNATURE: "invalid Ogg signature",
+    _atgpu.OGG_MAJOR_VERSION: "invalid major version",
+    _atgpu.OGG_MINOR_VERSION: "invalid minor version",
+    _atgpu.OGG_FLAC_SIGNATURE: "invalid FLAC signature",
+}
+
+
+class OggFlacAudio(FlacAudio):
+    """the read side of the reference's OggFlacAudio (audiotools/flac.py:
+    3040-3246): STREAMINFO from the first Ogg packet, to_pcm through
+    decoders.OggFlacDecoder (GPU), verify and convert as AudioFile's.
+    Writing is not provided: the reference's from_pcm pipes PCM into the
+    external `flac --ogg` program."""
+
+    SUFFIX = "oga"
+    NAME = SUFFIX
+    DESCRIPTION = u"Ogg FLAC"
+
+    def __init__(self, filename):
+        AudioFile.__init__(self, filename)
+        try:
+            with open(filename, "rb") as f:
+                data = f.read()
+        except IOError as err:
+            raise InvalidFLAC(str(err))
+        rc, info = _atgpu.oggflac_read_info(data)
+        if rc:
+            raise InvalidFLAC(_OGGFLAC_INIT_MESSAGES.get(
+                rc, _atgpu.OGG_MESSAGES.get(rc, "invalid Ogg FLAC file")))
+        self._si = info.si
+        self._info = info
+        self.__serial_number__ = info.serial_number
+        self.__header_packets__ = info.header_packets
+
+    def channel_mask(self):
+        """mono and stereo fixed, else the VORBIS_COMMENT packet's
+        WAVEFORMATEXTENSIBLE_CHANNEL_MASK when its speaker count matches,
+        else FLAC's default for the count (flac.py:1284-1341)"""
+        if self.channels() <= 2:
+            return ChannelMask.from_channels(self.channels())
+        return ChannelMask(self._si.channel_mask)
+
+    def to_pcm(self):
+        """OggFlacDecoder over the file; a PCMReaderError carrying the
+        message if it cannot be opened (flac.py:3229-3246)"""
+        from . import decoders
+        from . import PCMReaderError
+        try:
+            return decoders.OggFlacDecoder(self.filename, int(self.channel_mask()))
+        except (IOError, ValueError) as msg:
+            return PCMReaderError(error_message=str(msg),
+                                  sample_rate=self.sample_rate(),
+                                  channels=self.channels(),
+                                  channel_mask=int(self.channel_mask()),
+                                  bits_per_sample=self.bits_per_sample())
+
+    def convert(self, target_path, target_class, compression=None, progress=None):
+        from . import to_pcm_progress
+        return target_class.from_pcm(target_path, to_pcm_progress(self, progress),
+                                     compression, total_pcm_frames=self.total_frames())
+
+    @classmethod
+    def from_pcm(cls, filename, pcmreader, compression=None, total_pcm_frames=None,
+                 encoding_function=None):
+        raise EncodingError("writing Ogg FLAC is not supported: the reference encodes it "
+                            "through the external flac program")
+
+    def update_metadata(self, metadata):
+        raise NotImplementedError("Ogg FLAC metadata cannot be written")

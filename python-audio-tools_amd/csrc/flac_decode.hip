@@ -48,6 +48,7 @@
 
 #include "../../include/atgpu.h"
 #include "launch.h"
+#include "ogg_demux.h"
 #include "wave.h"
 
 namespace {
@@ -1713,7 +1714,284 @@ __global__ __launch_bounds__(256) void k_dec_emit(const DecTrack *__restrict__ t
     }
 }
 
+// ---- Ogg FLAC (ogg_demux.hip leaves a compacted stream and its packet table)
+//
+// The frame table is known, not guessed: every audio packet is one frame at a
+// known position whose reads end at its packet's end, so there is no sync
+// scan, no frame-end hypothesis and no `remaining` truncation; the walk goes
+// packet i -> packet i + 1.  The parse is parse_frame with the packet as the
+// EOF bound, the CRC-16 pass, restore, emit and MD5 are the native ones.
+
+// what the first packet says (oggflac_read_streaminfo, oggflac.c:324-394)
+struct OggHdr {
+    int32_t status;          // ATG_OGG_OK, a first-packet error, or what ended the headers
+    uint32_t header_packets; // the count the first packet states
+    uint32_t first_audio;    // stream-relative packet index
+    uint32_t n_audio;
+    uint64_t total;          // STREAMINFO total samples (never consulted)
+    uint32_t min_bs, pad;    // pad: 1 once STREAMINFO was read
+    uint8_t md5[16];
+};
+
+__global__ __launch_bounds__(64) void k_ogg_tracks(const uint32_t *__restrict__ w,
+                                                   const OggStream *__restrict__ streams,
+                                                   const OggSum *__restrict__ sum, uint32_t nt,
+                                                   const uint64_t *__restrict__ pk_pos,
+                                                   const uint32_t *__restrict__ pk_len,
+                                                   DecTrack *__restrict__ tr,
+                                                   OggHdr *__restrict__ hdr)
+{
+    const uint32_t ti = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ti >= nt)
+        return;
+    const OggStream st = streams[ti];
+    const OggSum sm = sum[ti];
+    OggHdr h;
+    h.status = ATG_OGG_OK;
+    h.header_packets = h.first_audio = h.n_audio = 0;
+    h.total = 0;
+    h.min_bs = h.pad = 0;
+    for (int i = 0; i < 16; ++i)
+        h.md5[i] = 0;
+    DecTrack t;
+    t.start = t.end = st.out_base + sm.bytes;
+    t.total = 0;
+    t.rate = 0;
+    t.channels = 1; // (a stream without STREAMINFO decodes nothing)
+    t.bps = 16;
+    t.max_bs = 1;
+    t.frame_base = t.pcm_base = t.md5_base = t.job_base = 0;
+    // a read past what the stream delivers: the page failure, or its end
+    const int32_t ran_out = sm.status != ATG_OGG_OK ? sm.status : ATG_OGG_STREAM_FINISHED;
+    if (sm.packets == 0) {
+        h.status = ran_out;
+    } else {
+        const uint64_t p = pk_pos[st.pkt_base];
+        const uint32_t L = pk_len[st.pkt_base];
+        auto B = [&](uint32_t i) { return byte_at(w, p + i); };
+        // the reference's reads in order: a mismatch is seen only once its
+        // bytes were read
+        if (L < 1) h.status = ATG_OGG_STREAMINFO_EOF;
+        else if (B(0) != 0x7Fu) h.status = ATG_OGG_PACKET_BYTE;
+        else if (L < 5) h.status = ATG_OGG_STREAMINFO_EOF;
+        else if (B(1) != 'F' || B(2) != 'L' || B(3) != 'A' || B(4) != 'C') h.status = ATG_OGG_SIGNATURE;
+        else if (L < 6) h.status = ATG_OGG_STREAMINFO_EOF;
+        else if (B(5) != 1u) h.status = ATG_OGG_MAJOR_VERSION;
+        else if (L < 7) h.status = ATG_OGG_STREAMINFO_EOF;
+        else if (B(6) != 0u) h.status = ATG_OGG_MINOR_VERSION;
+        else if (L < 9) h.status = ATG_OGG_STREAMINFO_EOF;
+        else {
+            h.header_packets = (B(7) << 8) | B(8);
+            if (L < 13) h.status = ATG_OGG_STREAMINFO_EOF;
+            else if (B(9) != 'f' || B(10) != 'L' || B(11) != 'a' || B(12) != 'C') h.status = ATG_OGG_FLAC_SIGNATURE;
+            else if (L < 14) h.status = ATG_OGG_STREAMINFO_EOF;
+            else if (B(13) & 0x7Fu) h.status = ATG_OGG_BLOCK_TYPE;
+            else if (L < 51) h.status = ATG_OGG_STREAMINFO_EOF;
+        }
+        if (h.status == ATG_OGG_OK) {
+            h.pad = 1; // STREAMINFO was read
+            h.min_bs = (B(17) << 8) | B(18);
+            t.max_bs = (B(19) << 8) | B(20);
+            t.rate = (B(27) << 12) | (B(28) << 4) | (B(29) >> 4);
+            t.channels = ((B(29) >> 1) & 7u) + 1u;
+            t.bps = (((B(29) & 1u) << 4) | (B(30) >> 4)) + 1u;
+            h.total = ((uint64_t)(B(30) & 15u) << 32) | ((uint64_t)B(31) << 24) | (B(32) << 16) |
+                      (B(33) << 8) | B(34);
+            t.total = h.total;
+            for (uint32_t i = 0; i < 16; ++i)
+                h.md5[i] = (uint8_t)B(35 + i);
+            if (sm.packets < 1ull + h.header_packets) {
+                h.status = ran_out; // the header packets are skipped unparsed
+            } else {
+                h.first_audio = 1u + h.header_packets;
+                h.n_audio = sm.packets - h.first_audio;
+                if (h.n_audio)
+                    t.start = pk_pos[st.pkt_base + h.first_audio];
+            }
+        }
+    }
+    tr[ti] = t;
+    hdr[ti] = h;
+}
+
+// A residual whose partition order does not divide the block is rejected by
+// the parse (FD_ERROR: the reference predicts from a stale buffer there).
+// The reference itself reads on with partitions of block / 2^order values,
+// rounded down, and fails further on -- an error in a later subframe, the
+// packet's end, or, the bytes being damaged, the CRC-16.  An Ogg packet
+// bounds the frame, so that outcome is known without decoding a sample: this
+// walks the frame with the reference's partition lengths (plain serial
+// reads; damaged streams only) and returns what stops it.  A frame that
+// passes even its CRC-16 stays FD_ERROR.
+__device__ int loose_subframe(BitR &r, uint32_t N, uint32_t bps)
+{
+    SubHdr sh;
+    const int rc = dec_subhdr(r, sh);
+    if (rc)
+        return rc;
+    bps -= sh.wasted;
+    if (sh.kind == 0) {
+        r.get_signed(bps);
+    } else if (sh.kind == 1) {
+        r.skip_far(bps ? (uint64_t)N * bps : (N ? 1ull << 33 : 0ull));
+    } else {
+        for (uint32_t i = 0; i < sh.order; ++i)
+            r.get_signed(bps);
+        if (sh.kind == 3) {
+            const uint32_t prec = r.get(4) + 1;
+            r.get_signed(5);
+            for (uint32_t i = 0; i < sh.order; ++i)
+                r.get_signed(prec);
+        }
+        const uint32_t method = r.get(2), porder = r.get(4);
+        if (method > 1)
+            RET(FD_CODING);
+        const uint32_t plen = N >> porder;
+        for (uint32_t part = 0; part < (1u << porder); ++part) {
+            uint32_t cnt = part ? plen : (plen > sh.order ? plen - sh.order : 0u);
+            const uint32_t rice = r.get(method ? 5u : 4u);
+            const uint32_t esc = rice == (method ? 0x1Fu : 0xFu) ? r.get(5) : 0u;
+            if (r.eof())
+                return FD_EOF;
+            if (esc) {
+                r.skip_far((uint64_t)cnt * esc);
+            } else {
+                for (; cnt; --cnt) {
+                    r.zeros();
+                    r.get(rice);
+                    if (r.eof())
+                        return FD_EOF;
+                }
+            }
+        }
+        if (r.eof())
+            return FD_EOF;
+        if (sh.kind == 2 && sh.order > 4)
+            return FD_FIXED_ORDER;
+    }
+    return r.eof() ? FD_EOF : FD_OK;
+}
+
+__device__ int loose_frame(const uint32_t *w, uint64_t nw, uint64_t pos, const DecTrack &t)
+{
+    BitR r;
+    r.init(w, nw, pos * 8, t.end * 8);
+    Hdr h;
+    int rc = dec_header(r, t, h);
+    for (uint32_t c = 0; !rc && c < h.ch; ++c)
+        rc = loose_subframe(r, h.bs, sub_bps(h.assign, c, h.bps));
+    if (rc)
+        return rc;
+    const uint32_t a = (uint32_t)(r.abspos() & 7);
+    if (a)
+        r.skip(8 - a);
+    r.get(16);
+    if (r.eof())
+        return FD_EOF;
+    return crc16_range(w, pos, r.abspos() >> 3, c_crc16) ? FD_FRAME_CRC : FD_ERROR;
+}
+
+// lane per packet: the frame in an audio packet, reads bounded by the packet
+__global__ __launch_bounds__(64) void k_ogg_parse(const uint32_t *__restrict__ w, uint64_t nw,
+                                                  const DecTrack *__restrict__ tr,
+                                                  const OggStream *__restrict__ streams,
+                                                  const OggHdr *__restrict__ hdr, uint32_t npk,
+                                                  const uint64_t *__restrict__ pk_pos,
+                                                  const uint32_t *__restrict__ pk_len,
+                                                  const uint32_t *__restrict__ pk_trk,
+                                                  ParseRec *__restrict__ recs)
+{
+    __shared__ __align__(16) uint32_t ring[64 * kRingStride];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npk; i += gridDim.x * blockDim.x) {
+        const uint32_t ti = pk_trk[i];
+        const OggHdr h = hdr[ti];
+        const uint64_t k = (uint64_t)i - streams[ti].pkt_base;
+        ParseRec rec;
+        if (h.status != ATG_OGG_OK || k < h.first_audio) { // a header packet: never parsed
+            rec.status = FD_ERROR;
+            rec.bs = rec.bytes = 0;
+            rec.assign = rec.ch = rec.bps = rec.pad = 0;
+            for (int c = 0; c < 8; ++c)
+                rec.sub_bit[c] = 0;
+        } else {
+            DecTrack t = tr[ti];
+            t.end = pk_pos[i] + pk_len[i];
+            parse_frame<true, false>(w, nw, pk_pos[i], t, ~0ull, nullptr, rec,
+                                     ring + threadIdx.x * kRingStride, 0u);
+            if (rec.status == FD_ERROR)
+                rec.status = loose_frame(w, nw, pk_pos[i], t);
+        }
+        recs[i] = rec;
+    }
+}
+
+// the read loop per stream over its audio packets (oggflac.c:471-559); pass 1
+// counts, pass 2 writes frames and subframe jobs
+__global__ __launch_bounds__(64) void k_ogg_chain(const DecTrack *__restrict__ tr, uint32_t nt,
+                                                  const OggStream *__restrict__ streams,
+                                                  const OggHdr *__restrict__ hdr,
+                                                  const uint64_t *__restrict__ pk_pos,
+                                                  const ParseRec *__restrict__ recs,
+                                                  DecCount *__restrict__ counts, int pass,
+                                                  DecFrame *__restrict__ frames,
+                                                  uint2 *__restrict__ jobs)
+{
+    const uint32_t ti = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ti >= nt)
+        return;
+    const DecTrack t = tr[ti];
+    const OggHdr h = hdr[ti];
+    const uint64_t p0 = streams[ti].pkt_base + h.first_audio;
+    uint64_t pcm = 0, stop = t.end;
+    uint32_t nf = 0;
+    int status = FD_OK;
+    for (uint32_t k = 0; k < h.n_audio; ++k) {
+        const ParseRec rec = recs[p0 + k];
+        const uint64_t pos = pk_pos[p0 + k];
+        if (rec.status) { // (a bad CRC-16 too: this stream has no offsets() view)
+            status = rec.status;
+            stop = pos;
+            break;
+        }
+        if (pass == 2) {
+            const uint64_t slot = t.frame_base + nf;
+            DecFrame f;
+            f.pos = pos;
+            f.pcm_start = t.pcm_base + pcm * t.channels;
+            f.n = rec.bs; // no block is truncated: total_samples is never consulted
+            f.track = ti;
+            f.bs = rec.bs;
+            f.assign = rec.assign;
+            f.ch = rec.ch;
+            f.bps = rec.bps;
+            f.spec = 0;
+            f.bytes = rec.bytes;
+            f.pad = 0;
+            for (int c = 0; c < 8; ++c)
+                f.sub_bit[c] = rec.sub_bit[c];
+            frames[slot] = f;
+            for (uint32_t c = 0; c < rec.ch; ++c)
+                jobs[t.job_base + (uint64_t)nf * rec.ch + c] = make_uint2((uint32_t)slot, c);
+        }
+        ++nf;
+        pcm += rec.bs;
+    }
+    if (pass == 1) {
+        DecCount dc;
+        dc.pcm_frames = pcm;
+        dc.n_frames = nf;
+        dc.status = status;
+        dc.crc_pcm = 0;
+        dc.crc_frame = 0xFFFFFFFFu;
+        dc.pad = 0;
+        dc.stop = stop - t.start;
+        counts[ti] = dc;
+    }
+}
+
 const int kDecTimed = 7;
+const int kOggTimed = 3;
+const char *kOggNames[kOggTimed] = {"ogg_walk", "ogg_crc", "ogg_gather"};
 const char *kDecNames[kDecTimed] = {"dec_scan",     "dec_parse", "dec_chain", "dec_subframe",
                                     "dec_emit",     "dec_md5",   "dec_total"};
 
@@ -1788,6 +2066,18 @@ struct atg_decoder {
     std::vector<DecSlot *> roll_q;  // rolled batches with slices to run, oldest first
     uint64_t next_ticket = 1;
     int last = -1; // slot of the last waited batch (decode_fetch)
+    // Ogg FLAC (atg_oggflac_decode_*): the container pass's tables, the
+    // compacted streams, its phase events and host copies
+    DevBuf og_streams, og_walk, og_pages, og_acc, og_sum, og_pos, og_len, og_trk, og_hdr, og_out;
+    hipEvent_t og_ev[kOggTimed + 1] = {};
+    float og_times[kOggTimed] = {};
+    bool og_ready = false; // tables uploaded, events created
+    bool last_ogg = false; // the last waited batch came through the Ogg entries
+    uint32_t og_npk = 0;   // packets of the batch (upload source)
+    std::vector<OggStream> og_st;
+    std::vector<OggWalk> og_wk;
+    std::vector<OggSum> og_sm;
+    std::vector<OggHdr> og_hd;
 };
 
 static void build_dec_adv(const uint16_t t16[4][256], uint16_t adv[24][16])
@@ -2001,8 +2291,13 @@ void atg_decoder_destroy(atg_decoder *d)
     (void)hipSetDevice(d->device);
     (void)hipStreamSynchronize(d->s);
     for (DevBuf *b : {&d->data, &d->tracks, &d->counts, &d->ncand, &d->cand_pos, &d->cand_idx,
-                    &d->recs, &d->hits, &d->segs, &d->cbits, &d->spec, &d->cand_trk})
+                    &d->recs, &d->hits, &d->segs, &d->cbits, &d->spec, &d->cand_trk,
+                    &d->og_streams, &d->og_walk, &d->og_pages, &d->og_acc, &d->og_sum,
+                    &d->og_pos, &d->og_len, &d->og_trk, &d->og_hdr, &d->og_out})
         b->release();
+    for (auto &e : d->og_ev)
+        if (e)
+            (void)hipEventDestroy(e);
     if (d->s_roll)
         (void)hipStreamSynchronize(d->s_roll);
     for (DecSlot &sl : d->slot) {
@@ -2116,6 +2411,15 @@ static atg_status dec_roll_step(atg_decoder *d, hipEvent_t after)
     }
     return ATG_OK;
 }
+
+// The back half of a batch whose frame walk has counted (sl.tr, sl.cnt): the
+// host prefix over tracks, the walk's second pass (`chain2`, on the decoder
+// stream, which writes the frame table and the subframe jobs), then restore
+// -> emit -> per-track MD5 on the slot's stream.  `w` is the buffer the
+// frames lie in.
+template <class F>
+static atg_status enqueue_restore(atg_decoder *d, DecSlot &sl, const uint32_t *w, uint64_t nw,
+                                  uint32_t n, F chain2);
 
 // Enqueue the device-resident decode of a batch on slot `sl`: scan ->
 // parse -> chain (two host round trips for the counts) on the decoder
@@ -2274,6 +2578,23 @@ static atg_status enqueue_decode(atg_decoder *d, DecSlot &sl, const uint8_t *d_d
     DHIP(hipMemcpyAsync(sl.cnt.data(), d->counts.p, sizeof(DecCount) * n, hipMemcpyDeviceToHost,
                         s));
     DHIP(hipStreamSynchronize(s));
+    return enqueue_restore(d, sl, w, nw, n, [&](const DecTrack *str) {
+        if (n)
+            hipLaunchKernelGGL(k_dec_chain, tg, dim3(64), 0, s, w, nw, str, n,
+                               (const uint32_t *)d->ncand.p, (const uint64_t *)d->cand_pos.p,
+                               (const uint32_t *)d->cand_idx.p, (const ParseRec *)d->recs.p,
+                               (DecCount *)d->counts.p, 2, (DecFrame *)sl.frames.p,
+                               (uint2 *)sl.jobs.p);
+    });
+}
+
+template <class F>
+static atg_status enqueue_restore(atg_decoder *d, DecSlot &sl, const uint32_t *w, uint64_t nw,
+                                  uint32_t n, F chain2)
+{
+    hipStream_t s = d->s;
+    std::vector<DecTrack> &tr = sl.tr;
+    hipEvent_t *ev = sl.ev;
     // host prefix over tracks: frame slots, PCM placement, MD5 byte streams
     uint64_t fb = 0, pb = 0, mb = 0, jb = 0;
     for (uint32_t t = 0; t < n; ++t) {
@@ -2312,12 +2633,7 @@ static atg_status enqueue_decode(atg_decoder *d, DecSlot &sl, const uint8_t *d_d
     DHIP(sl.tracks.ensure(sizeof(DecTrack) * std::max<uint32_t>(n, 1)));
     DecTrack *str = (DecTrack *)sl.tracks.p;
     DHIP(hipMemcpyAsync(str, tr.data(), sizeof(DecTrack) * n, hipMemcpyHostToDevice, s));
-    if (n)
-        hipLaunchKernelGGL(k_dec_chain, tg, dim3(64), 0, s, w, nw, (const DecTrack *)str, n,
-                           (const uint32_t *)d->ncand.p, (const uint64_t *)d->cand_pos.p,
-                           (const uint32_t *)d->cand_idx.p, (const ParseRec *)d->recs.p,
-                           (DecCount *)d->counts.p, 2, (DecFrame *)sl.frames.p,
-                           (uint2 *)sl.jobs.p);
+    chain2((const DecTrack *)str);
     DHIP(hipGetLastError());
     DHIP(hipEventRecord(sl.ev_chain, s));
     // the restore / emit stream: the slot's own, or in rolled mode the
@@ -2530,6 +2846,7 @@ atg_status atg_flac_decode_wait(atg_decoder *d, uint64_t ticket, atg_flac_dec_re
     atg_status st = finish_decode(d, *sl, results);
     if (st != ATG_OK)
         return st;
+    d->last_ogg = false;
     if (d_pcm)
         *d_pcm = (const int32_t *)sl->pcm.p;
     if (total_samples)
@@ -2670,14 +2987,478 @@ int atg_decoder_kernel_times(atg_decoder *d, const char **names, float *ms, int 
     ATG_HANDLE_LOCK(d);
     if (!d || !d->have_times)
         return 0;
-    const int n = cap < kDecTimed ? cap : kDecTimed;
+    int n = cap < kDecTimed ? cap : kDecTimed;
     for (int k = 0; k < n; ++k) {
         if (names)
             names[k] = kDecNames[k];
         if (ms)
             ms[k] = d->times[k];
     }
+    // an Ogg FLAC batch: the container pass's phases follow
+    for (int k = 0; d->last_ogg && k < kOggTimed && n < cap; ++k, ++n) {
+        if (names)
+            names[n] = kOggNames[k];
+        if (ms)
+            ms[n] = d->og_times[k];
+    }
     return n;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- Ogg FLAC
+//
+// Host side of the Ogg FLAC entries: the container pass of ogg_demux.hip
+// (walk -> page CRC-32 -> summary -> packet table + gather; two host round
+// trips, for the page and the packet counts), then the frame decode from the
+// packet table: k_ogg_tracks reads every stream's STREAMINFO on the device,
+// k_ogg_parse and the native k_dec_crc give a record per packet, k_ogg_chain
+// walks them (the third round trip), and enqueue_restore runs the native
+// restore, emit and MD5 over the compacted streams.
+
+// the host's page reader (src/ogg.c:24-119) over an image; same checks and
+// order as k_ogg_walk and k_ogg_crc
+namespace {
+
+struct HostPage {
+    int status;
+    uint32_t nseg, flags, serial;
+    const uint8_t *lacing, *body;
+    uint64_t size;
+};
+
+uint32_t host_ogg_crc(uint32_t crc, const uint8_t *p, uint64_t n, uint64_t zero_from,
+                      uint64_t zero_to)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        crc ^= (uint32_t)(i >= zero_from && i < zero_to ? 0u : p[i]) << 24;
+        for (int k = 0; k < 8; ++k)
+            crc = (crc & 0x80000000u) ? (crc << 1) ^ 0x04C11DB7u : crc << 1;
+    }
+    return crc;
+}
+
+HostPage host_read_page(const uint8_t *d, uint64_t len, uint64_t pos)
+{
+    HostPage p = {};
+    const uint64_t rem = len - pos;
+    const uint8_t *q = d + pos;
+    p.status = ATG_OGG_PREMATURE_EOF;
+    if (rem < 4)
+        return p;
+    if (std::memcmp(q, "OggS", 4) != 0) {
+        p.status = ATG_OGG_MAGIC;
+        return p;
+    }
+    if (rem < 5)
+        return p;
+    if (q[4] != 0) {
+        p.status = ATG_OGG_VERSION;
+        return p;
+    }
+    if (rem < 27)
+        return p;
+    p.flags = q[5];
+    p.serial = (uint32_t)q[14] | ((uint32_t)q[15] << 8) | ((uint32_t)q[16] << 16) |
+               ((uint32_t)q[17] << 24);
+    p.nseg = q[26];
+    if (rem < 27ull + p.nseg)
+        return p;
+    p.lacing = q + 27;
+    uint64_t body = 0;
+    for (uint32_t i = 0; i < p.nseg; ++i)
+        body += p.lacing[i];
+    p.size = 27ull + p.nseg + body;
+    if (rem < p.size)
+        return p;
+    p.body = q + 27 + p.nseg;
+    const uint32_t stored = (uint32_t)q[22] | ((uint32_t)q[23] << 8) | ((uint32_t)q[24] << 16) |
+                            ((uint32_t)q[25] << 24);
+    p.status = host_ogg_crc(0, q, p.size, 22, 26) == stored ? ATG_OGG_OK : ATG_OGG_CHECKSUM;
+    return p;
+}
+
+// the packet iterator (ogg.c:203-254)
+struct HostPackets {
+    const uint8_t *d;
+    uint64_t len, pos = 0;
+    HostPage page = {};
+    uint32_t seg = 0;
+    uint64_t body_at = 0;
+    bool have = false, ended = false;
+    uint32_t first_serial = 0;
+    bool any = false;
+    // -> ATG_OGG_OK with the packet in out, or what stopped it
+    int next(std::vector<uint8_t> &out)
+    {
+        out.clear();
+        for (;;) {
+            if (!have || seg >= page.nseg) {
+                if (ended)
+                    return ATG_OGG_STREAM_FINISHED;
+                page = host_read_page(d, len, pos);
+                if (page.status != ATG_OGG_OK)
+                    return page.status;
+                if (!any)
+                    first_serial = page.serial;
+                any = true;
+                pos += page.size;
+                ended = (page.flags & 4u) != 0;
+                have = true;
+                seg = 0;
+                body_at = 0;
+                continue;
+            }
+            const uint32_t v = page.lacing[seg++];
+            out.insert(out.end(), page.body + body_at, page.body + body_at + v);
+            body_at += v;
+            if (v < 255)
+                return ATG_OGG_OK;
+        }
+    }
+};
+
+} // namespace
+
+#define OGG_LIMIT(cond, text)                                                                 \
+    do {                                                                                      \
+        if (cond)                                                                             \
+            return g_dec_err.fail(ATG_ERR_UNSUPPORTED, text);                                 \
+    } while (0)
+
+static atg_status enqueue_ogg_decode(atg_decoder *d, DecSlot &sl, const uint8_t *d_data,
+                                     uint64_t len, const atg_oggflac_dec_track *tracks, uint32_t n)
+{
+    hipStream_t s = d->s;
+    OGG_LIMIT(len > ATG_OGG_MAX_BATCH_BYTES, "Ogg FLAC batch larger than ATG_OGG_MAX_BATCH_BYTES");
+    std::vector<OggStream> &st = d->og_st;
+    st.assign(n, OggStream());
+    for (uint32_t t = 0; t < n; ++t) {
+        const atg_oggflac_dec_track &a = tracks[t];
+        OGG_LIMIT(a.data_bytes > ATG_OGG_MAX_IMAGE_BYTES,
+                  "Ogg FLAC image larger than ATG_OGG_MAX_IMAGE_BYTES");
+        if (a.data_offset > len || a.data_bytes > len - a.data_offset)
+            return g_dec_err.fail(ATG_ERR_INVALID, "track data range outside the buffer");
+        st[t].start = a.data_offset;
+        st[t].end = a.data_offset + a.data_bytes;
+    }
+    if (!d->og_ready) {
+        DHIP(ogg_upload_tables());
+        for (auto &e : d->og_ev)
+            if (!e)
+                DHIP(hipEventCreate(&e));
+        d->og_ready = true;
+    }
+    const uint32_t n1 = std::max<uint32_t>(n, 1);
+    const uint64_t nw = std::max<uint64_t>(1, (len + 3) / 4);
+    const uint32_t *w = (const uint32_t *)d_data;
+    DHIP(d->og_streams.ensure(sizeof(OggStream) * n1));
+    DHIP(d->og_walk.ensure(sizeof(OggWalk) * n1));
+    DHIP(d->og_sum.ensure(sizeof(OggSum) * n1));
+    DHIP(d->og_hdr.ensure(sizeof(OggHdr) * n1));
+    OggStream *dst = (OggStream *)d->og_streams.p;
+    // 1: the page walk counts
+    DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
+    DHIP(hipEventRecord(d->og_ev[0], s));
+    DHIP(launch_ogg_walk(d_data, dst, n, 1, (OggWalk *)d->og_walk.p, nullptr, s));
+    d->og_wk.assign(n, OggWalk());
+    DHIP(hipMemcpyAsync(d->og_wk.data(), d->og_walk.p, sizeof(OggWalk) * n, hipMemcpyDeviceToHost,
+                        s));
+    DHIP(hipStreamSynchronize(s));
+    uint64_t npages = 0, nchunks = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        st[t].page_base = npages;
+        st[t].chunk_base = nchunks;
+        npages += d->og_wk[t].pages;
+        nchunks += d->og_wk[t].chunks;
+    }
+    // 2: the page records, their checksums, what is delivered
+    DHIP(d->og_pages.ensure(sizeof(OggPage) * std::max<uint64_t>(npages, 1)));
+    DHIP(d->og_acc.ensure(sizeof(uint32_t) * std::max<uint64_t>(npages, 1)));
+    DHIP(hipMemsetAsync(d->og_acc.p, 0, sizeof(uint32_t) * std::max<uint64_t>(npages, 1), s));
+    DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
+    const OggPage *pages = (const OggPage *)d->og_pages.p;
+    DHIP(launch_ogg_walk(d_data, dst, n, 2, (OggWalk *)d->og_walk.p, (OggPage *)d->og_pages.p, s));
+    DHIP(hipEventRecord(d->og_ev[1], s));
+    DHIP(launch_ogg_crc(w, nw, pages, npages, nchunks, (uint32_t *)d->og_acc.p, s));
+    DHIP(launch_ogg_summary(dst, n, (const OggWalk *)d->og_walk.p, pages,
+                            (const uint32_t *)d->og_acc.p, (OggSum *)d->og_sum.p, s));
+    d->og_sm.assign(n, OggSum());
+    DHIP(hipMemcpyAsync(d->og_sm.data(), d->og_sum.p, sizeof(OggSum) * n, hipMemcpyDeviceToHost,
+                        s));
+    DHIP(hipStreamSynchronize(s));
+    uint64_t npk = 0, out_bytes = 0, max_out = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        st[t].pkt_base = npk;
+        st[t].out_base = out_bytes;
+        npk += d->og_sm[t].packets;
+        const uint64_t slot = (d->og_sm[t].bytes + 15u) & ~15ull;
+        out_bytes += slot;
+        max_out = std::max(max_out, slot);
+    }
+    OGG_LIMIT(npk > 0xFFFFFFF0ull, "Ogg FLAC batch with more than 2^32 packets");
+    // 3: the packet table and the compacted streams (zero slack after the
+    // last: the bit reader's window loads are clamped to the buffer)
+    const uint64_t out_cap = out_bytes + 256;
+    DHIP(d->og_pos.ensure(sizeof(uint64_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og_len.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og_trk.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og_out.ensure(out_cap));
+    DHIP(hipMemsetAsync((uint8_t *)d->og_out.p + out_bytes, 0, 256, s));
+    DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
+    DHIP(hipEventRecord(d->og_ev[2], s));
+    DHIP(launch_ogg_packets(d_data, dst, (const OggSum *)d->og_sum.p, pages, npages,
+                            (uint64_t *)d->og_pos.p, (uint32_t *)d->og_len.p,
+                            (uint32_t *)d->og_trk.p, s));
+    DHIP(launch_ogg_gather(w, nw, dst, (const OggSum *)d->og_sum.p, pages, n, max_out,
+                           (uint32_t *)d->og_out.p, s));
+    DHIP(hipEventRecord(d->og_ev[3], s));
+    // the frame decode over the compacted streams
+    const uint32_t *cw = (const uint32_t *)d->og_out.p;
+    const uint64_t cnw = out_cap / 4;
+    DHIP(d->tracks.ensure(sizeof(DecTrack) * n1));
+    DHIP(d->counts.ensure(sizeof(DecCount) * n1));
+    DHIP(d->ncand.ensure(2 * sizeof(uint32_t)));
+    DHIP(d->recs.ensure(sizeof(ParseRec) * std::max<uint64_t>(npk, 1)));
+    d->og_npk = (uint32_t)npk;
+    DHIP(hipMemcpyAsync(d->ncand.p, &d->og_npk, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    DecTrack *dtr = (DecTrack *)d->tracks.p;
+    const OggHdr *dh = (const OggHdr *)d->og_hdr.p;
+    const uint64_t *pos = (const uint64_t *)d->og_pos.p;
+    hipEvent_t *ev = sl.ev;
+    const dim3 tg((n + 63) / 64);
+    DHIP(hipEventRecord(ev[0], s));
+    if (n)
+        hipLaunchKernelGGL(k_ogg_tracks, tg, dim3(64), 0, s, cw, (const OggStream *)dst,
+                           (const OggSum *)d->og_sum.p, n, pos, (const uint32_t *)d->og_len.p,
+                           dtr, (OggHdr *)d->og_hdr.p);
+    DHIP(hipGetLastError());
+    DHIP(hipEventRecord(ev[1], s));
+    if (npk) {
+        hipLaunchKernelGGL(k_ogg_parse, dim3((unsigned)std::min<uint64_t>((npk + 63) / 64, 4096)),
+                           dim3(64), 0, s, cw, cnw, (const DecTrack *)dtr, (const OggStream *)dst,
+                           dh, (uint32_t)npk, pos, (const uint32_t *)d->og_len.p,
+                           (const uint32_t *)d->og_trk.p, (ParseRec *)d->recs.p);
+        DHIP(hipGetLastError());
+        hipLaunchKernelGGL(k_dec_crc, dim3((unsigned)std::min<uint64_t>((npk + 3) / 4, 8192)),
+                           dim3(256), 0, s, cw, cnw, (const uint32_t *)d->ncand.p, pos,
+                           (ParseRec *)d->recs.p);
+    }
+    DHIP(hipGetLastError());
+    DHIP(hipEventRecord(ev[2], s));
+    if (n)
+        hipLaunchKernelGGL(k_ogg_chain, tg, dim3(64), 0, s, (const DecTrack *)dtr, n,
+                           (const OggStream *)dst, dh, pos, (const ParseRec *)d->recs.p,
+                           (DecCount *)d->counts.p, 1, (DecFrame *)nullptr, (uint2 *)nullptr);
+    DHIP(hipGetLastError());
+    sl.cnt.assign(n, DecCount());
+    sl.tr.assign(n, DecTrack());
+    d->og_hd.assign(n, OggHdr());
+    DHIP(hipMemcpyAsync(sl.cnt.data(), d->counts.p, sizeof(DecCount) * n, hipMemcpyDeviceToHost,
+                        s));
+    DHIP(hipMemcpyAsync(sl.tr.data(), dtr, sizeof(DecTrack) * n, hipMemcpyDeviceToHost, s));
+    DHIP(hipMemcpyAsync(d->og_hd.data(), d->og_hdr.p, sizeof(OggHdr) * n, hipMemcpyDeviceToHost,
+                        s));
+    DHIP(hipStreamSynchronize(s));
+    sl.want.assign(n, atg_flac_dec_track());
+    for (uint32_t t = 0; t < n; ++t)
+        std::memcpy(sl.want[t].md5, d->og_hd[t].md5, 16);
+    sl.data = d_data;
+    sl.len = len;
+    sl.spec = false;
+    return enqueue_restore(d, sl, cw, cnw, n, [&](const DecTrack *str) {
+        if (n)
+            hipLaunchKernelGGL(k_ogg_chain, tg, dim3(64), 0, s, str, n, (const OggStream *)dst, dh,
+                               pos, (const ParseRec *)d->recs.p, (DecCount *)d->counts.p, 2,
+                               (DecFrame *)sl.frames.p, (uint2 *)sl.jobs.p);
+    });
+}
+
+extern "C" {
+
+int atg_oggflac_read_info(const uint8_t *data, uint64_t len, atg_oggflac_info *info)
+{
+    if (!info || (!data && len))
+        return ATG_OGG_PREMATURE_EOF;
+    std::memset(info, 0, sizeof(*info));
+    HostPackets it;
+    it.d = data;
+    it.len = len;
+    std::vector<uint8_t> p;
+    int rc = it.next(p);
+    info->serial_number = it.first_serial;
+    if (rc != ATG_OGG_OK)
+        return rc;
+    const size_t L = p.size();
+    // oggflac_read_streaminfo (oggflac.c:324-394): a mismatch is seen once
+    // its bytes were read
+    if (L < 1) return ATG_OGG_STREAMINFO_EOF;
+    if (p[0] != 0x7F) return ATG_OGG_PACKET_BYTE;
+    if (L < 5) return ATG_OGG_STREAMINFO_EOF;
+    if (std::memcmp(&p[1], "FLAC", 4) != 0) return ATG_OGG_SIGNATURE;
+    if (L < 6) return ATG_OGG_STREAMINFO_EOF;
+    if (p[5] != 1) return ATG_OGG_MAJOR_VERSION;
+    if (L < 7) return ATG_OGG_STREAMINFO_EOF;
+    if (p[6] != 0) return ATG_OGG_MINOR_VERSION;
+    if (L < 9) return ATG_OGG_STREAMINFO_EOF;
+    info->header_packets = ((uint32_t)p[7] << 8) | p[8];
+    if (L < 13) return ATG_OGG_STREAMINFO_EOF;
+    if (std::memcmp(&p[9], "fLaC", 4) != 0) return ATG_OGG_FLAC_SIGNATURE;
+    if (L < 14) return ATG_OGG_STREAMINFO_EOF;
+    if (p[13] & 0x7F) return ATG_OGG_BLOCK_TYPE;
+    if (L < 51) return ATG_OGG_STREAMINFO_EOF;
+    atg_flac_streaminfo &si = info->si;
+    const uint8_t *q = &p[17];
+    si.min_block_size = ((uint32_t)q[0] << 8) | q[1];
+    si.max_block_size = ((uint32_t)q[2] << 8) | q[3];
+    si.min_frame_size = ((uint32_t)q[4] << 16) | ((uint32_t)q[5] << 8) | q[6];
+    si.max_frame_size = ((uint32_t)q[7] << 16) | ((uint32_t)q[8] << 8) | q[9];
+    si.sample_rate = ((uint32_t)q[10] << 12) | ((uint32_t)q[11] << 4) | (q[12] >> 4);
+    si.channels = ((q[12] >> 1) & 7u) + 1u;
+    si.bits_per_sample = (((uint32_t)(q[12] & 1u) << 4) | (q[13] >> 4)) + 1u;
+    si.total_samples = ((uint64_t)(q[13] & 15u) << 32) | ((uint64_t)q[14] << 24) |
+                       ((uint64_t)q[15] << 16) | ((uint64_t)q[16] << 8) | q[17];
+    std::memcpy(si.md5, q + 18, 16);
+    si.channel_mask = si.channels <= 8 ? kMasks[si.channels] : 0;
+    si.frames_offset = it.pos;
+    // the header packets: a VORBIS_COMMENT's channel mask (flac.c:508-566);
+    // a stream that ends among them is the decoder's to report
+    std::vector<uint8_t> fake;
+    for (uint32_t k = 0; k < info->header_packets; ++k) {
+        if (it.next(p) != ATG_OGG_OK)
+            break;
+        if (p.size() >= 4 && (p[0] & 0x7F) == 4) {
+            // the block as a one-block FLAC image for atg_flac_read_metadata's reader
+            fake.assign({'f', 'L', 'a', 'C', 0, 0, 0, 34});
+            fake.resize(8 + 34, 0);
+            fake[8 + 12] = (uint8_t)(((si.channels - 1u) & 7u) << 1);
+            fake.insert(fake.end(), p.begin(), p.end());
+            fake[8 + 34] |= 0x80;
+            atg_flac_streaminfo tmp;
+            if (atg_flac_read_metadata(fake.data(), fake.size(), &tmp, nullptr, 0) == 0 &&
+                tmp.channel_mask != (si.channels <= 8 ? kMasks[si.channels] : 0)) {
+                si.channel_mask = tmp.channel_mask;
+                info->has_channel_mask = 1;
+            }
+        }
+    }
+    return ATG_OGG_OK;
+}
+
+atg_status atg_oggflac_decode_device(atg_decoder *d, const void *d_data, uint64_t len,
+                                     const atg_oggflac_dec_track *tracks, uint32_t n,
+                                     atg_oggflac_dec_result *results, const int32_t **d_pcm,
+                                     uint64_t *total_samples)
+{
+    ATG_HANDLE_LOCK(d);
+    if (!d || (!tracks && n) || (!results && n) || (!d_data && len))
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
+    if (((uintptr_t)d_data) & 3)
+        return g_dec_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
+    for (DecSlot &sl : d->slot)
+        if (sl.busy)
+            return g_dec_err.fail(ATG_ERR_INVALID,
+                                  "a device decode is in flight: wait for it first");
+    DHIP(hipSetDevice(d->device));
+    DecSlot *sl = nullptr;
+    atg_status st = take_dec_slot(d, &sl);
+    if (st != ATG_OK)
+        return st;
+    st = enqueue_ogg_decode(d, *sl, (const uint8_t *)d_data, len, tracks, n);
+    if (st != ATG_OK) {
+        dec_abort(d, *sl);
+        return st;
+    }
+    sl->busy = true;
+    std::vector<atg_flac_dec_result> fr(std::max<uint32_t>(n, 1));
+    st = finish_decode(d, *sl, fr.data());
+    if (st != ATG_OK) {
+        dec_abort(d, *sl);
+        return st;
+    }
+    for (int k = 0; k < kOggTimed; ++k)
+        if (hipEventElapsedTime(&d->og_times[k], d->og_ev[k], d->og_ev[k + 1]) != hipSuccess)
+            d->og_times[k] = 0.f;
+    d->last_ogg = true;
+    for (uint32_t t = 0; t < n; ++t) {
+        atg_oggflac_dec_result &r = results[t];
+        const OggSum &sm = d->og_sm[t];
+        const OggHdr &h = d->og_hd[t];
+        std::memset(&r, 0, sizeof(r));
+        r.pcm_offset = fr[t].pcm_offset;
+        r.sample_offset = sl->tr[t].pcm_base;
+        r.pcm_frames = fr[t].pcm_frames;
+        r.n_frames = fr[t].n_frames;
+        std::memcpy(r.md5, fr[t].md5, 16);
+        r.header_packets = h.header_packets;
+        r.pages = sm.pages;
+        r.packets = sm.packets;
+        r.fail_page = sm.fail_page;
+        r.fail_offset = sm.fail_off;
+        // the first failure in stream order: a frame's, else the
+        // container's (the first packet's included), else the MD5's
+        r.status = fr[t].status;
+        r.ogg_status = h.status;
+        if (h.status == ATG_OGG_OK && (r.status == FD_OK || r.status == FD_MD5) &&
+            sm.status != ATG_OGG_OK) {
+            r.status = FD_OK;
+            r.ogg_status = sm.status;
+        }
+        if (h.status != ATG_OGG_OK)
+            r.status = FD_OK;
+        if (h.pad) {
+            r.sample_rate = sl->tr[t].rate;
+            r.channels = sl->tr[t].channels;
+            r.bits_per_sample = sl->tr[t].bps;
+            r.max_block_size = sl->tr[t].max_bs;
+            r.total_samples = h.total;
+            std::memcpy(r.streaminfo_md5, h.md5, 16);
+        }
+    }
+    if (d_pcm)
+        *d_pcm = (const int32_t *)sl->pcm.p;
+    if (total_samples)
+        *total_samples = sl->total_samples;
+    return ATG_OK;
+}
+
+atg_status atg_oggflac_decode_host(atg_decoder *d, const uint8_t *data, uint64_t len,
+                                   const atg_oggflac_dec_track *tracks, uint32_t n,
+                                   atg_oggflac_dec_result *results, uint64_t *total_samples,
+                                   uint64_t *total_frames)
+{
+    ATG_HANDLE_LOCK(d);
+    if (!d || (!tracks && n) || (!results && n) || (!data && len))
+        return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
+    if (len > ATG_OGG_MAX_BATCH_BYTES)
+        return g_dec_err.fail(ATG_ERR_UNSUPPORTED,
+                              "Ogg FLAC batch larger than ATG_OGG_MAX_BATCH_BYTES");
+    DHIP(hipSetDevice(d->device));
+    for (DecSlot &sl : d->slot)
+        if (sl.busy)
+            return g_dec_err.fail(ATG_ERR_INVALID,
+                                  "a device decode is in flight: wait for it first");
+    DHIP(d->data.ensure(len + 64));
+    DHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
+    if (len)
+        DHIP(hipMemcpyAsync(d->data.p, data, len, hipMemcpyHostToDevice, d->s));
+    uint64_t ts = 0;
+    const atg_status st = atg_oggflac_decode_device(d, d->data.p, len, tracks, n, results, nullptr,
+                                                    &ts);
+    if (st != ATG_OK)
+        return st;
+    if (total_samples)
+        *total_samples = ts;
+    if (total_frames)
+        *total_frames = d->slot[d->last].total_frames;
+    return ATG_OK;
+}
+
+atg_status atg_oggflac_decode_fetch(atg_decoder *d, int32_t *pcm, uint64_t pcm_cap,
+                                    uint64_t *frame_offsets, uint32_t *frame_block_sizes,
+                                    uint64_t frame_cap)
+{
+    return atg_flac_decode_fetch(d, pcm, pcm_cap, frame_offsets, frame_block_sizes, frame_cap);
 }
 
 } // extern "C"
