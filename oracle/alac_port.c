@@ -626,14 +626,19 @@ static int seektable(const uint8_t *d, uint64_t m0, uint64_t m1, uint32_t total,
         for (uint32_t j = first; last ? left > 0 : j < next_first; j++) {
             if (left < per)
                 return ALACPORT_INVALID_SEEKTABLE;
+            /* the chunk's frames a run of equal durations at a time, and no
+               further than one chunk past stco's count (the answer is then
+               settled): a damaged count costs no more than the tables' size */
             uint64_t chunk = 0;
-            for (uint32_t k = 0; k < per; k++) {
+            for (uint32_t need = per; need;) {
                 while (tleft == 0) {
                     ti++;
                     tleft = be32(d + t0 + 8 + 8 * ti);
                 }
-                chunk += be32(d + t0 + 12 + 8 * ti);
-                tleft--;
+                const uint32_t take = need < tleft ? need : tleft;
+                chunk += (uint64_t)take * be32(d + t0 + 12 + 8 * ti);
+                tleft -= take;
+                need -= take;
             }
             left -= per;
             if (nchunks < no && nchunks < sp_cap) {
@@ -642,6 +647,8 @@ static int seektable(const uint8_t *d, uint64_t m0, uint64_t m1, uint32_t total,
             }
             pcm += (uint32_t)chunk;
             nchunks++;
+            if (nchunks > no)
+                return ALACPORT_INVALID_SEEKTABLE;
         }
     }
     if (nchunks != no)
@@ -845,6 +852,13 @@ static void wave_order(unsigned n, unsigned *map)
         map[c] = n <= 8 ? M[n][c] : c;
 }
 
+static uint64_t short_blocks;
+
+uint64_t alacport_short_blocks(void)
+{
+    return short_blocks;
+}
+
 int alacport_decode(const uint8_t *d, size_t len, const alacport_info *in, uint64_t start,
                     uint64_t remaining, int32_t *pcm, size_t pcm_cap, uint64_t *pcm_frames,
                     uint32_t *fs_frames, uint64_t *fs_offsets, size_t fs_cap,
@@ -908,6 +922,7 @@ int alacport_decode(const uint8_t *d, size_t len, const alacport_info *in, uint6
                     const unsigned n = get_residuals(&r, res, N, ss, in);
                     if (r.eof)
                         break;
+                    short_blocks += n <= order[c];
                     const unsigned outn = order[c] > n ? order[c] : n;
                     free(chan[nchan + c]);
                     chan[nchan + c] = calloc((size_t)outn + 1, sizeof(int32_t));

@@ -77,6 +77,14 @@ int alacport_decode(const uint8_t *data, size_t len, const alacport_info *info, 
                     uint32_t *fs_frames, uint64_t *fs_offsets, size_t fs_cap,
                     size_t *n_framesets);
 
+/* How many compressed channels alacport_decode has met, since the library
+   was loaded, whose residual block held no more values than the subframe's
+   order.  The reference's decode_subframe (alac.c:1157-1173) then still
+   writes order + 1 samples from residuals it never read, whatever its
+   buffer holds; the port keeps the residual count.  A damaged stream on
+   which this counter moves has no defined reference result. */
+uint64_t alacport_short_blocks(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,9 +134,9 @@ struct Out4 {
 };
 
 // res: where this frameset's residuals go (channel k at res + k * stride,
-// at most stride values each), or null
+// at most stride values each, res_ch channels), or null
 __device__ void parse_fs(const uint32_t *w, const ADTrack &T, uint64_t start, AFs &F,
-                         int32_t *res = nullptr, uint32_t stride = 0)
+                         int32_t *res = nullptr, uint32_t stride = 0, uint32_t res_ch = 0)
 {
     ABitRC r;
     const uint64_t b0 = start * 8;
@@ -162,6 +162,10 @@ __device__ void parse_fs(const uint32_t *w, const ADTrack &T, uint64_t start, AF
             F.status = AD_IO_ERROR;
             return;
         }
+        // a damaged frameset can carry more channels than its track (and so
+        // the slot) has: nothing more is stored, the restore decodes again
+        if (F.nch + cc > res_ch)
+            res = nullptr;
         AElem &E = F.e[F.nelem];
         E.N = N;
         E.cc = (uint8_t)cc;
@@ -300,7 +304,8 @@ __global__ __launch_bounds__(64) void k_adec_parse(const uint32_t *__restrict__ 
     const ADTrack T = tr[pred_track[i]];
     AFs F;
     int32_t *res = resid ? resid + i * res_fs : nullptr;
-    parse_fs(w, T, pred_start[i], F, res, res_stride);
+    parse_fs(w, T, pred_start[i], F, res, res_stride,
+             res ? (uint32_t)(res_fs / res_stride) : 0u);
     // every channel's residuals stored (parse_fs drops res on a channel
     // longer than the slot; a failed parse is never restored)
     if (res && F.status == AD_OK) {
@@ -902,14 +907,20 @@ int atg_alac_read_info(const uint8_t *d, uint64_t len, atg_alac_info *info,
             for (uint32_t j = first; last ? left > 0 : j < next_first; ++j) {
                 if (left < per)
                     return AD_INVALID_SEEKTABLE;
+                // the chunk's frames a run of equal durations at a time,
+                // and no further than one chunk past stco's count (the
+                // answer is then settled): a damaged count costs no more
+                // than the tables' size
                 uint64_t chunk = 0;
-                for (uint32_t k = 0; k < per; ++k) {
+                for (uint32_t need = per; need;) {
                     while (tleft == 0) {
                         ++ti;
                         tleft = be32(d + t0 + 8 + 8 * ti);
                     }
-                    chunk += be32(d + t0 + 12 + 8 * ti);
-                    --tleft;
+                    const uint32_t take = std::min(need, tleft);
+                    chunk += (uint64_t)take * be32(d + t0 + 12 + 8 * ti);
+                    tleft -= take;
+                    need -= take;
                 }
                 left -= per;
                 if (nchunks < no && sp && nchunks < sp_cap) {
@@ -918,6 +929,8 @@ int atg_alac_read_info(const uint8_t *d, uint64_t len, atg_alac_info *info,
                 }
                 pcm += (uint32_t)chunk;
                 ++nchunks;
+                if (nchunks > no)
+                    return AD_INVALID_SEEKTABLE;
             }
         }
         if (nchunks != no)

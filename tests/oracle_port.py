@@ -494,8 +494,17 @@ def _alac_lib():
                                         ctypes.POINTER(AlacInfo), c_u64, c_u64, P,
                                         ctypes.c_size_t, ctypes.POINTER(c_u64), P, P,
                                         ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        lib.alacport_short_blocks.restype = c_u64
+        lib.alacport_short_blocks.argtypes = []
         lib._alac_ready = True
     return lib
+
+
+def alac_short_blocks():
+    """the running count of compressed channels alac_decode has met whose
+    residual block was no longer than the subframe's order (the reference
+    then returns samples made of residuals it never read)"""
+    return int(_alac_lib().alacport_short_blocks())
 
 
 def alac_encode(pcm, channels, bps, **opts):

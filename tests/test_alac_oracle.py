@@ -119,3 +119,47 @@ def test_port_matches_reference_live():
         x = signals.make(kind, 3 * bs + 17, ch, bps, seed=ch)
         assert op.alac_encode(x, ch, bps, block_size=bs)[0] == \
             op.ref_alac_encode(x, ch, bps, block_size=bs)
+
+
+@pytest.mark.parametrize("name", sorted(alac_cases.DAMAGE_IMAGES))
+def test_damage_record(name):
+    """oracle/alac_port.c against the reference decoder's recorded outcome
+    (tests/golden/make_alac_damage_golden.py) on every single-bit flip of
+    the mdat atom, every truncation and every header flip that changes what
+    the reference returns, with the mapping of test_decoder_vectors: a
+    header the port refuses is return code 1 and no bytes, otherwise the
+    same success class and PCM bytes.
+
+    Set aside are the cases on which the reference dies, and those on which
+    a compressed channel's residual block is no longer than its subframe's
+    order (max_samples_per_frame flipped to 0 is one): the reference's
+    decode_subframe (alac.c:1157-1173) then returns order + 1 samples made
+    of residuals it never read, so what it writes depends on what its buffer
+    held.  The port, and the GPU with it, return the residual count's
+    samples there and are held to each other, not to the reference."""
+    rec = alac_cases.damage_load(name)
+    img, start, x = alac_cases.damage_image(name)
+    assert hashlib.sha256(img).hexdigest() == rec["image_sha256"] and start == rec["mdat_start"]
+    n = rec["counts"]
+    assert len(rec["mdat_flips"]["rc"]) == 8 * (len(img) - start) == n["mdat_flips"]
+    assert len(rec["truncations"]) == len(img) == n["truncations"]
+    # the caps on what the comparison leaves out
+    assert 200 * len(rec["set_aside"]["reference_died"]) <= n["cases"]
+    assert 10 * n["channel_mismatch_mdat_flips"] <= n["mdat_flips"]
+    aside = set()
+    for c in alac_cases.DAMAGE_SET_ASIDE:
+        aside |= set(rec["set_aside"][c])
+    mismatch = 0
+    for kind, cases in alac_cases.damage_cases(name, rec, img).items():
+        for key, data, outcome in cases:
+            status, pcm, bps = alac_cases.port_outcome(data)
+            mismatch += kind == "mdat" and status == 10
+            if key in aside:
+                continue
+            if status == 10:  # Python-path ValueError; the standalone has no such check
+                continue
+            assert alac_cases.matches_reference(status, pcm, bps, outcome), \
+                (key, status, len(pcm), outcome)
+    assert mismatch == n["channel_mismatch_mdat_flips"]
+    status, pcm, _ = alac_cases.port_outcome(img)
+    assert status == 0 and np.array_equal(pcm, x)

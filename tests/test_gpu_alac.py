@@ -177,16 +177,16 @@ def test_decoder_vectors_batch(s, hints):
             continue
         r = res[k]
         k += 1
+        got = pcm[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels]
+        # sample for sample the CPU oracle's walk
+        want = op.alac_decode(alac_cases.mutate(img, c))
+        assert np.array_equal(got, want["pcm"]) and (want["code"] == r.status), c["name"]
         if r.status == _atgpu.AD_CHANNEL_MISMATCH:
             continue  # the Python path raises; the standalone has no check
         assert (r.status == 0) == (c["rc"] == 0), (c["name"], r.status, c["rc"])
-        got = pcm[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels]
         b = op.pcm_bytes(got, info.bits_per_sample)
         assert len(b) == c["pcm_bytes"], c["name"]
         assert hashlib.md5(b).hexdigest() == c["pcm_md5"], c["name"]
-        # and sample for sample the CPU oracle's walk
-        want = op.alac_decode(alac_cases.mutate(img, c))
-        assert np.array_equal(got, want["pcm"]) and (want["code"] == r.status), c["name"]
 
 
 def test_reference_fixture():
