@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 5
+#define ATG_ABI_VERSION 6
 
 typedef enum {
     ATG_OK = 0,
@@ -640,6 +640,80 @@ atg_status atg_oggflac_decode_device(atg_decoder *dec, const void *d_data, uint6
 atg_status atg_oggflac_decode_fetch(atg_decoder *dec, int32_t *pcm, uint64_t pcm_cap,
                                     uint64_t *frame_offsets, uint32_t *frame_block_sizes,
                                     uint64_t frame_cap);
+
+/* ------------------------------------------------------------------ */
+/* Ogg FLAC (.oga) batch encode: the FLAC frames of atg_flac_encode_*   */
+/* in an Ogg container (csrc/ogg_mux.hip).  The reference pipes PCM to  */
+/* the external `flac --ogg` program (audiotools/flac.py:3249-3367);    */
+/* the page layout here is this library's own,   */
+/* and what the reference's decoder (src/ogg.c, src/decoders/oggflac.c) */
+/* accepts.  Packets: the mapping's first packet with STREAMINFO, one   */
+/* per further metadata block (VORBIS_COMMENT, PADDING when             */
+/* padding_size > 0), one per FLAC frame.  A page closes when it holds  */
+/* page_segments lacing values, when a header packet ends on it, and    */
+/* with ATG_OGG_PAGE_PER_PACKET when any packet ends on it.             */
+/* ------------------------------------------------------------------ */
+#define ATG_OGG_PAGE_PER_PACKET 1u
+typedef struct {
+    uint32_t serial_number; /* track t gets serial_number + t (mod 2^32) */
+    uint32_t page_segments; /* 1..255; 0 = 255 */
+    uint32_t flags;         /* ATG_OGG_PAGE_PER_PACKET */
+    uint32_t channel_mask;  /* nonzero: VORBIS_COMMENT carries
+                               WAVEFORMATEXTENSIBLE_CHANNEL_MASK=0x%.4X */
+} atg_oggflac_enc_options;
+
+/* As atg_track_result (bytes = the whole .oga image at out + out_offset),
+   plus the image's pages, its header pages and its serial number. */
+typedef struct {
+    uint64_t out_offset;
+    uint64_t bytes;
+    uint32_t first_frame;
+    uint32_t n_frames;
+    uint32_t min_frame_bytes;
+    uint32_t max_frame_bytes;
+    uint8_t md5[16];
+    int32_t status;
+    uint32_t pages;
+    uint32_t header_pages;
+    uint32_t serial_number;
+} atg_oggflac_track_result;
+
+/* Frames and worst-case output bytes of a batch (host code, no HIP call):
+   an upper bound on the layout for any frame sizes up to
+   atg_flac_batch_bounds' worst case.  ATG_ERR_INVALID for page_segments >
+   255, unknown flags and whatever the FLAC options are refused for. */
+atg_status atg_oggflac_batch_bounds(const atg_flac_options *opts,
+                                    const atg_oggflac_enc_options *ogg_opts,
+                                    const atg_track *tracks, uint32_t n_tracks,
+                                    uint32_t channels, uint32_t bits_per_sample,
+                                    uint64_t *total_frames, uint64_t *out_bytes);
+
+/* Encode a batch to .oga images.  As atg_flac_encode_device / _host; the
+   device entry leaves track t's image at results[t].out_offset of d_out
+   (16-byte aligned slots sized by the bounds), the host entry packs the
+   images back to back, 16-byte aligned.  frame_page_offsets[first_frame + i]
+   = byte, from the image's start, of the page on which frame i's packet
+   begins; frame_pcm_frames as the FLAC entries (both host arrays of
+   total_frames entries, may be NULL).  ATG_ERR_INVALID while an asynchronous
+   FLAC batch or host job of the engine is unwaited. */
+atg_status atg_oggflac_encode_device(atg_engine *eng, const atg_flac_options *opts,
+                                     const atg_oggflac_enc_options *ogg_opts,
+                                     const void *d_pcm, atg_pcm_format format,
+                                     const atg_track *tracks, uint32_t n_tracks,
+                                     uint32_t channels, uint32_t bits_per_sample,
+                                     uint32_t sample_rate, void *d_out, uint64_t out_cap,
+                                     atg_oggflac_track_result *results,
+                                     uint64_t *frame_page_offsets,
+                                     uint32_t *frame_pcm_frames);
+atg_status atg_oggflac_encode_host(atg_engine *eng, const atg_flac_options *opts,
+                                   const atg_oggflac_enc_options *ogg_opts,
+                                   const void *pcm, atg_pcm_format format,
+                                   const atg_track *tracks, uint32_t n_tracks,
+                                   uint32_t channels, uint32_t bits_per_sample,
+                                   uint32_t sample_rate, uint8_t *out, uint64_t out_cap,
+                                   atg_oggflac_track_result *results,
+                                   uint64_t *frame_page_offsets,
+                                   uint32_t *frame_pcm_frames);
 
 /* ------------------------------------------------------------------ */
 /* Integer PCM converters (track2track --bits-per-sample / --channels). */

@@ -50,6 +50,7 @@ EXPORTS = (
     "atg_decoder_set_frame_hypothesis", "atg_decoder_frame_hypothesis_redos",
     "atg_oggflac_read_info", "atg_oggflac_decode_host", "atg_oggflac_decode_device",
     "atg_oggflac_decode_fetch",
+    "atg_oggflac_batch_bounds", "atg_oggflac_encode_device", "atg_oggflac_encode_host",
     "atg_pcm_convert_last_error", "atg_pcm_convert_out_channels",
     "atg_pcm_convert_device", "atg_pcm_convert_host",
     "atg_replaygain_last_error", "atg_replaygain_device", "atg_replaygain_hist_gain",
@@ -194,6 +195,31 @@ FD_MESSAGES = {
     14: "invalid checksum in frame", 15: "EOF reading frame",
     16: "MD5 mismatch at end of stream",
 }
+
+
+OGG_PAGE_PER_PACKET = 1  # ATG_OGG_PAGE_PER_PACKET
+
+
+class OggFlacEncOptions(ctypes.Structure):
+    _fields_ = [("serial_number", c_u32), ("page_segments", c_u32), ("flags", c_u32),
+                ("channel_mask", c_u32)]
+
+
+class OggFlacTrackResult(ctypes.Structure):
+    _fields_ = [("out_offset", c_u64), ("bytes", c_u64),
+                ("first_frame", c_u32), ("n_frames", c_u32),
+                ("min_frame_bytes", c_u32), ("max_frame_bytes", c_u32),
+                ("md5", ctypes.c_uint8 * 16), ("status", c_i32),
+                ("pages", c_u32), ("header_pages", c_u32), ("serial_number", c_u32)]
+
+
+def oggflac_enc_options(serial_number=0, page_segments=255, page_per_packet=True,
+                        channel_mask=0, flags=None):
+    """atg_oggflac_enc_options; `flags` overrides page_per_packet"""
+    if flags is None:
+        flags = OGG_PAGE_PER_PACKET if page_per_packet else 0
+    return OggFlacEncOptions(int(serial_number) & 0xFFFFFFFF, int(page_segments), int(flags),
+                             int(channel_mask))
 
 
 class RgTrack(ctypes.Structure):
@@ -445,6 +471,17 @@ def load_library():
             c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(TrackResult),
             P, P]
         lib.atg_flac_encode_host.restype = ctypes.c_int
+        lib.atg_oggflac_batch_bounds.argtypes = [
+            ctypes.POINTER(FlacOptions), ctypes.POINTER(OggFlacEncOptions),
+            ctypes.POINTER(Track), c_u32, c_u32, c_u32, ctypes.POINTER(c_u64),
+            ctypes.POINTER(c_u64)]
+        lib.atg_oggflac_batch_bounds.restype = ctypes.c_int
+        for name in ("atg_oggflac_encode_device", "atg_oggflac_encode_host"):
+            getattr(lib, name).argtypes = [
+                P, ctypes.POINTER(FlacOptions), ctypes.POINTER(OggFlacEncOptions), P,
+                ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32, c_u32, P, c_u64,
+                ctypes.POINTER(OggFlacTrackResult), P, P]
+            getattr(lib, name).restype = ctypes.c_int
         lib.atg_flac_encode_host_async.argtypes = [
             P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, ctypes.POINTER(Track),
             c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(TrackResult),
@@ -1006,6 +1043,61 @@ class Engine(_Handle):
             channels, bits_per_sample, sample_rate, ctypes.c_void_p(d_out),
             out_cap, res))
         return [res[i] for i in range(n)]
+
+    def oggflac_bounds(self, options, ogg_options, tracks, channels, bits_per_sample):
+        arr, n, _keep = _track_array(tracks)
+        nf, nb = c_u64(), c_u64()
+        _check(self.lib, self.lib.atg_oggflac_batch_bounds(
+            ctypes.byref(options), ctypes.byref(ogg_options), arr, n, channels,
+            bits_per_sample, ctypes.byref(nf), ctypes.byref(nb)))
+        return nf.value, nb.value
+
+    def encode_oggflac(self, options, ogg_options, pcm, tracks, channels, bits_per_sample,
+                       sample_rate):
+        """encode a batch held in host memory to Ogg FLAC images
+        (atg_oggflac_encode_host).  pcm as encode().
+        Returns (out: uint8 array, results: list of OggFlacTrackResult,
+                 frame_page_offsets: uint64 array, frame_pcm: uint32 array)."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype == np.int16:
+            fmt = PCM_S16
+        elif pcm.dtype == np.int32:
+            fmt = PCM_S32
+        else:
+            raise TypeError("pcm must be int16 or int32")
+        tracks = list(tracks)
+        nf, nb = self.oggflac_bounds(options, ogg_options, tracks, channels, bits_per_sample)
+        arr, n, keep = _track_array(tracks)
+        out = np.empty(max(1, nb), dtype=np.uint8)
+        res = (OggFlacTrackResult * max(1, n))()
+        offs = np.zeros(max(1, nf), dtype=np.uint64)
+        fpcm = np.zeros(max(1, nf), dtype=np.uint32)
+        _check(self.lib, self.lib.atg_oggflac_encode_host(
+            self.handle, ctypes.byref(options), ctypes.byref(ogg_options),
+            pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels, bits_per_sample,
+            sample_rate, out.ctypes.data_as(ctypes.c_void_p), nb, res,
+            offs.ctypes.data_as(ctypes.c_void_p), fpcm.ctypes.data_as(ctypes.c_void_p)))
+        return out, [res[i] for i in range(n)], offs[:nf], fpcm[:nf]
+
+    def encode_oggflac_device(self, options, ogg_options, d_pcm, fmt, tracks, channels,
+                              bits_per_sample, sample_rate, d_out, out_cap, n_frames=0):
+        """as encode_device, to Ogg FLAC images (atg_oggflac_encode_device).
+        Returns (results, frame_page_offsets, frame_pcm); the two arrays are
+        filled when n_frames (oggflac_bounds' frame count) is given."""
+        if isinstance(tracks, TrackTable):
+            arr, n = tracks.arr, tracks.n
+        else:
+            arr, n, keep = _track_array(tracks)
+        res = (OggFlacTrackResult * max(1, n))()
+        offs = np.zeros(max(1, n_frames), dtype=np.uint64)
+        fpcm = np.zeros(max(1, n_frames), dtype=np.uint32)
+        _check(self.lib, self.lib.atg_oggflac_encode_device(
+            self.handle, ctypes.byref(options), ctypes.byref(ogg_options),
+            ctypes.c_void_p(d_pcm), fmt, arr, n, channels, bits_per_sample, sample_rate,
+            ctypes.c_void_p(d_out), out_cap, res,
+            offs.ctypes.data_as(ctypes.c_void_p) if n_frames else None,
+            fpcm.ctypes.data_as(ctypes.c_void_p) if n_frames else None))
+        return [res[i] for i in range(n)], offs[:n_frames], fpcm[:n_frames]
 
     def encode_device_async(self, options, d_pcm, fmt, tracks, channels, bits_per_sample,
                             sample_rate, d_out, out_cap):

@@ -33,6 +33,10 @@ under track2track).
 in one GPU pass (what track2track -j N achieves with N processes), MD5
 chains on the GPU, the tracks sharded over the node's GPUs.
 
+`encode_oggflac` / `encode_oggflac_batch` write the same frames into an Ogg
+container (.oga; GPU kernels ogg_mux.hip), where the reference calls the
+external `flac --ogg` (audiotools/flac.py:3249-3367).
+
 `encode_alac` / `encode_alac_batch` do the same for ALAC (reference
 src/encoders/alac.c:30-189; GPU kernels alac_encode.hip).
 
@@ -88,14 +92,12 @@ def _frame_sizes_or_none(sizes, block_size):
     return np.asarray(sizes, dtype=np.uint32)
 
 
-def encode_flac_batch(filenames, pcmreaders, block_size, max_lpc_order,
-                      min_residual_partition_order, max_residual_partition_order,
-                      mid_side=0, adaptive_mid_side=0, exhaustive_model_search=0,
-                      disable_verbatim_subframes=0, disable_constant_subframes=0,
-                      disable_fixed_subframes=0, disable_lpc_subframes=0,
-                      padding_size=4096):
-    """encode several PCMReaders (same channels / bits / rate) to several
-    .flac files in one GPU batch; returns one offsets list per file"""
+def _flac_batch(filenames, pcmreaders, block_size, flac_args, encode):
+    """what encode_flac_batch and encode_oggflac_batch share: the readers
+    drained to one PCM array, the tracks sharded over the node's GPUs,
+    encode(engine, options, pcm, tracks, channels, bps, rate, first track) ->
+    (out, results, per-frame offsets, per-frame pcm frames) per shard, the
+    images written to the files; returns one offsets list per file"""
     filenames = list(filenames)
     pcmreaders = list(pcmreaders)
     if len(filenames) != len(pcmreaders):
@@ -110,12 +112,7 @@ def encode_flac_batch(filenames, pcmreaders, block_size, max_lpc_order,
                              "bits-per-sample and sample rate")
     files = [open(fn, "wb") for fn in filenames]
     try:
-        opts = _atgpu.make_options(
-            block_size, max_lpc_order, min_residual_partition_order,
-            max_residual_partition_order, mid_side, adaptive_mid_side,
-            exhaustive_model_search, disable_verbatim_subframes,
-            disable_constant_subframes, disable_fixed_subframes,
-            disable_lpc_subframes, padding_size)
+        opts = _atgpu.make_options(block_size, *flac_args)
         parts, tracks, start = [], [], 0
         for r in pcmreaders:
             samples, sizes = _collect(r, block_size)
@@ -138,9 +135,9 @@ def encode_flac_batch(filenames, pcmreaders, block_size, max_lpc_order,
             s1 = tracks[t1 - 1][0] + tracks[t1 - 1][1]
             eng = (_atgpu.engine() if len(ranges) == 1
                    else _atgpu.shard_object("engine", i, devs[i]))
-            return eng.encode(opts, pcm[s0 * channels:s1 * channels],
-                              [(a - s0, n, fs) for a, n, fs in tracks[t0:t1]],
-                              channels, bps, rate)
+            return encode(eng, opts, pcm[s0 * channels:s1 * channels],
+                          [(a - s0, n, fs) for a, n, fs in tracks[t0:t1]],
+                          channels, bps, rate, t0)
 
         lists = []
         for (t0, t1), (out, results, offsets, pcm_frames) in zip(
@@ -156,6 +153,65 @@ def encode_flac_batch(filenames, pcmreaders, block_size, max_lpc_order,
     finally:
         for f in files:
             f.close()
+
+
+def encode_flac_batch(filenames, pcmreaders, block_size, max_lpc_order,
+                      min_residual_partition_order, max_residual_partition_order,
+                      mid_side=0, adaptive_mid_side=0, exhaustive_model_search=0,
+                      disable_verbatim_subframes=0, disable_constant_subframes=0,
+                      disable_fixed_subframes=0, disable_lpc_subframes=0,
+                      padding_size=4096):
+    """encode several PCMReaders (same channels / bits / rate) to several
+    .flac files in one GPU batch; returns one offsets list per file"""
+    def encode(eng, opts, pcm, tracks, channels, bps, rate, t0):
+        return eng.encode(opts, pcm, tracks, channels, bps, rate)
+
+    return _flac_batch(filenames, pcmreaders, block_size,
+                       (max_lpc_order, min_residual_partition_order,
+                        max_residual_partition_order, mid_side, adaptive_mid_side,
+                        exhaustive_model_search, disable_verbatim_subframes,
+                        disable_constant_subframes, disable_fixed_subframes,
+                        disable_lpc_subframes, padding_size), encode)
+
+
+def encode_oggflac_batch(filenames, pcmreaders, block_size, max_lpc_order,
+                         min_residual_partition_order, max_residual_partition_order,
+                         mid_side=0, adaptive_mid_side=0, exhaustive_model_search=0,
+                         disable_verbatim_subframes=0, disable_constant_subframes=0,
+                         disable_fixed_subframes=0, disable_lpc_subframes=0,
+                         padding_size=4096, serial_number=None, page_segments=255,
+                         page_per_packet=True, channel_mask=0):
+    """encode several PCMReaders (same channels / bits / rate) to several
+    Ogg FLAC (.oga) files in one GPU batch (ogg_mux.hip; the reference pipes
+    each to `flac --ogg`, audiotools/flac.py:3249-3367).  File k of the call
+    gets the serial number serial_number + k (None: 32 random bits per call);
+    a page holds page_segments lacing values at most and, with
+    page_per_packet, no more than one FLAC frame; a nonzero channel_mask is
+    written as WAVEFORMATEXTENSIBLE_CHANNEL_MASK.  Returns one list of
+    (offset of the page the frame's packet begins on, pcm frames) per file."""
+    if serial_number is None:
+        import random
+        serial_number = random.getrandbits(32)
+
+    def encode(eng, opts, pcm, tracks, channels, bps, rate, t0):
+        ogg = _atgpu.oggflac_enc_options(serial_number + t0, page_segments, page_per_packet,
+                                         channel_mask)
+        return eng.encode_oggflac(opts, ogg, pcm, tracks, channels, bps, rate)
+
+    return _flac_batch(filenames, pcmreaders, block_size,
+                       (max_lpc_order, min_residual_partition_order,
+                        max_residual_partition_order, mid_side, adaptive_mid_side,
+                        exhaustive_model_search, disable_verbatim_subframes,
+                        disable_constant_subframes, disable_fixed_subframes,
+                        disable_lpc_subframes, padding_size), encode)
+
+
+def encode_oggflac(filename, pcmreader, block_size, max_lpc_order,
+                   min_residual_partition_order, max_residual_partition_order, **options):
+    """one PCMReader to one Ogg FLAC file: encode_oggflac_batch of one"""
+    return encode_oggflac_batch([filename], [pcmreader], block_size, max_lpc_order,
+                                min_residual_partition_order, max_residual_partition_order,
+                                **options)[0]
 
 
 def encode_alac_batch(files, pcmreaders, block_size, initial_history, history_multiplier,

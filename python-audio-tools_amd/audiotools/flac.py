@@ -371,8 +371,9 @@ class OggFlacAudio(FlacAudio):
     """the read side of the reference's OggFlacAudio (audiotools/flac.py:
     3040-3246): STREAMINFO from the first Ogg packet, to_pcm through
     decoders.OggFlacDecoder (GPU), verify and convert as AudioFile's.
-    Writing is not provided: the reference's from_pcm pipes PCM into the
-    external `flac --ogg` program."""
+    from_pcm writes through encoders.encode_oggflac when given it as
+    encoding_function (the reference pipes PCM into the external
+    `flac --ogg` program); metadata cannot be rewritten."""
 
     SUFFIX = "oga"
     NAME = SUFFIX
@@ -424,8 +425,40 @@ class OggFlacAudio(FlacAudio):
     @classmethod
     def from_pcm(cls, filename, pcmreader, compression=None, total_pcm_frames=None,
                  encoding_function=None):
-        raise EncodingError("writing Ogg FLAC is not supported: the reference encodes it "
-                            "through the external flac program")
+        """with encoding_function = audiotools.encoders.encode_oggflac: the
+        reference's from_pcm (flac.py:3249-3367), the external `flac --ogg`
+        replaced by the GPU encoder -- the preset from `compression`, channel
+        counts and masks refused as there (:3280-3316), the mask written as
+        WAVEFORMATEXTENSIBLE_CHANNEL_MASK for more than 2 channels or 16 bits
+        (:3355-3363).  With the default None it raises EncodingError, as
+        before the encoder existed (turning it on by default is a separate
+        decision)."""
+        if encoding_function is None:
+            raise EncodingError("writing Ogg FLAC is not enabled by default: pass "
+                                "encoding_function=audiotools.encoders.encode_oggflac "
+                                "(the reference encodes it through the external flac program)")
+        if compression is None or compression not in cls.COMPRESSION_MODES:
+            compression = DEFAULT_COMPRESSION
+        if pcmreader.channels > 8:
+            raise UnsupportedChannelCount(filename, pcmreader.channels)
+        if int(pcmreader.channel_mask) == 0:
+            channel_mask = _DEFAULT_MASKS.get(pcmreader.channels, 0)
+        elif int(pcmreader.channel_mask) not in _VALID_MASKS:
+            raise UnsupportedChannelMask(filename, int(pcmreader.channel_mask))
+        else:
+            channel_mask = int(pcmreader.channel_mask)
+        if not (pcmreader.channels > 2 or pcmreader.bits_per_sample > 16):
+            channel_mask = 0
+        try:
+            encoding_function(filename, pcmreader=BufferedPCMReader(pcmreader),
+                              channel_mask=channel_mask, **COMPRESSION_PRESETS[compression])
+            return cls(filename)
+        except (IOError, ValueError) as err:
+            _unlink(filename)
+            raise EncodingError(str(err))
+        except Exception:
+            _unlink(filename)
+            raise
 
     def update_metadata(self, metadata):
         raise NotImplementedError("Ogg FLAC metadata cannot be written")

@@ -32,16 +32,22 @@
 #include "flac_dev.h"
 #include "launch.h"
 #include "md5_cpu.h"
+#include "ogg_demux.h"
+#include "ogg_mux.h"
 
 namespace {
 
 thread_local ErrSlot g_err;
 #define HIP_TRY(expr) ATG_HIP_TRY(g_err, expr, #expr)
 
+// the VORBIS_COMMENT vendor string (version_string of the reference)
+const char kVendor[] = "Python Audio Tools 2.22alpha1";
+
 const int kNumTimed = 8;
 const char *kTimedNames[kNumTimed] = {"lpc_analyze", "subframe_search", "frame_decide",
                                       "track_scan",  "frame_pack",      "track_md5",
                                       "stream_header", "total"};
+const char *kOggTimedNames[4] = {"ogg_plan", "ogg_pages", "ogg_split", "ogg_crc"};
 
 // CRC-16 (0x8005) slicing tables t16[k][b] = CRC of byte b followed by k
 // zero bytes, the CRC-8 table, and "advance by 2^m zero bytes" matrices
@@ -324,6 +330,14 @@ struct atg_engine {
     // the plan (and a slot's frame/track tables when it last ran that plan)
     std::vector<uint8_t> plan_key;
     std::shared_ptr<Plan> plan_cached;
+    // Ogg FLAC encode (atg_oggflac_encode_*): the native images are staged in
+    // ogg_stage and muxed from there by ogg_mux.hip
+    DevBuf ogg_stage, ogg_tmpl, ogg_hp, ogg_trk, ogg_frm, ogg_pgoff, ogg_out, ogg_pages;
+    DevBuf ogg_pcm, ogg_img; // the host entry's device PCM and images
+    const uint32_t *ogg_crc = nullptr, *ogg_adv = nullptr; // ogg_demux.hip's tables
+    hipEvent_t ogg_ev[5] = {};
+    float ogg_times[4] = {};
+    bool ogg_last = false; // the engine's last batch was an Ogg one
 };
 
 namespace {
@@ -1172,6 +1186,7 @@ atg_status finish_batch(atg_engine *e, EncSlot &sl)
         e->times[k] = ms;
     }
     e->have_times = true;
+    e->ogg_last = false;
     uint32_t err_h = *sl.err_h;
     if (err_h & 1u)
         return g_err.fail(ATG_ERR_UNSUPPORTED, "frame longer than the GPU block limit");
@@ -1648,6 +1663,242 @@ uint64_t auto_depth(atg_engine *e, const Plan &pl, int fmt)
     return std::max<uint64_t>(kEncSlots, std::min(d, cap));
 }
 
+
+// ---- Ogg FLAC encode (ogg_mux.hip) ----------------------------------------
+// The page layout of DESIGN.md section 4k.  The header pages are the same for
+// every track of a batch but for the serial number, STREAMINFO and the
+// end-of-stream flag of an empty track: built once here, patched on the device.
+struct OggLayout {
+    uint32_t S = 255;
+    bool per_packet = true;
+    std::vector<uint8_t> tmpl; // header pages: serial 0, checksum 0, STREAMINFO 0
+    std::vector<uint32_t> hp;  // (offset, size) of each
+};
+
+atg_status ogg_layout(const atg_flac_options *fo, const atg_oggflac_enc_options *oo, OggLayout &L)
+{
+    if (!fo || !oo)
+        return g_err.fail(ATG_ERR_INVALID, "options is NULL");
+    if (oo->page_segments > 255u)
+        return g_err.fail(ATG_ERR_INVALID, "page_segments must be 0..255");
+    if (oo->flags & ~ATG_OGG_PAGE_PER_PACKET)
+        return g_err.fail(ATG_ERR_INVALID, "unknown Ogg FLAC encoder flag");
+    if (fo->padding_size > 0xFFFFFFu)
+        return g_err.fail(ATG_ERR_INVALID, "padding_size must fit in 24 bits");
+    L.S = oo->page_segments ? oo->page_segments : 255u;
+    L.per_packet = (oo->flags & ATG_OGG_PAGE_PER_PACKET) != 0;
+    const uint32_t pad = fo->padding_size;
+    std::vector<std::vector<uint8_t>> pk(2);
+    // the mapping's first packet: STREAMINFO's 34 bytes are filled per track
+    const uint8_t first[17] = {0x7F, 'F', 'L', 'A', 'C', 1, 0, 0, (uint8_t)(pad ? 2 : 1),
+                               'f', 'L', 'a', 'C', 0, 0, 0, 34};
+    pk[0].assign(first, first + 17);
+    pk[0].resize(17 + 34, 0);
+    // VORBIS_COMMENT: the vendor string and, with a mask, its one comment
+    std::vector<uint8_t> &vc = pk[1];
+    auto le32 = [&vc](uint32_t v) {
+        for (int k = 0; k < 4; ++k)
+            vc.push_back((uint8_t)(v >> (8 * k)));
+    };
+    char tag[64] = "";
+    const int tlen = oo->channel_mask
+                         ? std::snprintf(tag, sizeof(tag), "WAVEFORMATEXTENSIBLE_CHANNEL_MASK=0x%.4X",
+                                         (unsigned)oo->channel_mask)
+                         : 0;
+    const uint32_t vlen = (uint32_t)std::strlen(kVendor);
+    const uint32_t vcb = 4u + vlen + 4u + (tlen ? 4u + (uint32_t)tlen : 0u);
+    vc.push_back((uint8_t)(0x04 | (pad ? 0 : 0x80)));
+    vc.push_back((uint8_t)(vcb >> 16));
+    vc.push_back((uint8_t)(vcb >> 8));
+    vc.push_back((uint8_t)vcb);
+    le32(vlen);
+    vc.insert(vc.end(), kVendor, kVendor + vlen);
+    le32(tlen ? 1u : 0u);
+    if (tlen) {
+        le32((uint32_t)tlen);
+        vc.insert(vc.end(), tag, tag + tlen);
+    }
+    if (pad) {
+        pk.emplace_back();
+        pk[2] = {0x81, (uint8_t)(pad >> 16), (uint8_t)(pad >> 8), (uint8_t)pad};
+        pk[2].resize(4 + (size_t)pad, 0);
+    }
+    L.tmpl.clear();
+    L.hp.clear();
+    uint32_t seq = 0;
+    for (const std::vector<uint8_t> &p : pk) {
+        const size_t nseg = p.size() / 255 + 1;
+        for (size_t s0 = 0; s0 < nseg; s0 += L.S, ++seq) {
+            const size_t ns = std::min<size_t>(L.S, nseg - s0);
+            const size_t b0 = 255 * s0, b1 = std::min(p.size(), 255 * (s0 + ns));
+            const size_t off = L.tmpl.size();
+            L.tmpl.insert(L.tmpl.end(), {'O', 'g', 'g', 'S', 0,
+                                         (uint8_t)((s0 ? 1 : 0) | (seq ? 0 : 2))});
+            L.tmpl.resize(off + 18, 0); // granule 0, serial (per track)
+            for (int k = 0; k < 4; ++k)
+                L.tmpl.push_back((uint8_t)(seq >> (8 * k)));
+            L.tmpl.resize(off + 26, 0); // checksum (k_ogg_mux_crc)
+            L.tmpl.push_back((uint8_t)ns);
+            for (size_t k = s0; k < s0 + ns; ++k)
+                L.tmpl.push_back((uint8_t)(k + 1 < nseg ? 255 : p.size() % 255));
+            L.tmpl.insert(L.tmpl.end(), p.begin() + (std::ptrdiff_t)b0,
+                          p.begin() + (std::ptrdiff_t)b1);
+            L.hp.push_back((uint32_t)off);
+            L.hp.push_back((uint32_t)(L.tmpl.size() - off));
+        }
+    }
+    return ATG_OK;
+}
+
+// audio pages one frame of at most fb bytes can take, and its bytes in the
+// image with them (both ascend with the frame's bytes, and a filled layout
+// takes no more pages than a page per packet)
+uint64_t ogg_frame_pages(const OggLayout &L, uint64_t fb) { return (fb / 255 + 1 + L.S - 1) / L.S; }
+
+uint64_t ogg_track_bound(const OggLayout &L, uint64_t n_frames, uint64_t fb)
+{
+    const uint64_t b = L.tmpl.size() + n_frames * (27 * ogg_frame_pages(L, fb) + fb / 255 + 1 + fb);
+    return (b + 15) & ~15ull;
+}
+
+atg_status ogg_encode_device(atg_engine *e, const atg_flac_options *opts,
+                             const atg_oggflac_enc_options *oo, const void *d_pcm,
+                             atg_pcm_format format, const atg_track *tracks, uint32_t n_tracks,
+                             uint32_t channels, uint32_t bps, uint32_t rate, void *d_out,
+                             uint64_t out_cap, atg_oggflac_track_result *results,
+                             uint64_t *frame_page_offsets, uint32_t *frame_pcm_frames)
+{
+    OggLayout L;
+    atg_status st = ogg_layout(opts, oo, L);
+    if (st != ATG_OK)
+        return st;
+    if (!engine_idle(e))
+        return g_err.fail(ATG_ERR_INVALID,
+                          "an encode batch or host job is in flight: wait for it first");
+    std::shared_ptr<Plan> plp;
+    st = get_plan(e, opts, tracks, n_tracks, channels, bps, rate, plp);
+    if (st != ATG_OK)
+        return st;
+    const Plan &pl = *plp;
+    const size_t nt = pl.tracks.size(), nf = pl.frames.size();
+    const uint32_t HP = (uint32_t)(L.hp.size() / 2);
+    const uint64_t per_frame = ogg_frame_pages(L, pl.frame_bound);
+    std::vector<OggMuxTrack> mt(nt);
+    uint64_t out = 0, page_slots = 0, max_audio = 0;
+    for (size_t t = 0; t < nt; ++t) {
+        const TrackInfo &ti = pl.tracks[t];
+        mt[t].out_base = out;
+        mt[t].src_base = ti.out_base;
+        mt[t].page_base = page_slots;
+        mt[t].first_pos = ti.first_pos;
+        mt[t].n_frames = ti.n_frames;
+        out += ogg_track_bound(L, ti.n_frames, pl.frame_bound);
+        page_slots += HP + ti.n_frames * per_frame;
+        max_audio = std::max<uint64_t>(max_audio, ti.n_frames * per_frame);
+    }
+    if (out > out_cap)
+        return g_err.fail(ATG_ERR_CAPACITY, "output smaller than atg_oggflac_batch_bounds");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->ogg_crc) {
+        HIP_TRY(ogg_upload_tables());
+        HIP_TRY(ogg_crc_tables(&e->ogg_crc, &e->ogg_adv));
+        for (hipEvent_t &ev : e->ogg_ev)
+            HIP_TRY(hipEventCreate(&ev));
+    }
+    // the native images, into the staging buffer
+    HIP_TRY(e->ogg_stage.ensure((size_t)std::max<uint64_t>(pl.out_bytes, 16)));
+    uint64_t ticket = 0;
+    e->sync_call = true;
+    st = atg_flac_encode_device_async(e, opts, d_pcm, format, tracks, n_tracks, channels, bps,
+                                      rate, e->ogg_stage.p, e->ogg_stage.cap, &ticket);
+    e->sync_call = false;
+    if (st != ATG_OK)
+        return st;
+    EncSlot *sl = nullptr;
+    st = wait_ticket(e, ticket, sl);
+    if (st != ATG_OK)
+        return st;
+    if (!nt)
+        return ATG_OK;
+    OggMuxParams mp;
+    mp.n_tracks = (uint32_t)nt;
+    mp.S = L.S;
+    mp.per_packet = L.per_packet ? 1u : 0u;
+    mp.serial = oo->serial_number;
+    mp.hdr_pages = HP;
+    mp.native_hdr = pl.p.header_bytes;
+    mp.hdr_bytes = L.tmpl.size();
+    HIP_TRY(e->ogg_tmpl.ensure(L.tmpl.size() + 4));
+    HIP_TRY(e->ogg_hp.ensure(L.hp.size() * sizeof(uint32_t)));
+    HIP_TRY(e->ogg_trk.ensure(nt * sizeof(OggMuxTrack)));
+    HIP_TRY(e->ogg_frm.ensure(std::max<size_t>(nf, 1) * sizeof(OggMuxFrame)));
+    HIP_TRY(e->ogg_pgoff.ensure(std::max<size_t>(nf, 1) * sizeof(uint64_t)));
+    HIP_TRY(e->ogg_out.ensure(nt * sizeof(OggMuxOut)));
+    HIP_TRY(e->ogg_pages.ensure((size_t)page_slots * sizeof(OggMuxPage)));
+    hipStream_t q = e->s_main;
+    HIP_TRY(hipMemcpyAsync(e->ogg_tmpl.p, L.tmpl.data(), L.tmpl.size(), hipMemcpyHostToDevice, q));
+    HIP_TRY(hipMemcpyAsync(e->ogg_hp.p, L.hp.data(), L.hp.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, q));
+    HIP_TRY(hipMemcpyAsync(e->ogg_trk.p, mt.data(), nt * sizeof(OggMuxTrack),
+                           hipMemcpyHostToDevice, q));
+    const OggMuxTrack *dtr = (const OggMuxTrack *)e->ogg_trk.p;
+    const OggMuxOut *dout = (const OggMuxOut *)e->ogg_out.p;
+    OggMuxPage *dpg = (OggMuxPage *)e->ogg_pages.p;
+    const uint8_t *stage = (const uint8_t *)e->ogg_stage.p;
+    HIP_TRY(hipEventRecord(e->ogg_ev[0], q));
+    HIP_TRY(launch_ogg_mux_plan(mp, dtr, (const uint32_t *)sl->order.p,
+                                (const FrameDesc *)sl->fdesc.p, (const FrameInfo *)sl->frames.p,
+                                (OggMuxFrame *)e->ogg_frm.p, (uint64_t *)e->ogg_pgoff.p,
+                                (OggMuxOut *)e->ogg_out.p, q));
+    HIP_TRY(hipEventRecord(e->ogg_ev[1], q));
+    HIP_TRY(launch_ogg_mux_headers(mp, dtr, (const uint32_t *)e->ogg_hp.p,
+                                   (const uint8_t *)e->ogg_tmpl.p, stage, (uint8_t *)d_out, dpg,
+                                   q));
+    HIP_TRY(launch_ogg_mux_pages(mp, dtr, (const OggMuxFrame *)e->ogg_frm.p, dout,
+                                 (uint8_t *)d_out, dpg, max_audio, q));
+    HIP_TRY(hipEventRecord(e->ogg_ev[2], q));
+    HIP_TRY(launch_ogg_mux_split(mp, dtr, dout, dpg, stage, (uint8_t *)d_out, max_audio, q));
+    HIP_TRY(hipEventRecord(e->ogg_ev[3], q));
+    HIP_TRY(launch_ogg_mux_crc(mp, dtr, dout, dpg, e->ogg_crc, e->ogg_adv, (uint8_t *)d_out,
+                               max_audio, q));
+    HIP_TRY(hipEventRecord(e->ogg_ev[4], q));
+    std::vector<OggMuxOut> mo(nt);
+    std::vector<uint64_t> pgoff(nf);
+    HIP_TRY(hipMemcpyAsync(mo.data(), e->ogg_out.p, nt * sizeof(OggMuxOut),
+                           hipMemcpyDeviceToHost, q));
+    if (nf)
+        HIP_TRY(hipMemcpyAsync(pgoff.data(), e->ogg_pgoff.p, nf * sizeof(uint64_t),
+                               hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    for (int k = 0; k < 4; ++k)
+        if (hipEventElapsedTime(&e->ogg_times[k], e->ogg_ev[k], e->ogg_ev[k + 1]) != hipSuccess)
+            e->ogg_times[k] = 0.f;
+    e->ogg_last = true;
+    for (size_t t = 0; t < nt; ++t) {
+        const TrackInfo &ti = pl.tracks[t];
+        const TrackOut &to = sl->tout_h[t];
+        atg_oggflac_track_result &r = results[t];
+        r.out_offset = mt[t].out_base;
+        r.bytes = mo[t].bytes;
+        r.first_frame = pl.track_frame_pos[t];
+        r.n_frames = ti.n_frames;
+        r.min_frame_bytes = to.min_fs;
+        r.max_frame_bytes = to.max_fs;
+        std::memcpy(r.md5, to.md5, 16);
+        r.status = 0;
+        r.pages = HP + mo[t].pages;
+        r.header_pages = HP;
+        r.serial_number = oo->serial_number + (uint32_t)t;
+        for (uint32_t i = 0; i < ti.n_frames; ++i) {
+            if (frame_page_offsets)
+                frame_page_offsets[r.first_frame + i] = pgoff[ti.first_pos + i];
+            if (frame_pcm_frames)
+                frame_pcm_frames[r.first_frame + i] = pl.frames[pl.order[ti.first_pos + i]].n;
+        }
+    }
+    return ATG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1771,6 +2022,12 @@ void atg_engine_destroy(atg_engine *e)
     for (hipStream_t q : {e->s_h2d, e->s_hpack, e->s_d2h})
         if (q)
             (void)hipStreamDestroy(q);
+    for (DevBuf *b : {&e->ogg_stage, &e->ogg_tmpl, &e->ogg_hp, &e->ogg_trk, &e->ogg_frm,
+                      &e->ogg_pgoff, &e->ogg_out, &e->ogg_pages, &e->ogg_pcm, &e->ogg_img})
+        b->release();
+    for (hipEvent_t ev : e->ogg_ev)
+        if (ev)
+            (void)hipEventDestroy(ev);
     e->windows.release();
     if (e->ev_win)
         (void)hipEventDestroy(e->ev_win);
@@ -2011,6 +2268,98 @@ atg_status atg_flac_encode_host(atg_engine *e, const atg_flac_options *opts, con
     return atg_flac_encode_host_wait(e, t);
 }
 
+atg_status atg_oggflac_batch_bounds(const atg_flac_options *opts,
+                                    const atg_oggflac_enc_options *ogg_opts,
+                                    const atg_track *tracks, uint32_t n_tracks,
+                                    uint32_t channels, uint32_t bps, uint64_t *total_frames,
+                                    uint64_t *out_bytes)
+{
+    OggLayout L;
+    atg_status st = ogg_layout(opts, ogg_opts, L);
+    if (st != ATG_OK)
+        return st;
+    Plan pl;
+    st = make_plan(opts, tracks, n_tracks, channels, bps, 44100, pl);
+    if (st != ATG_OK)
+        return st;
+    uint64_t out = 0;
+    for (const TrackInfo &ti : pl.tracks)
+        out += ogg_track_bound(L, ti.n_frames, pl.frame_bound);
+    if (total_frames)
+        *total_frames = pl.frames.size();
+    if (out_bytes)
+        *out_bytes = out;
+    return ATG_OK;
+}
+
+atg_status atg_oggflac_encode_device(atg_engine *e, const atg_flac_options *opts,
+                                     const atg_oggflac_enc_options *ogg_opts, const void *d_pcm,
+                                     atg_pcm_format format, const atg_track *tracks,
+                                     uint32_t n_tracks, uint32_t channels, uint32_t bps,
+                                     uint32_t rate, void *d_out, uint64_t out_cap,
+                                     atg_oggflac_track_result *results,
+                                     uint64_t *frame_page_offsets, uint32_t *frame_pcm_frames)
+{
+    ATG_HANDLE_LOCK(e);
+    if (!e || (!tracks && n_tracks) || (!results && n_tracks))
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
+    return ogg_encode_device(e, opts, ogg_opts, d_pcm, format, tracks, n_tracks, channels, bps,
+                             rate, d_out, out_cap, results, frame_page_offsets,
+                             frame_pcm_frames);
+}
+
+atg_status atg_oggflac_encode_host(atg_engine *e, const atg_flac_options *opts,
+                                   const atg_oggflac_enc_options *ogg_opts, const void *pcm,
+                                   atg_pcm_format format, const atg_track *tracks,
+                                   uint32_t n_tracks, uint32_t channels, uint32_t bps,
+                                   uint32_t rate, uint8_t *out, uint64_t out_cap,
+                                   atg_oggflac_track_result *results,
+                                   uint64_t *frame_page_offsets, uint32_t *frame_pcm_frames)
+{
+    ATG_HANDLE_LOCK(e);
+    if (!e || (!tracks && n_tracks) || (!results && n_tracks) || (!out && n_tracks))
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
+    uint64_t bound = 0, samples = 0;
+    atg_status st = atg_oggflac_batch_bounds(opts, ogg_opts, tracks, n_tracks, channels, bps,
+                                             nullptr, &bound);
+    if (st != ATG_OK)
+        return st;
+    if (format == ATG_PCM_S16 && bps > 16)
+        return g_err.fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
+    for (uint32_t t = 0; t < n_tracks; ++t)
+        samples = std::max(samples, (tracks[t].pcm_offset + tracks[t].pcm_frames) * channels);
+    if (samples && !pcm)
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
+    const size_t pcm_bytes = (size_t)samples * (format == ATG_PCM_S16 ? 2u : 4u);
+    HIP_TRY(hipSetDevice(e->device));
+    if (!engine_idle(e))
+        return g_err.fail(ATG_ERR_INVALID,
+                          "an encode batch or host job is in flight: wait for it first");
+    HIP_TRY(e->ogg_pcm.ensure(std::max<size_t>(pcm_bytes, 16)));
+    HIP_TRY(e->ogg_img.ensure((size_t)std::max<uint64_t>(bound, 16)));
+    if (pcm_bytes)
+        HIP_TRY(hipMemcpy(e->ogg_pcm.p, pcm, pcm_bytes, hipMemcpyHostToDevice));
+    st = ogg_encode_device(e, opts, ogg_opts, e->ogg_pcm.p, format, tracks, n_tracks, channels,
+                           bps, rate, e->ogg_img.p, e->ogg_img.cap, results, frame_page_offsets,
+                           frame_pcm_frames);
+    if (st != ATG_OK)
+        return st;
+    // the images back to back, 16-byte aligned
+    uint64_t pos = 0;
+    for (uint32_t t = 0; t < n_tracks; ++t) {
+        atg_oggflac_track_result &r = results[t];
+        if (pos + r.bytes > out_cap)
+            return g_err.fail(ATG_ERR_CAPACITY, "output buffer too small for the images");
+        HIP_TRY(hipMemcpy(out + pos, (const uint8_t *)e->ogg_img.p + r.out_offset, r.bytes,
+                          hipMemcpyDeviceToHost));
+        const uint64_t next = (pos + r.bytes + 15) & ~15ull;
+        std::memset(out + pos + r.bytes, 0, (size_t)(std::min(next, out_cap) - pos - r.bytes));
+        r.out_offset = pos;
+        pos = next;
+    }
+    return ATG_OK;
+}
+
 uint64_t atg_flac_stream_header(const atg_flac_options *o, uint32_t channels, uint32_t bps,
                                 uint32_t rate, uint64_t total_samples, uint32_t min_frame_bytes,
                                 uint32_t max_frame_bytes, const uint8_t *md5, uint8_t *out,
@@ -2019,8 +2368,8 @@ uint64_t atg_flac_stream_header(const atg_flac_options *o, uint32_t channels, ui
     // fLaC + STREAMINFO (flacenc_write_streaminfo, flac.c:376-409, fields
     // clamped) + VORBIS_COMMENT with the vendor string + PADDING
     // (flac.c:208-238): the bytes k_stream_header writes on the device
-    static const char vendor[] = "Python Audio Tools 2.22alpha1";
-    const uint32_t vlen = (uint32_t)sizeof(vendor) - 1u;
+    const char *vendor = kVendor;
+    const uint32_t vlen = (uint32_t)std::strlen(kVendor);
     if (!o || !md5 || channels < 1 || bps < 1 || o->padding_size > 0xFFFFFFu)
         return 0;
     const uint64_t need = 4 + 4 + 34 + 4 + 4 + vlen + 4 + 4 + (uint64_t)o->padding_size;
@@ -2259,12 +2608,19 @@ int atg_engine_kernel_times(atg_engine *e, const char **names, float *ms, int ca
     ATG_HANDLE_LOCK(e);
     if (!e || !e->have_times)
         return 0;
-    const int n = cap < kNumTimed ? cap : kNumTimed;
+    int n = cap < kNumTimed ? cap : kNumTimed;
     for (int k = 0; k < n; ++k) {
         if (names)
             names[k] = kTimedNames[k];
         if (ms)
             ms[k] = e->times[k];
+    }
+    // after an Ogg FLAC batch: the container phases (ogg_mux.hip)
+    for (int k = 0; e->ogg_last && k < 4 && n < cap; ++k, ++n) {
+        if (names)
+            names[n] = kOggTimedNames[k];
+        if (ms)
+            ms[n] = e->ogg_times[k];
     }
     return n;
 }

@@ -51,6 +51,9 @@ struct OggSum {
 };
 
 hipError_t ogg_upload_tables();
+// the device addresses of the uploaded tables, for the muxer (ogg_mux.hip):
+// crc[4][256] slicing tables, adv[17][32] "2^m zero bytes" matrices
+hipError_t ogg_crc_tables(const uint32_t **crc, const uint32_t **adv);
 // the page walk, one wave per stream; pass 1 counts (walk), pass 2 also fills
 // the page records
 hipError_t launch_ogg_walk(const uint8_t *data, const OggStream *streams, uint32_t n, int pass,

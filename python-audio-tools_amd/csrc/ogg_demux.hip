@@ -412,6 +412,14 @@ hipError_t ogg_upload_tables()
     return e;
 }
 
+hipError_t ogg_crc_tables(const uint32_t **crc, const uint32_t **adv)
+{
+    hipError_t e = hipGetSymbolAddress((void **)crc, HIP_SYMBOL(g_ogg_crc));
+    if (e == hipSuccess)
+        e = hipGetSymbolAddress((void **)adv, HIP_SYMBOL(g_ogg_adv));
+    return e;
+}
+
 hipError_t launch_ogg_walk(const uint8_t *data, const OggStream *streams, uint32_t n, int pass,
                            OggWalk *walk, OggPage *pages, hipStream_t s)
 {

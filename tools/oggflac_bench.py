@@ -16,6 +16,20 @@ The container pass moves each image about three times (the checksum pass
 reads it, the gather reads and writes it): that over 8 TB/s is the roofline
 share given for its kernels.  Writes one JSON document (--out, default
 profiles/oggflac_bench.json) and prints it.
+
+--encode measures the other direction instead: the Ogg FLAC batch encode
+(atg_oggflac_encode_device) of device-made PCM in both page layouts -- a page
+per packet (the default) and filled 255-segment pages -- against the native
+atg_flac_encode_device of the same batch, alternating step by step in one
+process.  Every Ogg image is decoded back on the GPU (status 0, MD5 equal to
+the source's) and 4 images are compared byte for byte with
+tests/oggflac_mux_port.py.  The container phases (ogg_plan, ogg_pages,
+ogg_split, ogg_crc of atg_engine_kernel_times) move the image about three
+times: the split reads and writes it, the checksum pass reads it.  There is
+no reference Ogg FLAC encoder (the reference calls the external `flac --ogg`);
+where oracle/_ref/oggflacdec exists its decode of the same images at --procs
+processes is recorded for scale only.  Default output:
+profiles/oggflac_enc_bench.json.
 """
 import argparse
 import concurrent.futures
@@ -60,6 +74,135 @@ def reference_run(images, n_tracks, procs):
         return time.perf_counter() - t0
 
 
+def encode_main(args):
+    import torch
+    import oggflac_mux_port as mp
+    import oracle_port
+    from audiotools import _atgpu
+
+    ch, bps, rate = 2, 16, args.rate
+    n = int(args.seconds * rate)
+    distinct = min(args.distinct, args.tracks)
+    torch.cuda.init()
+    # the PCM, made on the device: two sines per channel and noise
+    g = torch.Generator(device="cuda").manual_seed(1)
+    t = torch.arange(n, device="cuda", dtype=torch.float64)[:, None]
+    sig = []
+    for k in range(distinct):
+        f = torch.rand(2, ch, device="cuda", generator=g, dtype=torch.float64)
+        x = (0.35 * torch.sin(2 * np.pi * (100 + 1900 * f[0]) * t / rate) +
+             0.25 * torch.sin(2 * np.pi * (2000 + 10000 * f[1]) * t / rate)) * 32767
+        x = x + 8.0 * torch.randn(n, ch, device="cuda", generator=g, dtype=torch.float64)
+        sig.append(x.round().clamp(-32768, 32767).to(torch.int16))
+    src = [x.cpu().numpy().reshape(-1) for x in sig]
+    want_md5 = [hashlib.md5(x.astype("<i2").tobytes()).digest() for x in src]
+    pcm = torch.stack([sig[k % distinct] for k in range(args.tracks)]).contiguous()
+    del sig
+    tracks = _atgpu.TrackTable([(k * n, n) for k in range(args.tracks)])
+    preset = dict(oracle_port.PRESETS["8"])
+    opts = _atgpu.make_options(**preset)
+    eng = _atgpu.Engine(0)
+    serial = 0x4F676721
+    layouts = {"page_per_packet": dict(page_segments=255, page_per_packet=True),
+               "filled_255": dict(page_segments=255, page_per_packet=False)}
+    ogg = {k: _atgpu.oggflac_enc_options(serial, **v) for k, v in layouts.items()}
+    plain = [(k * n, n) for k in range(args.tracks)]
+    nf, cap = eng.bounds(opts, plain, ch, bps)
+    for o in ogg.values():
+        cap = max(cap, eng.oggflac_bounds(opts, o, plain, ch, bps)[1])
+    out = torch.empty(cap + 64, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    names = list(layouts) + ["native"]
+    rows, walls, last = {k: [] for k in names}, {k: [] for k in names}, {}
+    for step in range(args.warmup + args.steps):
+        for name in names:
+            t0 = time.perf_counter()
+            if name == "native":
+                r = eng.encode_device(opts, pcm.data_ptr(), _atgpu.PCM_S16, tracks, ch, bps, rate,
+                                      out.data_ptr(), cap)
+            else:
+                r, _, _ = eng.encode_oggflac_device(opts, ogg[name], pcm.data_ptr(),
+                                                    _atgpu.PCM_S16, tracks, ch, bps, rate,
+                                                    out.data_ptr(), cap)
+            wall = (time.perf_counter() - t0) * 1e3
+            if step >= args.warmup:
+                rows[name].append(eng.kernel_times())
+                walls[name].append(wall)
+    # verify: every image of both layouts decoded back on the GPU, 4 compared
+    # with the port; the reference's decoder on them for scale
+    dec = _atgpu.Decoder(0)
+    bad, compared, ref_s, image_bytes, pages = {}, {}, {}, {}, {}
+    for name in layouts:
+        r, _, _ = eng.encode_oggflac_device(opts, ogg[name], pcm.data_ptr(), _atgpu.PCM_S16,
+                                            tracks, ch, bps, rate, out.data_ptr(), cap)
+        image_bytes[name] = int(sum(x.bytes for x in r))
+        pages[name] = int(sum(x.pages for x in r))
+        dr, _, _ = dec.decode_oggflac_device(
+            out.data_ptr(), cap, [_atgpu.oggflac_dec_track(x.out_offset, x.bytes) for x in r])
+        bad[name] = int(sum(not (d.status == 0 and d.ogg_status == 0 and d.pcm_frames == n and
+                                 bytes(d.md5) == want_md5[k % distinct] and
+                                 bytes(x.md5) == want_md5[k % distinct])
+                            for k, (d, x) in enumerate(zip(dr, r))))
+        picks = sorted(set([0, 1, args.tracks // 2, args.tracks - 1]))
+        same, images = 0, []
+        for k in picks:
+            img = out[r[k].out_offset:r[k].out_offset + r[k].bytes].cpu().numpy().tobytes()
+            want = mp.encode(src[k % distinct], ch, bps, rate,
+                             dict(layouts[name], serial_number=serial + k), **preset)["image"]
+            same += img == want
+            images.append(img)
+        compared[name] = {"tracks": picks, "equal_to_port": int(same)}
+        if os.path.exists(REF_DEC) and not args.no_reference:
+            ref_s[name] = reference_run(images, args.tracks, args.procs)
+    dec.close()
+    eng.close()
+
+    native = mean_times(rows["native"])
+    native_wall = float(np.mean(walls["native"]))
+    doc = {"shape": {"tracks": args.tracks, "seconds": args.seconds, "rate": rate, "channels": ch,
+                     "bits_per_sample": bps, "kind": "two sines + noise, made on the device",
+                     "distinct_signals": distinct, "flac_frames": nf, "warmup": args.warmup,
+                     "steps": args.steps, "device": torch.cuda.get_device_name(0)},
+           "verify": {"tracks": args.tracks, "tracks_not_verified": bad,
+                      "compared_with_port": compared},
+           "native_flac": {"stage_ms": native, "wall_ms_per_batch": spread(walls["native"])}}
+    for name in layouts:
+        ms = mean_times(rows[name])
+        wall = float(np.mean(walls[name]))
+        phases = {k: ms[k] for k in ("ogg_plan", "ogg_pages", "ogg_split", "ogg_crc")}
+        container = sum(phases.values())
+        moved = 3 * image_bytes[name]
+        diff = wall - native_wall
+        doc[name] = {
+            "stage_ms": ms, "wall_ms_per_batch": spread(walls[name]),
+            "over_native_wall": wall / native_wall, "wall_minus_native_ms": diff,
+            "container_ms": container, "container_phases_ms": phases,
+            "largest_container_phase": max(phases, key=phases.get),
+            "host_side_of_the_difference_ms": diff - container,
+            "image_bytes": image_bytes[name], "pages": pages[name],
+            "container_bytes_moved": moved,
+            "container_fraction_of_8TBps": moved / (container * 1e-3) / HBM_BYTES_PER_S,
+            "pcm_frames_per_s_wall": n * args.tracks / (wall * 1e-3)}
+        if name in ref_s:
+            doc[name]["reference_decoder_s"] = ref_s[name]
+    doc["reference"] = (
+        "no reference Ogg FLAC encoder exists (the reference pipes PCM to the external "
+        "`flac --ogg`): nothing here is a baseline for the encode. " +
+        ("reference_decoder_s is oracle/_ref/oggflacdec DECODING the same images, %d processes "
+         "at a time, same host, for scale only" % args.procs if ref_s
+         else "oracle/_ref/oggflacdec absent or skipped"))
+    text = json.dumps(doc, indent=1, sort_keys=True)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    ok = not any(bad.values()) and all(c["equal_to_port"] == len(c["tracks"])
+                                       for c in compared.values())
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tracks", type=int, default=1024)
@@ -70,8 +213,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--procs", type=int, default=16)
     ap.add_argument("--no-reference", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "oggflac_bench.json"))
+    ap.add_argument("--encode", action="store_true",
+                    help="measure the Ogg FLAC encoder instead (see the module text)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "oggflac_enc_bench.json" if args.encode
+                                else "oggflac_bench.json")
+    if args.encode:
+        return encode_main(args)
 
     import torch
     import oggflac_port as op
