@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 6
+#define ATG_ABI_VERSION 7
 
 typedef enum {
     ATG_OK = 0,
@@ -746,6 +746,70 @@ atg_status atg_pcm_convert_host(int device, int kind, const int32_t *in, int32_t
                                 uint64_t frames, uint32_t channels, uint32_t channel_mask,
                                 uint32_t in_bps, uint32_t out_bps, const uint8_t *dither,
                                 uint64_t dither_bytes, uint64_t dither_bit0);
+
+/* ------------------------------------------------------------------ */
+/* AccurateRip checksums (trackverify -R, cd2track).                    */
+/* Replaces audiotools._accuraterip.ChecksumV1 / ChecksumV2             */
+/* (src/accuraterip.c:121-326) for every track of a batch, and gives v1 */
+/* at every drive read offset in [-max_offset, max_offset].  Tracks are */
+/* stereo, 16 bits per sample, interleaved, in ATG_PCM_S16 or           */
+/* ATG_PCM_S32.  Stateless: no handle.                                  */
+/* ------------------------------------------------------------------ */
+#define ATG_AR_FIRST 1u /* atg_ar_track.flags: first track of the disc */
+#define ATG_AR_LAST 2u  /* last track of the disc */
+
+/* One track, or one piece of a track fed in pieces.  Frame i (from 1) has
+   the index index0 + i and the value (uint16(right) << 16) | uint16(left);
+   it counts when start <= index <= end, start = (sample_rate / 75) * 5 for
+   a first track (else 0), end = (uint32_t)(total_pcm_frames - that skip)
+   for a last track (else total_pcm_frames).  The cast wraps, as the
+   reference's does: a last track shorter than the skip has nothing cut.
+   At offset k frame i is read from frame position pcm_offset + k + i - 1 of
+   the buffer; positions outside [lo_frame, hi_frame) read as silence (the
+   track itself for separate files, the whole image for a disc image). */
+typedef struct {
+    int64_t pcm_offset;   /* buffer position of the track's first frame */
+    uint64_t pcm_frames;
+    uint64_t lo_frame, hi_frame;
+    uint32_t index0;           /* index of the first frame, minus 1 */
+    uint32_t total_pcm_frames; /* the range rule's length; pcm_frames unless
+                                  this is a piece of a longer track */
+    uint32_t sample_rate;
+    uint32_t flags;            /* ATG_AR_FIRST | ATG_AR_LAST */
+} atg_ar_track;
+
+typedef struct {
+    uint32_t v1, v2; /* at offset 0 */
+    int32_t status;  /* 0 */
+    uint32_t reserved;
+} atg_ar_result;
+
+const char *atg_accuraterip_last_error(void);
+
+/* Checksums of n_tracks tracks whose PCM is in device memory (16-byte
+   aligned, readable over every track's [lo_frame, hi_frame)).  offset_v1 is
+   a host array of n_tracks x (2 * max_offset + 1) values, v1 at offset k of
+   track t at [t * (2 * max_offset + 1) + max_offset + k]; it may be NULL
+   when max_offset is 0.  v2 is not linear in the offset and is given at
+   offset 0 only: submit the track again with pcm_offset + k for v2 there.
+   Checked before any GPU call, ATG_ERR_INVALID: NULL arrays with n_tracks
+   > 0, an unknown format, sample_rate 0, pcm_frames or total_pcm_frames 0,
+   lo_frame > hi_frame, index0 + pcm_frames >= 2^32; ATG_ERR_UNSUPPORTED:
+   max_offset above 65535.  Synchronises `stream` before it returns. */
+atg_status atg_accuraterip_device(const void *d_pcm, int format, const atg_ar_track *tracks,
+                                  uint32_t n_tracks, uint32_t max_offset,
+                                  atg_ar_result *results, uint32_t *offset_v1, void *stream);
+
+/* The same for PCM in host memory (pcm_frames_total frames), staged through
+   `device`; also ATG_ERR_INVALID for a hi_frame above pcm_frames_total. */
+atg_status atg_accuraterip_host(int device, const void *pcm, int format,
+                                uint64_t pcm_frames_total, const atg_ar_track *tracks,
+                                uint32_t n_tracks, uint32_t max_offset,
+                                atg_ar_result *results, uint32_t *offset_v1);
+
+/* PCM frames per tile of the streaming pass (tests place track lengths
+   around it). */
+uint32_t atg_accuraterip_tile_frames(void);
 
 /* ------------------------------------------------------------------ */
 /* ReplayGain analysis (tracktag/track2track --replay-gain).           */

@@ -81,6 +81,8 @@ EXPORTS = (
     "atg_shn_decoder_kernel_times",
     "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
+    "atg_accuraterip_last_error", "atg_accuraterip_device", "atg_accuraterip_host",
+    "atg_accuraterip_tile_frames",
 )
 
 CONV_BPS, CONV_DOWNMIX, CONV_AVERAGE = 0, 1, 2
@@ -243,6 +245,19 @@ class RgTrack(ctypes.Structure):
 class RgResult(ctypes.Structure):
     _fields_ = [("title_gain", ctypes.c_double), ("title_peak", ctypes.c_double),
                 ("status", c_i32), ("reserved", c_u32)]
+
+
+AR_FIRST, AR_LAST = 1, 2
+
+
+class ArTrack(ctypes.Structure):
+    _fields_ = [("pcm_offset", ctypes.c_int64), ("pcm_frames", c_u64),
+                ("lo_frame", c_u64), ("hi_frame", c_u64), ("index0", c_u32),
+                ("total_pcm_frames", c_u32), ("sample_rate", c_u32), ("flags", c_u32)]
+
+
+class ArResult(ctypes.Structure):
+    _fields_ = [("v1", c_u32), ("v2", c_u32), ("status", c_i32), ("reserved", c_u32)]
 
 
 class AlacOptions(ctypes.Structure):
@@ -594,6 +609,16 @@ def load_library():
             ctypes.c_int, ctypes.c_int, P, P, c_u64, c_u32, c_u32, c_u32, c_u32, P, c_u64,
             c_u64]
         lib.atg_pcm_convert_host.restype = ctypes.c_int
+        lib.atg_accuraterip_last_error.restype = ctypes.c_char_p
+        lib.atg_accuraterip_device.argtypes = [
+            P, ctypes.c_int, ctypes.POINTER(ArTrack), c_u32, c_u32, ctypes.POINTER(ArResult),
+            P, P]
+        lib.atg_accuraterip_device.restype = ctypes.c_int
+        lib.atg_accuraterip_host.argtypes = [
+            ctypes.c_int, P, ctypes.c_int, c_u64, ctypes.POINTER(ArTrack), c_u32, c_u32,
+            ctypes.POINTER(ArResult), P]
+        lib.atg_accuraterip_host.restype = ctypes.c_int
+        lib.atg_accuraterip_tile_frames.restype = c_u32
         lib.atg_replaygain_last_error.restype = ctypes.c_char_p
         lib.atg_replaygain_device.argtypes = [
             P, ctypes.POINTER(RgTrack), c_u32, c_u32, ctypes.POINTER(RgResult), P,
@@ -2303,6 +2328,51 @@ def replaygain_hist_gain_host(hists):
         return replaygain_hist_gain(d.value, n)
     finally:
         lib.atg_device_free(eng.handle, d)
+
+
+def ar_track(pcm_offset, pcm_frames, sample_rate=44100, is_first=False, is_last=False,
+             lo_frame=None, hi_frame=None, index0=0, total_pcm_frames=None):
+    """ArTrack of pcm_frames frames at frame position pcm_offset of the batch
+    buffer; the readable region defaults to the track itself"""
+    lo = max(0, pcm_offset) if lo_frame is None else lo_frame
+    hi = max(lo, pcm_offset + pcm_frames) if hi_frame is None else hi_frame
+    return ArTrack(pcm_offset, pcm_frames, lo, hi, index0,
+                   pcm_frames if total_pcm_frames is None else total_pcm_frames, sample_rate,
+                   (AR_FIRST if is_first else 0) | (AR_LAST if is_last else 0))
+
+
+def _ar_call(call, tracks, max_offset):
+    lib = load_library()
+    n = len(tracks)
+    arr = (ArTrack * max(1, n))(*tracks)
+    res = (ArResult * max(1, n))()
+    table = np.zeros((n, 2 * max_offset + 1), dtype=np.uint32)
+    st = call(lib, arr, n, res, table.ctypes.data_as(ctypes.c_void_p))
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_accuraterip_last_error().decode("utf-8", "replace"))
+    return [res[i] for i in range(n)], table
+
+
+def accuraterip_device(d_pcm, fmt, tracks, max_offset=0):
+    """AccurateRip checksums of a batch whose PCM (PCM_S16 / PCM_S32) is in
+    device memory (on the device that holds it).  tracks: list of ArTrack.
+    -> ([ArResult], uint32 array [track][k + max_offset] of v1 at offset k)"""
+    return _ar_call(lambda lib, arr, n, res, table: lib.atg_accuraterip_device(
+        ctypes.c_void_p(d_pcm), fmt, arr, n, max_offset, res, table, None), tracks, max_offset)
+
+
+def accuraterip_host(pcm, fmt, tracks, max_offset=0, device=None):
+    """the same for interleaved stereo PCM in host memory (int16 for PCM_S16,
+    int32 for PCM_S32), staged through `device`"""
+    a = np.ascontiguousarray(pcm, dtype=np.int16 if fmt == PCM_S16 else np.int32)
+    return _ar_call(lambda lib, arr, n, res, table: lib.atg_accuraterip_host(
+        default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p), fmt,
+        len(a) // 2, arr, n, max_offset, res, table), tracks, max_offset)
+
+
+def accuraterip_tile_frames():
+    """PCM frames per tile of the checksum's streaming pass"""
+    return int(load_library().atg_accuraterip_tile_frames())
 
 
 def apply_gain(pcm, channels, bits_per_sample, multiplier, chunk_frames, dither,
