@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 7
+#define ATG_ABI_VERSION 8
 
 typedef enum {
     ATG_OK = 0,
@@ -810,6 +810,132 @@ atg_status atg_accuraterip_host(int device, const void *pcm, int format,
 /* PCM frames per tile of the streaming pass (tests place track lengths
    around it). */
 uint32_t atg_accuraterip_tile_frames(void);
+
+/* ------------------------------------------------------------------ */
+/* Packed PCM bytes <-> integer PCM, and the AIFF / Sun AU containers.  */
+/* The ten byte layouts of the reference's FrameList(bytes, ...) and    */
+/* FrameList.to_bytes (src/pcm.c, converters src/pcmconv.c): 1, 2 or 3  */
+/* bytes per sample, little or big endian, signed or unsigned (an       */
+/* unsigned sample's value is raw - 2^(bits-1)).  Stateless: no handle. */
+/* ------------------------------------------------------------------ */
+typedef struct {
+    uint8_t bytes_per_sample; /* 1, 2 or 3 */
+    uint8_t big_endian;       /* ignored for 1 byte per sample */
+    uint8_t is_signed;
+    uint8_t reserved;
+} atg_pcm_layout;
+
+/* `samples` packed samples from byte `byte_offset` of the packed buffer
+   (any offset) <-> the samples from index `sample_offset` of the integer
+   buffer.  Runs of one call must not overlap on the side written. */
+typedef struct {
+    uint64_t byte_offset, samples, sample_offset;
+} atg_pcm_run;
+
+const char *atg_pcm_bytes_last_error(void);
+
+/* Unpack every run of d_bytes (device memory) into d_pcm, interleaved int16
+   (ATG_PCM_S16, layouts of at most 2 bytes) or int32.  One launch for the
+   whole table.  Memory contract: the kernel reads only aligned 16-byte
+   units of d_bytes that hold at least one byte of some run, so d_bytes must
+   be 16-byte aligned and bytes_cap a multiple of 16; it writes d_pcm in
+   16-byte groups inside the runs' sample ranges, so d_pcm must be 16-byte
+   aligned and every sample_offset a multiple of 16 / sizeof(sample).
+   Checked before any GPU call, ATG_ERR_INVALID: NULL arrays with n_runs >
+   0, bytes_per_sample outside 1..3, ATG_PCM_S16 with 3 bytes per sample, an
+   unknown format, a misaligned buffer, capacity or sample_offset;
+   ATG_ERR_CAPACITY: a run whose packed range passes bytes_cap or whose
+   sample range passes pcm_cap_samples.  Nothing is launched for n_runs ==
+   0 or when every run is empty.  `stream` is a hipStream_t (NULL = default
+   stream); it is synchronised before the call returns. */
+atg_status atg_pcm_unpack_device(const void *d_bytes, uint64_t bytes_cap, atg_pcm_layout layout,
+                                 const atg_pcm_run *runs, uint32_t n_runs, void *d_pcm,
+                                 atg_pcm_format format, uint64_t pcm_cap_samples, void *stream);
+
+/* The inverse: d_pcm's runs packed into d_bytes, each value (plus 2^(bits-1)
+   when unsigned) masked to the layout's width as FrameList.to_bytes masks
+   it.  The kernel writes only bytes inside a run's packed range and never
+   reads the packed buffer, so runs may sit back to back at odd offsets; it
+   reads only the runs' own samples.  d_bytes must be 16-byte aligned and
+   d_pcm aligned to its sample size; sample_offset may be any.  The other
+   checks are those of atg_pcm_unpack_device. */
+atg_status atg_pcm_pack_device(const void *d_pcm, atg_pcm_format format, uint64_t pcm_cap_samples,
+                               atg_pcm_layout layout, const atg_pcm_run *runs, uint32_t n_runs,
+                               void *d_bytes, uint64_t bytes_cap, void *stream);
+
+/* The same for host buffers of any alignment, staged through `device`: only
+   the runs' ranges of the output buffer are written. */
+atg_status atg_pcm_unpack_host(int device, const void *bytes, uint64_t n_bytes,
+                               atg_pcm_layout layout, const atg_pcm_run *runs, uint32_t n_runs,
+                               void *pcm, atg_pcm_format format, uint64_t pcm_cap_samples);
+atg_status atg_pcm_pack_host(int device, const void *pcm, atg_pcm_format format,
+                             uint64_t pcm_cap_samples, atg_pcm_layout layout,
+                             const atg_pcm_run *runs, uint32_t n_runs, void *bytes,
+                             uint64_t n_bytes);
+
+/* Samples per tile of both kernels (tests place run lengths around it). */
+uint32_t atg_pcm_bytes_tile_samples(void);
+
+/* Name and milliseconds of the calling thread's last launch ("unpack" or
+   "pack"); returns the number of entries written, 0 before any launch. */
+int atg_pcm_bytes_kernel_times(const char **names, float *ms, int cap);
+
+/* Status bit of a file decoded by the batch PCM reader: the file holds fewer
+   data bytes than its header says; the PCM is the whole frames present. */
+#define ATG_PCMF_TRUNCATED 1
+
+/* atg_aiff_read_info: 0, or one of these for the reference's errors
+   (audiotools/text.py:530-545, those AiffReader.__init__ can raise), or
+   ATG_ERR_UNSUPPORTED for a bits_per_sample other than 8, 16 or 24 or a
+   sample rate outside [0, 2^32), ATG_ERR_INVALID for a NULL argument. */
+enum {
+    ATG_AIFF_OK = 0,
+    ATG_AIFF_NOT_AIFF = 1,         /* "not an AIFF file" */
+    ATG_AIFF_INVALID_AIFF = 2,     /* "invalid AIFF file" */
+    ATG_AIFF_INVALID_CHUNK_ID = 3, /* "invalid AIFF chunk ID" */
+    ATG_AIFF_INVALID_CHUNK = 4,    /* "invalid AIFF chunk": pad byte missing */
+    ATG_AIFF_PREMATURE_SSND = 5,   /* "SSND chunk found before fmt", and no
+                                      COMM chunk after it */
+    ATG_AIFF_NO_SSND = 6,          /* "SSND chunk not found" */
+    ATG_AIFF_IOERROR = 7           /* the file ends inside the COMM fields */
+};
+
+typedef struct {
+    uint32_t channels;
+    uint32_t bits_per_sample;
+    uint32_t sample_rate;  /* the 80-bit extended field, truncated */
+    uint32_t channel_mask; /* 0x4 for 1 channel, 0x3 for 2, otherwise 0 */
+    uint64_t total_pcm_frames;
+    uint64_t ssnd_data_offset; /* first sound byte: after SSND's two words */
+    uint64_t ssnd_data_bytes;  /* the chunk's sound bytes present in the image */
+} atg_aiff_info;
+
+/* Walks the chunks of a whole file image up to SSND, as the reference's
+   AiffReader does; an SSND chunk met before COMM is kept and the walk goes on
+   to COMM (the reference refuses such a file).  ssnd_data_offset +
+   ssnd_data_bytes <= len always. */
+int atg_aiff_read_info(const uint8_t *data, uint64_t len, atg_aiff_info *info);
+
+/* atg_au_read_info: 0, one of these (text.py:547-548), ATG_ERR_UNSUPPORTED
+   for a header with no channels, ATG_ERR_INVALID for a NULL argument. */
+enum {
+    ATG_AU_OK = 0,
+    ATG_AU_INVALID_HEADER = 1,     /* "invalid Sun AU header" */
+    ATG_AU_UNSUPPORTED_FORMAT = 2, /* "unsupported Sun AU format" */
+    ATG_AU_IOERROR = 3             /* fewer than the header's 24 bytes */
+};
+
+typedef struct {
+    uint32_t channels;
+    uint32_t bits_per_sample; /* encodings 2, 3, 4 -> 8, 16, 24 */
+    uint32_t sample_rate;
+    uint32_t channel_mask;
+    uint64_t total_pcm_frames; /* data_size / bytes per frame */
+    uint64_t data_offset, data_size; /* as the header states them */
+    uint64_t data_bytes; /* of data_size, those present in the image */
+} atg_au_info;
+
+int atg_au_read_info(const uint8_t *data, uint64_t len, atg_au_info *info);
 
 /* ------------------------------------------------------------------ */
 /* ReplayGain analysis (tracktag/track2track --replay-gain).           */

@@ -594,6 +594,8 @@ def calculate_replay_gain(tracks, progress=None):
 # the format classes (their modules import the names above)
 from .flac import FlacAudio, InvalidFLAC, OggFlacAudio  # noqa: E402,F401
 from .wav import WaveAudio, InvalidWave  # noqa: E402,F401
+from .aiff import AiffAudio, InvalidAIFF  # noqa: E402,F401
+from .au import AuAudio, InvalidAU  # noqa: E402,F401
 from .m4a import ALACAudio, InvalidALAC  # noqa: E402,F401
 from .tta import TrueAudio, InvalidTTA  # noqa: E402,F401
 from .wavpack import WavPackAudio, InvalidWavPack  # noqa: E402,F401

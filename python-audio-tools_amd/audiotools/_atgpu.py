@@ -83,6 +83,9 @@ EXPORTS = (
     "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
     "atg_accuraterip_last_error", "atg_accuraterip_device", "atg_accuraterip_host",
     "atg_accuraterip_tile_frames",
+    "atg_pcm_bytes_last_error", "atg_pcm_unpack_device", "atg_pcm_pack_device",
+    "atg_pcm_unpack_host", "atg_pcm_pack_host", "atg_pcm_bytes_tile_samples",
+    "atg_pcm_bytes_kernel_times", "atg_aiff_read_info", "atg_au_read_info",
 )
 
 CONV_BPS, CONV_DOWNMIX, CONV_AVERAGE = 0, 1, 2
@@ -444,6 +447,45 @@ WVD_MESSAGES = {1: "I/O error", 3: "invalid block header ID", 4: "invalid reserv
 WV_INITIAL, WV_FINAL = 1 << 11, 1 << 12
 
 
+class PcmLayout(ctypes.Structure):
+    """atg_pcm_layout: how a packed sample lies in its bytes"""
+    _fields_ = [("bytes_per_sample", ctypes.c_uint8), ("big_endian", ctypes.c_uint8),
+                ("is_signed", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class PcmRun(ctypes.Structure):
+    """atg_pcm_run: samples at byte_offset of the packed buffer <-> the
+    samples from sample_offset of the integer buffer"""
+    _fields_ = [("byte_offset", c_u64), ("samples", c_u64), ("sample_offset", c_u64)]
+
+
+class AiffInfo(ctypes.Structure):
+    _fields_ = [("channels", c_u32), ("bits_per_sample", c_u32), ("sample_rate", c_u32),
+                ("channel_mask", c_u32), ("total_pcm_frames", c_u64),
+                ("ssnd_data_offset", c_u64), ("ssnd_data_bytes", c_u64)]
+
+
+class AuInfo(ctypes.Structure):
+    _fields_ = [("channels", c_u32), ("bits_per_sample", c_u32), ("sample_rate", c_u32),
+                ("channel_mask", c_u32), ("total_pcm_frames", c_u64), ("data_offset", c_u64),
+                ("data_size", c_u64), ("data_bytes", c_u64)]
+
+
+PCMF_TRUNCATED = 1
+(AIFF_OK, AIFF_NOT_AIFF, AIFF_INVALID_AIFF, AIFF_INVALID_CHUNK_ID, AIFF_INVALID_CHUNK,
+ AIFF_PREMATURE_SSND, AIFF_NO_SSND, AIFF_IOERROR) = range(8)
+AIFF_ERRORS = {AIFF_NOT_AIFF: "not an AIFF file", AIFF_INVALID_AIFF: "invalid AIFF file",
+               AIFF_INVALID_CHUNK_ID: "invalid AIFF chunk ID",
+               AIFF_INVALID_CHUNK: "invalid AIFF chunk",
+               AIFF_PREMATURE_SSND: "SSND chunk found before fmt",
+               AIFF_NO_SSND: "SSND chunk not found",
+               AIFF_IOERROR: "I/O error reading COMM chunk"}
+AU_OK, AU_INVALID_HEADER, AU_UNSUPPORTED_FORMAT, AU_IOERROR = range(4)
+AU_ERRORS = {AU_INVALID_HEADER: "invalid Sun AU header",
+             AU_UNSUPPORTED_FORMAT: "unsupported Sun AU format",
+             AU_IOERROR: "I/O error reading Sun AU header"}
+
+
 class ATGError(RuntimeError):
     """failure reported by libatgpu (status code + message)"""
 
@@ -619,6 +661,28 @@ def load_library():
             ctypes.POINTER(ArResult), P]
         lib.atg_accuraterip_host.restype = ctypes.c_int
         lib.atg_accuraterip_tile_frames.restype = c_u32
+        lib.atg_pcm_bytes_last_error.restype = ctypes.c_char_p
+        lib.atg_pcm_unpack_device.argtypes = [
+            P, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, ctypes.c_int, c_u64, P]
+        lib.atg_pcm_unpack_device.restype = ctypes.c_int
+        lib.atg_pcm_pack_device.argtypes = [
+            P, ctypes.c_int, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, c_u64, P]
+        lib.atg_pcm_pack_device.restype = ctypes.c_int
+        lib.atg_pcm_unpack_host.argtypes = [
+            ctypes.c_int, P, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, ctypes.c_int,
+            c_u64]
+        lib.atg_pcm_unpack_host.restype = ctypes.c_int
+        lib.atg_pcm_pack_host.argtypes = [
+            ctypes.c_int, P, ctypes.c_int, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P,
+            c_u64]
+        lib.atg_pcm_pack_host.restype = ctypes.c_int
+        lib.atg_pcm_bytes_tile_samples.restype = c_u32
+        lib.atg_pcm_bytes_kernel_times.argtypes = [P, P, ctypes.c_int]
+        lib.atg_pcm_bytes_kernel_times.restype = ctypes.c_int
+        lib.atg_aiff_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AiffInfo)]
+        lib.atg_aiff_read_info.restype = ctypes.c_int
+        lib.atg_au_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AuInfo)]
+        lib.atg_au_read_info.restype = ctypes.c_int
         lib.atg_replaygain_last_error.restype = ctypes.c_char_p
         lib.atg_replaygain_device.argtypes = [
             P, ctypes.POINTER(RgTrack), c_u32, c_u32, ctypes.POINTER(RgResult), P,
@@ -2373,6 +2437,99 @@ def accuraterip_host(pcm, fmt, tracks, max_offset=0, device=None):
 def accuraterip_tile_frames():
     """PCM frames per tile of the checksum's streaming pass"""
     return int(load_library().atg_accuraterip_tile_frames())
+
+
+# ------------------------------------------------- packed PCM bytes (pcm_bytes.hip)
+def pcm_layout(bytes_per_sample, big_endian, is_signed):
+    return PcmLayout(bytes_per_sample, 1 if big_endian else 0, 1 if is_signed else 0, 0)
+
+
+def pcm_runs(runs):
+    """[(byte_offset, samples, sample_offset)] -> (PcmRun array, count)"""
+    runs = list(runs)
+    arr = (PcmRun * max(1, len(runs)))()
+    for i, (b, n, s) in enumerate(runs):
+        arr[i].byte_offset, arr[i].samples, arr[i].sample_offset = b, n, s
+    return arr, len(runs)
+
+
+def _pb_check(lib, st):
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_pcm_bytes_last_error().decode("utf-8", "replace"))
+
+
+def pcm_unpack_device(d_bytes, bytes_cap, layout, runs, d_pcm, fmt, pcm_cap_samples):
+    """packed bytes in device memory -> interleaved int16 (PCM_S16) or int32
+    (PCM_S32) in device memory, one launch for all runs (atg_pcm_unpack_device);
+    runs: [(byte_offset, samples, sample_offset)] or a pcm_runs() pair"""
+    lib = load_library()
+    arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
+    _pb_check(lib, lib.atg_pcm_unpack_device(
+        ctypes.c_void_p(d_bytes), bytes_cap, layout, arr, n, ctypes.c_void_p(d_pcm), fmt,
+        pcm_cap_samples, None))
+
+
+def pcm_pack_device(d_pcm, fmt, pcm_cap_samples, layout, runs, d_bytes, bytes_cap):
+    """the inverse (atg_pcm_pack_device): only the runs' packed bytes are written"""
+    lib = load_library()
+    arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
+    _pb_check(lib, lib.atg_pcm_pack_device(
+        ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, layout, arr, n, ctypes.c_void_p(d_bytes),
+        bytes_cap, None))
+
+
+def pcm_unpack_host(data, layout, runs, out, device=None):
+    """packed bytes in host memory (bytes or uint8 array) -> the runs' sample
+    ranges of `out` (int16 or int32 numpy array), staged through `device`"""
+    lib = load_library()
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
+    fmt = PCM_S16 if out.dtype == np.int16 else PCM_S32
+    _pb_check(lib, lib.atg_pcm_unpack_host(
+        default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
+        a.nbytes, layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, len(out)))
+    return out
+
+
+def pcm_pack_host(pcm, layout, runs, out, device=None):
+    """int16 / int32 samples in host memory -> the runs' byte ranges of the
+    uint8 array `out`, staged through `device`"""
+    lib = load_library()
+    a = np.ascontiguousarray(pcm)
+    arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
+    fmt = PCM_S16 if a.dtype == np.int16 else PCM_S32
+    _pb_check(lib, lib.atg_pcm_pack_host(
+        default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p), fmt,
+        len(a), layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+    return out
+
+
+def pcm_bytes_tile_samples():
+    """samples per tile of the pack / unpack kernels"""
+    return int(load_library().atg_pcm_bytes_tile_samples())
+
+
+def pcm_bytes_kernel_times():
+    """{"unpack" or "pack": ms} of this thread's last launch"""
+    lib = load_library()
+    names = (ctypes.c_char_p * 1)()
+    ms = (ctypes.c_float * 1)()
+    k = lib.atg_pcm_bytes_kernel_times(names, ms, 1)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+def aiff_read_info(data):
+    """(status, AiffInfo) of a whole AIFF file image (atg_aiff_read_info)"""
+    info = AiffInfo()
+    data = bytes(data)
+    return int(load_library().atg_aiff_read_info(data, len(data), ctypes.byref(info))), info
+
+
+def au_read_info(data):
+    """(status, AuInfo) of a whole Sun AU file image (atg_au_read_info)"""
+    info = AuInfo()
+    data = bytes(data)
+    return int(load_library().atg_au_read_info(data, len(data), ctypes.byref(info))), info
 
 
 def apply_gain(pcm, channels, bits_per_sample, multiplier, chunk_frames, dither,

@@ -35,7 +35,9 @@ src/decoders/tta.c; GPU kernels tta_decode.hip), `SHNDecoder` /
 `decode_wavpack_batch` for WavPack (reference src/decoders/wavpack.c; GPU
 kernels wavpack_decode.hip), `OggFlacDecoder` / `decode_oggflac_batch` for
 Ogg FLAC (src/ogg.c, src/decoders/oggflac.c; ogg_demux.hip and
-flac_decode.hip).
+flac_decode.hip).  `decode_pcm_batch` reads the uncompressed containers (RIFF
+WAVE, AIFF, Sun AU) in a batch, their samples unpacked on the GPU
+(pcm_bytes.hip).
 There is no CPU decoding path.
 """
 
@@ -638,6 +640,38 @@ def decode_wavpack_batch(images, md5_mode=1):
                     pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * info.channels],
                     bad))
     return out
+
+
+# ------------------------------------------- uncompressed: WAV, AIFF, Sun AU
+def decode_pcm_batch(images):
+    """a list of RIFF WAVE, AIFF or Sun AU file images (bytes), told apart by
+    magic and mixed freely, to integer PCM in one GPU batch: the headers are
+    read on the host (wav.py's parser, atg_aiff_read_info, atg_au_read_info),
+    the data chunks go up as they lie in the files, and one launch per sample
+    layout unpacks them on the device (pcm_bytes.hip).
+    -> list of (status, PcmImage, int32 interleaved PCM, frames); status is 0,
+    or ATG_PCMF_TRUNCATED when the file holds fewer data bytes than its header
+    says: the PCM is then the whole frames present.  A header error raises
+    what the file's single-file reader raises."""
+    from . import pcmfiles
+    images = [bytes(i) for i in images]
+    infos = [pcmfiles.image_info(i) for i in images]
+    if not infos:
+        return []
+    runs, cap, n_samples = pcmfiles.plan(infos, 4)
+    eng = _atgpu.engine()
+    out = np.zeros(max(n_samples, 4), dtype=np.int32)
+    d_bytes = eng.device_alloc(max(cap, 16))
+    d_pcm = eng.device_alloc(out.nbytes)
+    try:
+        eng.copy_to_device(d_bytes, pcmfiles.gather(images, infos, cap))
+        pcmfiles.unpack_groups(infos, runs, d_bytes, cap, d_pcm, _atgpu.PCM_S32, len(out))
+        eng.copy_to_host(out, d_pcm)
+    finally:
+        eng.device_free(d_bytes)
+        eng.device_free(d_pcm)
+    return [(_atgpu.PCMF_TRUNCATED if i.frames < i.total_pcm_frames else 0, i,
+             out[slot:slot + n], i.frames) for i, (_, n, slot) in zip(infos, runs)]
 
 
 # -------------------------------------------------------------- Ogg FLAC

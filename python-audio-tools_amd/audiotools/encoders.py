@@ -46,6 +46,12 @@ src/encoders/tta.c:31-114; GPU kernels tta_encode.hip), `encode_shn` /
 
 `encode_wavpack` / `encode_wavpack_batch` do the same for WavPack (reference
 src/encoders/wavpack.c; GPU kernels wavpack_encode.hip): complete .wv files.
+
+`encode_aiff_batch` / `encode_au_batch` write AIFF / Sun AU files whose
+big-endian samples are packed on the GPU (pcm_bytes.hip), the files of
+AiffAudio.from_pcm / AuAudio.from_pcm; `encode_flac_files_batch` encodes
+WAV / AIFF / AU files to FLAC with their data chunks uploaded as they lie on
+disk and unpacked on the device.
 """
 
 import numpy as np
@@ -471,3 +477,191 @@ def encode_wavpack(filename, pcmreader, block_size, total_pcm_frames=0, false_st
     encode_wavpack_batch([filename], [pcmreader], block_size, total_pcm_frames, false_stereo,
                          wasted_bits, joint_stereo, correlation_passes, wave_header,
                          wave_footer)
+
+
+# ------------------------------------------- uncompressed: AIFF, Sun AU, files
+def _pack_batch(filenames, pcmreaders, check, finish):
+    """what encode_aiff_batch and encode_au_batch share: the readers drained
+    as _collect drains them, their samples uploaded as integers, packed big
+    endian on the device (pcm_bytes.hip) and the packed image brought down at
+    1 to 3 bytes per sample; finish(file object, reader, frames, data bytes)
+    writes each file.  Readers of one batch may differ in every parameter."""
+    from . import EncodingError, FRAMELIST_SIZE
+    filenames = list(filenames)
+    pcmreaders = list(pcmreaders)
+    if len(filenames) != len(pcmreaders):
+        raise ValueError("filenames and pcmreaders differ in length")
+    for name, r in zip(filenames, pcmreaders):
+        check(name, r)
+    drained = []
+    for r in pcmreaders:
+        try:
+            samples, _ = _collect(r, FRAMELIST_SIZE)
+        except (IOError, ValueError) as err:
+            raise EncodingError(str(err))
+        drained.append(samples)
+    eng = _atgpu.engine()
+    packed = [None] * len(pcmreaders)
+    # one launch per sample width; up to 16 bits the samples go up as int16
+    for width in (1, 2, 3):
+        idx = [k for k, r in enumerate(pcmreaders) if r.bits_per_sample // 8 == width]
+        if not idx:
+            continue
+        dtype, fmt = (np.int32, _atgpu.PCM_S32) if width == 3 else (np.int16, _atgpu.PCM_S16)
+        group = 16 // np.dtype(dtype).itemsize
+        runs, pos, slot = [], 0, 0
+        for k in idx:
+            n = len(drained[k])
+            runs.append((pos, n, slot))
+            pos += n * width
+            slot += (n + group - 1) // group * group
+        if not pos:
+            for k in idx:
+                packed[k] = np.zeros(0, dtype=np.uint8)
+            continue
+        pcm = np.zeros(slot, dtype=dtype)
+        for k, (_, n, s) in zip(idx, runs):
+            pcm[s:s + n] = drained[k]
+        out = np.empty(pos, dtype=np.uint8)
+        d_pcm, d_bytes = eng.device_alloc(pcm.nbytes), eng.device_alloc(pos)
+        try:
+            eng.copy_to_device(d_pcm, pcm)
+            _atgpu.pcm_pack_device(d_pcm, fmt, slot, _atgpu.pcm_layout(width, True, True), runs,
+                                   d_bytes, pos)
+            eng.copy_to_host(out, d_bytes)
+        finally:
+            eng.device_free(d_pcm)
+            eng.device_free(d_bytes)
+        for k, (off, n, _) in zip(idx, runs):
+            packed[k] = out[off:off + n * width]
+    for name, r, data in zip(filenames, pcmreaders, packed):
+        try:
+            with open(name, "wb") as f:
+                finish(f, r, len(data) // (r.channels * (r.bits_per_sample // 8)), data)
+        except IOError as err:
+            raise EncodingError(str(err))
+    for r in pcmreaders:
+        r.close()
+
+
+def _check_bits(name, r):
+    if r.bits_per_sample not in (8, 16, 24):
+        from .m4a import UnsupportedBitsPerSample
+        raise UnsupportedBitsPerSample(name, r.bits_per_sample)
+
+
+def encode_aiff_batch(filenames, pcmreaders):
+    """several PCMReaders -> one AIFF file each, the samples packed on the GPU
+    in one batch; the files are those AiffAudio.from_pcm writes"""
+    from . import EncodingError
+    from .aiff import aiff_header, ERR_AIFF_TOO_LARGE
+
+    def finish(f, r, frames, data):
+        data_size = 8 + len(data)
+        if 4 + 8 + 18 + 8 + data_size + data_size % 2 >= (1 << 32):
+            raise EncodingError(ERR_AIFF_TOO_LARGE)
+        f.write(aiff_header(r.sample_rate, r.channels, r.bits_per_sample, frames, data_size))
+        f.write(memoryview(data))
+        if data_size % 2:
+            f.write(b"\0")
+
+    _pack_batch(filenames, pcmreaders, _check_bits, finish)
+
+
+def encode_au_batch(filenames, pcmreaders):
+    """several PCMReaders -> one Sun AU file each, the samples packed on the
+    GPU in one batch; the files are those AuAudio.from_pcm writes"""
+    from . import EncodingError
+    from .au import au_header, ERR_AU_TOO_LARGE
+
+    def finish(f, r, frames, data):
+        if len(data) >= (1 << 32):
+            raise EncodingError(ERR_AU_TOO_LARGE)
+        f.write(au_header(len(data), r.bits_per_sample, r.sample_rate, r.channels))
+        f.write(memoryview(data))
+
+    _pack_batch(filenames, pcmreaders, _check_bits, finish)
+
+
+def encode_flac_files_batch(filenames, sources, block_size, max_lpc_order,
+                            min_residual_partition_order, max_residual_partition_order,
+                            mid_side=0, adaptive_mid_side=0, exhaustive_model_search=0,
+                            disable_verbatim_subframes=0, disable_constant_subframes=0,
+                            disable_fixed_subframes=0, disable_lpc_subframes=0,
+                            padding_size=4096):
+    """WaveAudio / AiffAudio / AuAudio objects (same channels / bits / rate) ->
+    one .flac file each, the PCM never unpacked on the host: the files' data
+    chunks are uploaded as they lie on disk (1 to 3 bytes per sample),
+    unpacked on the device (pcm_bytes.hip) into the engine's int16 / int32
+    container and encoded from there, the tracks sharded over the node's GPUs
+    as encode_flac_batch shards them.  The files are those
+    encode_flac_batch(filenames, [s.to_pcm() for s in sources], ...) writes.
+    Returns one (bytes written, pcm frames) per file; IOError with the
+    reader's message for a file whose data ends early."""
+    from . import pcmfiles
+    filenames = list(filenames)
+    sources = list(sources)
+    if len(filenames) != len(sources):
+        raise ValueError("filenames and sources differ in length")
+    if not sources:
+        return []
+    images, infos = [], []
+    for s in sources:
+        with open(s.filename, "rb") as f:
+            images.append(f.read())
+        infos.append(pcmfiles.image_info(images[-1]))
+        if infos[-1].frames < infos[-1].total_pcm_frames:
+            raise IOError(pcmfiles.TRUNCATED[infos[-1].kind])
+    i0 = infos[0]
+    channels, bps, rate = i0.channels, i0.bits_per_sample, i0.sample_rate
+    for i in infos:
+        if (i.channels, i.bits_per_sample, i.sample_rate) != (channels, bps, rate):
+            raise ValueError("all sources of a batch must share channels, "
+                             "bits-per-sample and sample rate")
+    files = [open(fn, "wb") for fn in filenames]
+    try:
+        opts = _atgpu.make_options(block_size, max_lpc_order, min_residual_partition_order,
+                                   max_residual_partition_order, mid_side, adaptive_mid_side,
+                                   exhaustive_model_search, disable_verbatim_subframes,
+                                   disable_constant_subframes, disable_fixed_subframes,
+                                   disable_lpc_subframes, padding_size)
+        fmt, dtype = ((_atgpu.PCM_S16, np.int16) if bps <= 16 else (_atgpu.PCM_S32, np.int32))
+        devs = _atgpu.batch_devices()
+        ranges = (_atgpu.shard_ranges([i.frames for i in infos], len(devs))
+                  if len(devs) > 1 else [(0, len(infos))])
+
+        def shard(k):
+            t0, t1 = ranges[k]
+            eng = (_atgpu.engine() if len(ranges) == 1
+                   else _atgpu.shard_object("engine", k, devs[k]))
+            part = infos[t0:t1]
+            # every track's first frame on a 16-byte boundary of the container
+            runs, cap, n_samples = pcmfiles.plan(part, 8 * channels)
+            tracks = [(slot // channels, i.frames, None) for i, (_, _, slot) in zip(part, runs)]
+            _, nb = eng.bounds(opts, tracks, channels, bps)
+            out = np.empty(max(1, nb), dtype=np.uint8)
+            bufs = []
+            try:
+                for nbytes in (max(cap, 16), max(16, n_samples * np.dtype(dtype).itemsize),
+                               max(16, nb)):
+                    bufs.append(eng.device_alloc(nbytes))
+                d_bytes, d_pcm, d_out = bufs
+                eng.copy_to_device(d_bytes, pcmfiles.gather(images[t0:t1], part, cap))
+                pcmfiles.unpack_groups(part, runs, d_bytes, cap, d_pcm, fmt, n_samples)
+                results = eng.encode_device(opts, d_pcm, fmt, tracks, channels, bps, rate,
+                                            d_out, nb)
+                eng.copy_to_host(out, d_out)
+            finally:
+                for d in bufs:
+                    eng.device_free(d)
+            return out, results
+
+        written = []
+        for (t0, t1), (out, results) in zip(ranges, _atgpu.run_shards(shard, len(ranges))):
+            for f, res, i in zip(files[t0:t1], results, infos[t0:t1]):
+                f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+                written.append((int(res.bytes), i.frames))
+        return written
+    finally:
+        for f in files:
+            f.close()
