@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 8
+#define ATG_ABI_VERSION 9
 
 typedef enum {
     ATG_OK = 0,
@@ -936,6 +936,83 @@ typedef struct {
 } atg_au_info;
 
 int atg_au_read_info(const uint8_t *data, uint64_t len, atg_au_info *info);
+
+/* ------------------------------------------------------------------ */
+/* PCM comparison (trackcmp) and offset search.                         */
+/* Replaces pcm_frame_cmp over two decoded streams (trackcmp's          */
+/* cmp_files) and over PCMReaderWindow views of a CD image (its         */
+/* image_compare) for every pair of a batch, and finds the frame shift  */
+/* at which two streams hold the same audio.  Stateless: no handle.     */
+/* ------------------------------------------------------------------ */
+#define ATG_PCM_NO_MISMATCH UINT64_MAX
+
+/* A view: an infinite sequence of PCM frames over a finite source.  View
+   frame i is source frame window_offset + i; source frames outside
+   [0, src_frames) are silence (every channel 0).  The source's samples are
+   d_pcm[sample_offset .. sample_offset + src_frames * channels), channel-
+   interleaved int16 or int32. */
+typedef struct {
+    const void *d_pcm;      /* device memory, aligned to its sample size */
+    uint64_t sample_offset; /* index in d_pcm of the source's first sample */
+    uint64_t src_frames;    /* PCM frames the source holds */
+    int64_t window_offset;  /* source frame of view frame 0; may be negative */
+    uint32_t format;        /* ATG_PCM_S16 / ATG_PCM_S32 */
+    uint32_t reserved;
+} atg_pcm_view;
+
+/* `frames` frames of view a against view b, both of `channels` channels;
+   the two formats are independent and an int16 sample is compared by its
+   sign-extended value. */
+typedef struct {
+    atg_pcm_view a, b;
+    uint64_t frames;
+    uint32_t channels, reserved;
+} atg_pcm_pair;
+
+typedef struct {
+    uint64_t first_mismatch; /* smallest i in [0, frames) at which any channel
+                                differs, or ATG_PCM_NO_MISMATCH */
+    int32_t offset;          /* the search's shift k: a(i) == b(i + k) */
+    uint32_t offset_found;
+} atg_pcm_cmp_result;
+
+const char *atg_pcm_compare_last_error(void);
+
+/* first_mismatch of every pair, one launch for the whole table; offset and
+   offset_found are set to 0.  Memory contract: the kernel reads only
+   aligned 16-byte units that hold at least one sample of a view's source
+   range [sample_offset, sample_offset + src_frames * channels); buffers
+   need only be aligned to their sample size, and a and b may share one.
+   Checked before any GPU call, ATG_ERR_INVALID: NULL arrays with n_pairs >
+   0, an unknown format, d_pcm NULL with src_frames > 0, a pointer off its
+   sample size, channels == 0, frames * channels or src_frames * channels at
+   or above 2^62, a source that ends at or beyond sample 2^62,
+   |window_offset| at or above 2^62; ATG_ERR_UNSUPPORTED: channels > 8.
+   Nothing is launched for n_pairs == 0 or when every pair has frames == 0
+   (an empty pair has no mismatch).  `stream` is a hipStream_t (NULL =
+   default stream); it is synchronised before the call returns. */
+atg_status atg_pcm_compare_device(const atg_pcm_pair *pairs, uint32_t n_pairs,
+                                  atg_pcm_cmp_result *results, void *stream);
+
+/* With S = { k in [-max_offset, max_offset] : a(i) == b(i + k) for every i in
+   [0, frames) }, b read at any index with silence outside its source:
+   offset is the k in S of smallest |k| (of +k and -k the positive one) and
+   offset_found says whether S has any; first_mismatch is the one at shift
+   0.  An empty pair gives offset_found = 1, offset = 0.  The checks are
+   those of atg_pcm_compare_device, and ATG_ERR_UNSUPPORTED for max_offset
+   above 65535.  At most 2 * max_offset + 1 shifts are verified per pair. */
+atg_status atg_pcm_offset_search_device(const atg_pcm_pair *pairs, uint32_t n_pairs,
+                                        uint32_t max_offset, atg_pcm_cmp_result *results,
+                                        void *stream);
+
+/* PCM frames per tile of the compare pass (tests place lengths around it). */
+uint32_t atg_pcm_compare_tile_frames(void);
+
+/* Milliseconds the calling thread's last call spent in its kernels:
+   "compare" (every compare launch of the call) and "probe" (the search's
+   shift probe); returns the number of entries written, 0 before any call
+   that launched. */
+int atg_pcm_compare_kernel_times(const char **names, float *ms, int cap);
 
 /* ------------------------------------------------------------------ */
 /* ReplayGain analysis (tracktag/track2track --replay-gain).           */

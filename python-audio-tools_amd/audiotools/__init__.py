@@ -600,3 +600,6 @@ from .m4a import ALACAudio, InvalidALAC  # noqa: E402,F401
 from .tta import TrueAudio, InvalidTTA  # noqa: E402,F401
 from .wavpack import WavPackAudio, InvalidWavPack  # noqa: E402,F401
 from .shn import ShortenAudio, InvalidShorten  # noqa: E402,F401
+from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa: E402,F401
+                       frame_cmp_value, compare_files_batch, compare_image_batch,
+                       find_offset_batch, compare_pcm_batch)

@@ -86,6 +86,8 @@ EXPORTS = (
     "atg_pcm_bytes_last_error", "atg_pcm_unpack_device", "atg_pcm_pack_device",
     "atg_pcm_unpack_host", "atg_pcm_pack_host", "atg_pcm_bytes_tile_samples",
     "atg_pcm_bytes_kernel_times", "atg_aiff_read_info", "atg_au_read_info",
+    "atg_pcm_compare_last_error", "atg_pcm_compare_device", "atg_pcm_offset_search_device",
+    "atg_pcm_compare_tile_frames", "atg_pcm_compare_kernel_times",
 )
 
 CONV_BPS, CONV_DOWNMIX, CONV_AVERAGE = 0, 1, 2
@@ -459,6 +461,26 @@ class PcmRun(ctypes.Structure):
     _fields_ = [("byte_offset", c_u64), ("samples", c_u64), ("sample_offset", c_u64)]
 
 
+class PcmView(ctypes.Structure):
+    """atg_pcm_view: view frame i is source frame window_offset + i, silence
+    outside the source's src_frames frames"""
+    _fields_ = [("d_pcm", ctypes.c_void_p), ("sample_offset", c_u64), ("src_frames", c_u64),
+                ("window_offset", ctypes.c_int64), ("format", c_u32), ("reserved", c_u32)]
+
+
+class PcmPair(ctypes.Structure):
+    """atg_pcm_pair: `frames` frames of view a against view b"""
+    _fields_ = [("a", PcmView), ("b", PcmView), ("frames", c_u64), ("channels", c_u32),
+                ("reserved", c_u32)]
+
+
+class PcmCmpResult(ctypes.Structure):
+    _fields_ = [("first_mismatch", c_u64), ("offset", c_i32), ("offset_found", c_u32)]
+
+
+PCM_NO_MISMATCH = (1 << 64) - 1
+
+
 class AiffInfo(ctypes.Structure):
     _fields_ = [("channels", c_u32), ("bits_per_sample", c_u32), ("sample_rate", c_u32),
                 ("channel_mask", c_u32), ("total_pcm_frames", c_u64),
@@ -679,6 +701,16 @@ def load_library():
         lib.atg_pcm_bytes_tile_samples.restype = c_u32
         lib.atg_pcm_bytes_kernel_times.argtypes = [P, P, ctypes.c_int]
         lib.atg_pcm_bytes_kernel_times.restype = ctypes.c_int
+        lib.atg_pcm_compare_last_error.restype = ctypes.c_char_p
+        lib.atg_pcm_compare_device.argtypes = [
+            ctypes.POINTER(PcmPair), c_u32, ctypes.POINTER(PcmCmpResult), P]
+        lib.atg_pcm_compare_device.restype = ctypes.c_int
+        lib.atg_pcm_offset_search_device.argtypes = [
+            ctypes.POINTER(PcmPair), c_u32, c_u32, ctypes.POINTER(PcmCmpResult), P]
+        lib.atg_pcm_offset_search_device.restype = ctypes.c_int
+        lib.atg_pcm_compare_tile_frames.restype = c_u32
+        lib.atg_pcm_compare_kernel_times.argtypes = [P, P, ctypes.c_int]
+        lib.atg_pcm_compare_kernel_times.restype = ctypes.c_int
         lib.atg_aiff_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AiffInfo)]
         lib.atg_aiff_read_info.restype = ctypes.c_int
         lib.atg_au_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AuInfo)]
@@ -2515,6 +2547,61 @@ def pcm_bytes_kernel_times():
     names = (ctypes.c_char_p * 1)()
     ms = (ctypes.c_float * 1)()
     k = lib.atg_pcm_bytes_kernel_times(names, ms, 1)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+# ------------------------------------------------- PCM comparison (pcm_compare.hip)
+def pcm_view(d_pcm, fmt, src_frames, sample_offset=0, window_offset=0):
+    """PcmView over the src_frames frames whose first sample is
+    d_pcm[sample_offset] (PCM_S16 / PCM_S32); view frame 0 is source frame
+    window_offset"""
+    return PcmView(d_pcm, sample_offset, src_frames, window_offset, fmt, 0)
+
+
+def pcm_pair(a, b, frames, channels):
+    return PcmPair(a, b, frames, channels, 0)
+
+
+def _pc_call(call, pairs):
+    lib = load_library()
+    n = len(pairs)
+    arr = (PcmPair * max(1, n))(*pairs)
+    res = (PcmCmpResult * max(1, n))()
+    st = call(lib, arr, n, res)
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_pcm_compare_last_error().decode("utf-8", "replace"))
+    return [res[i] for i in range(n)]
+
+
+def pcm_compare_device(pairs):
+    """first differing frame of every PcmPair, one launch for the batch
+    (atg_pcm_compare_device) -> [first_mismatch or None]"""
+    res = _pc_call(lambda lib, arr, n, res: lib.atg_pcm_compare_device(arr, n, res, None), pairs)
+    return [None if r.first_mismatch == PCM_NO_MISMATCH else int(r.first_mismatch) for r in res]
+
+
+def pcm_offset_search_device(pairs, max_offset):
+    """the shift k of smallest |k| in [-max_offset, max_offset] with
+    a(i) == b(i + k) over every PcmPair (atg_pcm_offset_search_device)
+    -> [(offset or None, first_mismatch at shift 0 or None)]"""
+    res = _pc_call(lambda lib, arr, n, res: lib.atg_pcm_offset_search_device(
+        arr, n, max_offset, res, None), pairs)
+    return [(int(r.offset) if r.offset_found else None,
+             None if r.first_mismatch == PCM_NO_MISMATCH else int(r.first_mismatch))
+            for r in res]
+
+
+def pcm_compare_tile_frames():
+    """PCM frames per tile of the compare pass"""
+    return int(load_library().atg_pcm_compare_tile_frames())
+
+
+def pcm_compare_kernel_times():
+    """{"compare": ms, "probe": ms} of this thread's last compare or search"""
+    lib = load_library()
+    names = (ctypes.c_char_p * 2)()
+    ms = (ctypes.c_float * 2)()
+    k = lib.atg_pcm_compare_kernel_times(names, ms, 2)
     return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
