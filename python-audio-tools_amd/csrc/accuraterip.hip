@@ -41,6 +41,8 @@
 
 #include "../../include/atgpu.h"
 #include "host_common.h"
+#include "table_search.h"
+#include "wave.h"
 
 namespace {
 
@@ -118,26 +120,10 @@ struct Sums {
     }
 };
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1)
-        v += __shfl_down(v, d, 64);
-    return v;
-}
-
 // the track whose tile run holds batch tile `tile`
 __device__ __forceinline__ uint32_t track_of_tile(const ArTrack *tr, uint32_t n, uint64_t tile)
 {
-    uint32_t l = 0, r = n; // last t with tr[t].tile0 <= tile
-    while (r - l > 1) {
-        const uint32_t m = (l + r) >> 1;
-        if (tr[m].tile0 <= tile)
-            l = m;
-        else
-            r = m;
-    }
-    return l;
+    return last_le(tr, n, tile, &ArTrack::tile0);
 }
 
 // pass 1: per-tile sums (x = values, y = low words, z = high words)
@@ -171,9 +157,9 @@ __global__ __launch_bounds__(kBlock) void k_ar_tiles(const void *__restrict__ pc
                         acc.add(Pcm<FMT>::one(pcm, p + f), (uint32_t)p + f + bias);
             }
         }
-        acc.s = wave_sum(acc.s);
-        acc.lo = wave_sum(acc.lo);
-        acc.hi = wave_sum(acc.hi);
+        acc.s = wave_sum_u32(acc.s);
+        acc.lo = wave_sum_u32(acc.lo);
+        acc.hi = wave_sum_u32(acc.hi);
         if ((threadIdx.x & 63) == 0) {
             red[0][threadIdx.x >> 6] = acc.s;
             red[1][threadIdx.x >> 6] = acc.lo;
@@ -209,9 +195,9 @@ __global__ __launch_bounds__(kBlock) void k_ar_tracks(const ArTrack *__restrict_
         lo += v.y;
         hi += v.z;
     }
-    s = wave_sum(s);
-    lo = wave_sum(lo);
-    hi = wave_sum(hi);
+    s = wave_sum_u32(s);
+    lo = wave_sum_u32(lo);
+    hi = wave_sum_u32(hi);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = s;
         red[1][threadIdx.x >> 6] = lo;
@@ -270,14 +256,8 @@ __global__ __launch_bounds__(kBlock) void k_ar_sweep(const void *__restrict__ pc
             dg = neg ? wa - wb : wb - wa;
         }
         // inclusive scan over the workgroup
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t uf = __shfl_up(df, d, 64), ug = __shfl_up(dg, d, 64);
-            if (lane >= (uint32_t)d) {
-                df += uf;
-                dg += ug;
-            }
-        }
+        df = wave_incl_scan_u32(df, (int)lane);
+        dg = wave_incl_scan_u32(dg, (int)lane);
         if (lane == 63) {
             wtot[0][wave] = df;
             wtot[1][wave] = dg;

@@ -40,6 +40,7 @@
 
 #include "../../include/atgpu.h"
 #include "alac_common.h"
+#include "wave.h"
 
 // Active lanes per 64-thread block of the walk kernels.  The read() chain
 // walk runs one track per wave (it was one track per lane: 3.6 -> 1.5 ms,
@@ -322,19 +323,6 @@ __global__ __launch_bounds__(64) void k_adec_parse(const uint32_t *__restrict__ 
     recs[i] = F;
 }
 
-// exclusive prefix sum over the wave
-template <typename V>
-__device__ __forceinline__ V wave_excl_sum(V v, int lane)
-{
-    V x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const V y = __shfl_up(x, d, 64);
-        x += lane >= d ? y : (V)0;
-    }
-    return x - v;
-}
-
 // K2: the read() walk per track (alac.c:183-254, remaining_frames), a wave
 // per track.  While the predictions chain -- each starts where the one
 // before it ends and parsed without error -- the wave takes 64 framesets a
@@ -377,8 +365,8 @@ __global__ __launch_bounds__(64) void k_adec_chain(const uint32_t *__restrict__ 
         }
         uint64_t at = __shfl_up(fend, 1, 64);
         at = lane == 0 ? pos : at;
-        const uint64_t before = wave_excl_sum<uint64_t>((uint64_t)n0, lane);
-        const uint32_t jbefore = wave_excl_sum<uint32_t>(nch, lane);
+        const uint64_t before = wave_excl_scan_u64((uint64_t)n0, lane);
+        const uint32_t jbefore = wave_excl_scan_u32(nch, lane);
         const bool take = valid && ps == at && st == AD_OK && before < remaining;
         const uint64_t bad = __ballot(!take);
         const uint32_t m = bad ? (uint32_t)__ffsll((long long)bad) - 1u : 64u;
@@ -398,11 +386,7 @@ __global__ __launch_bounds__(64) void k_adec_chain(const uint32_t *__restrict__ 
         const uint64_t s_n0 = __shfl(before + n0, (int)m - 1, 64);
         const uint32_t s_nch = __shfl(jbefore + nch, (int)m - 1, 64);
         const uint64_t end_m = __shfl(fend, (int)m - 1, 64);
-        uint32_t mx = (uint32_t)lane < m ? n0 : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1)
-            mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-        max_n0 = max(max_n0, mx);
+        max_n0 = max(max_n0, wave_max_u32((uint32_t)lane < m ? n0 : 0u));
         remaining = remaining > s_n0 ? remaining - s_n0 : 0u;
         pcm += s_n0;
         njob += s_nch;

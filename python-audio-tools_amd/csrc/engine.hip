@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "crc_common.h"
 #include "flac_dev.h"
 #include "launch.h"
 #include "md5_cpu.h"
@@ -54,53 +55,18 @@ const char *kOggTimedNames[4] = {"ogg_plan", "ogg_pages", "ogg_split", "ogg_crc"
 void build_crc_tables(uint32_t t16[4][256], uint32_t *t8, uint16_t adv[24][16],
                       uint16_t advq[kCrcQ][6][16])
 {
-    for (uint32_t b = 0; b < 256; ++b) {
-        uint32_t c = b << 8, c8 = b;
-        for (int i = 0; i < 8; ++i) {
-            c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) : (c << 1);
-            c8 = (c8 & 0x80u) ? ((c8 << 1) ^ 0x07u) : (c8 << 1);
-        }
-        t16[0][b] = c & 0xFFFFu;
-        t8[b] = c8 & 0xFFu;
-    }
-    for (int k = 1; k < 4; ++k)
-        for (uint32_t b = 0; b < 256; ++b) {
-            const uint32_t c = t16[k - 1][b];
-            t16[k][b] = ((c << 8) ^ t16[0][(c >> 8) & 0xFFu]) & 0xFFFFu;
-        }
-    // m = 0: one zero byte
-    for (int i = 0; i < 16; ++i) {
-        uint32_t s = 1u << i;
-        s = ((s << 8) ^ t16[0][(s >> 8) & 0xFFu]) & 0xFFFFu;
-        adv[0][i] = (uint16_t)s;
-    }
-    for (int m = 1; m < 24; ++m) {
-        for (int i = 0; i < 16; ++i) {
-            // apply adv[m-1] twice to basis vector i
-            uint32_t v = adv[m - 1][i], r = 0;
-            for (int j = 0; j < 16; ++j)
-                if ((v >> j) & 1u)
-                    r ^= adv[m - 1][j];
-            adv[m][i] = (uint16_t)r;
-        }
-    }
+    crc_build_tables<16>(0x8005u, &t16[0][0], 4);
+    crc_build_tables<8>(0x07u, t8, 1);
+    crc_build_advance<16>(t16[0], &adv[0][0], 24);
     // advq[q - 1][s]: 4 q 2^s zero bytes = (4 bytes)^q, squared s times
-    auto apply = [](const uint16_t *a, uint32_t v) {
-        uint32_t r = 0;
-        for (int j = 0; j < 16; ++j)
-            if ((v >> j) & 1u)
-                r ^= a[j];
-        return (uint16_t)r;
-    };
     for (int i = 0; i < 16; ++i)
         advq[0][0][i] = adv[2][i];
     for (int q = 1; q < kCrcQ; ++q)
         for (int i = 0; i < 16; ++i)
-            advq[q][0][i] = apply(adv[2], advq[q - 1][0][i]);
+            advq[q][0][i] = (uint16_t)crc_advance<16>(adv[2], advq[q - 1][0][i]);
     for (int q = 0; q < kCrcQ; ++q)
         for (int s = 1; s < 6; ++s)
-            for (int i = 0; i < 16; ++i)
-                advq[q][s][i] = apply(advq[q][s - 1], advq[q][s - 1][i]);
+            crc_square<16>(advq[q][s - 1], advq[q][s]);
 }
 
 } // namespace

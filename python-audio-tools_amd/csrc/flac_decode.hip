@@ -47,8 +47,10 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "crc_common.h"
 #include "launch.h"
 #include "ogg_demux.h"
+#include "table_search.h"
 #include "wave.h"
 
 namespace {
@@ -961,13 +963,7 @@ __device__ __forceinline__ void load_crc_lds(uint16_t (*T)[256])
 __device__ __forceinline__ uint32_t find_track(const DecTrack *tr, uint32_t nt, uint64_t p)
 {
     // last track with start <= p (tracks sorted by start)
-    uint32_t lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tr[mid].start <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
+    return last_le(tr, nt, p, &DecTrack::start);
 }
 
 // K1: sync-code candidates.  A position needs byte 0xFF followed by
@@ -1125,28 +1121,6 @@ __global__ __launch_bounds__(64) void k_dec_parse(const uint32_t *__restrict__ w
     }
 }
 
-// CRC-16 advance: the state after 2^m more zero bytes (GF(2) matrix m)
-__device__ __forceinline__ uint32_t dcrc_adv(uint32_t c, int m)
-{
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        r ^= ((c >> i) & 1u) ? (uint32_t)c_crc_adv[m][i] : 0u;
-    return r;
-}
-
-// big-endian 32 bits at absolute byte b of the buffer (two aligned loads)
-__device__ __forceinline__ uint32_t be32_at(const uint32_t *w, uint64_t last, uint64_t b)
-{
-    const uint64_t i = b >> 2;
-    const uint32_t x = bswap32(w[i < last ? i : last]);
-    const uint32_t r = (uint32_t)(b & 3u);
-    if (!r)
-        return x;
-    const uint32_t y = bswap32(w[i + 1 < last ? i + 1 : last]);
-    return (x << (8u * r)) | (y >> (32u - 8u * r));
-}
-
 // CRC-16 residue of bytes [pos, pos + L) on one wave (0 for an intact
 // frame: header to CRC bytes): 64 chunks of Lc = 2^m bytes of a virtually
 // zero-prefixed image (leading zeros leave a zero-init CRC unchanged),
@@ -1216,7 +1190,7 @@ __device__ uint32_t wave_crc16(const uint32_t *__restrict__ w, uint64_t nw, uint
     for (int k = 0; k < 6; ++k) {
         const uint32_t other = (uint32_t)__shfl_down((int)crc, 1 << k, 64);
         if ((lane & ((2u << k) - 1u)) == 0)
-            crc = dcrc_adv(crc, (int)lc_log + k) ^ other;
+            crc = crc_advance<16>(c_crc_adv[(int)lc_log + k], crc) ^ other;
     }
     return (uint32_t)__shfl((int)crc, 0, 64);
 }
@@ -2080,43 +2054,6 @@ struct atg_decoder {
     std::vector<OggHdr> og_hd;
 };
 
-static void build_dec_adv(const uint16_t t16[4][256], uint16_t adv[24][16])
-{
-    // adv[0]: one zero byte; adv[m] = adv[m-1] applied twice
-    for (int i = 0; i < 16; ++i) {
-        uint32_t c = 1u << i;
-        c = ((c << 8) ^ t16[0][(c >> 8) & 0xFFu]) & 0xFFFFu;
-        adv[0][i] = (uint16_t)c;
-    }
-    for (int m = 1; m < 24; ++m)
-        for (int i = 0; i < 16; ++i) {
-            uint32_t v = adv[m - 1][i], r = 0;
-            for (int j = 0; j < 16; ++j)
-                if ((v >> j) & 1u)
-                    r ^= adv[m - 1][j];
-            adv[m][i] = (uint16_t)r;
-        }
-}
-
-static void build_dec_tables(uint8_t *t8, uint16_t t16[4][256])
-{
-    for (uint32_t b = 0; b < 256; ++b) {
-        uint32_t c8 = b;
-        for (int i = 0; i < 8; ++i)
-            c8 = (c8 & 0x80) ? ((c8 << 1) ^ 0x07) : (c8 << 1);
-        t8[b] = (uint8_t)c8;
-        uint32_t c = b << 8;
-        for (int i = 0; i < 8; ++i)
-            c = (c & 0x8000) ? ((c << 1) ^ 0x8005) : (c << 1);
-        t16[0][b] = (uint16_t)c;
-    }
-    for (int k = 1; k < 4; ++k)
-        for (uint32_t b = 0; b < 256; ++b) {
-            const uint32_t p = t16[k - 1][b];
-            t16[k][b] = (uint16_t)(((p << 8) & 0xFFFF) ^ t16[0][p >> 8]);
-        }
-}
-
 static const uint32_t kMasks[9] = {0, 0x4, 0x3, 0x7, 0x33, 0x37, 0x3F, 0x70F, 0x63F};
 
 extern "C" {
@@ -2261,11 +2198,12 @@ atg_status atg_decoder_create(int device, atg_decoder **out)
     DHIP(hipSetDevice(device));
     static uint8_t t8[256];
     static uint16_t t16[4][256];
-    build_dec_tables(t8, t16);
+    crc_build_tables<8>(0x07u, t8, 1);
+    crc_build_tables<16>(0x8005u, &t16[0][0], 4);
     DHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_crc8), t8, sizeof(t8)));
     DHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_crc16), t16, sizeof(t16)));
     static uint16_t adv[24][16];
-    build_dec_adv(t16, adv);
+    crc_build_advance<16>(t16[0], &adv[0][0], 24);
     DHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_adv), adv, sizeof(adv)));
     atg_decoder *d = new atg_decoder();
     d->device = device;

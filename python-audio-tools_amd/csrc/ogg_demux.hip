@@ -38,7 +38,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/atgpu.h"
+#include "crc_common.h"
 #include "ogg_demux.h"
+#include "table_search.h"
 #include "wave.h"
 
 namespace {
@@ -148,27 +150,6 @@ __global__ __launch_bounds__(64) void k_ogg_walk(const uint8_t *__restrict__ dat
     }
 }
 
-__device__ __forceinline__ uint32_t ogg_adv(uint32_t c, int m)
-{
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        r ^= ((c >> i) & 1u) ? g_ogg_adv[m][i] : 0u;
-    return r;
-}
-
-// big-endian 32 bits at absolute byte b (two aligned loads, clamped to the buffer)
-__device__ __forceinline__ uint32_t ogg_be32(const uint32_t *w, uint64_t last, uint64_t b)
-{
-    const uint64_t i = b >> 2;
-    const uint32_t x = __builtin_bswap32(w[i < last ? i : last]);
-    const uint32_t r = (uint32_t)(b & 3u);
-    if (!r)
-        return x;
-    const uint32_t y = __builtin_bswap32(w[i + 1 < last ? i + 1 : last]);
-    return (x << (8u * r)) | (y >> (32u - 8u * r));
-}
-
 // K2: page checksums, a lane per chunk
 __global__ __launch_bounds__(256) void k_ogg_crc(const uint32_t *__restrict__ w, uint64_t nw,
                                                  const OggPage *__restrict__ pages,
@@ -183,12 +164,7 @@ __global__ __launch_bounds__(256) void k_ogg_crc(const uint32_t *__restrict__ w,
     if (c >= nchunks || !npages)
         return;
     // the chunk's page: the last one with chunk_base <= c
-    uint64_t lo = 0, hi = npages;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pages[mid].chunk_base <= c) lo = mid;
-        else hi = mid;
-    }
+    const uint64_t lo = last_le(pages, npages, c, &OggPage::chunk_base);
     const OggPage p = pages[lo];
     const uint32_t size = 27u + p.nseg + p.body;
     const uint32_t from = (uint32_t)(c - p.chunk_base) * kOggCrcChunk;
@@ -197,14 +173,14 @@ __global__ __launch_bounds__(256) void k_ogg_crc(const uint32_t *__restrict__ w,
     const uint32_t upto = from + kOggCrcChunk < size ? from + kOggCrcChunk : size;
     uint32_t crc = 0, q = from;
     for (; q + 4 <= upto; q += 4) {
-        uint32_t x = ogg_be32(w, nw - 1, p.off + q);
+        uint32_t x = be32_at(w, nw - 1, p.off + q);
         // the checksum field (bytes 22-25) counts as zero
         x = q == 20u ? x & 0xFFFF0000u : (q == 24u ? x & 0x0000FFFFu : x);
         x ^= crc;
         crc = T[3][x >> 24] ^ T[2][(x >> 16) & 0xFFu] ^ T[1][(x >> 8) & 0xFFu] ^ T[0][x & 0xFFu];
     }
     if (q < upto) { // the page's last 1-3 bytes (of a 27-byte page: 24, 25 of the field, 26)
-        const uint32_t x = ogg_be32(w, nw - 1, p.off + q);
+        const uint32_t x = be32_at(w, nw - 1, p.off + q);
         for (uint32_t k = 0; q < upto; ++q, ++k) {
             const uint32_t b = q >= 22u && q < 26u ? 0u : (x >> (24u - 8u * k)) & 0xFFu;
             crc = (crc << 8) ^ T[0][(crc >> 24) ^ b];
@@ -214,7 +190,7 @@ __global__ __launch_bounds__(256) void k_ogg_crc(const uint32_t *__restrict__ w,
     uint32_t z = size - upto;
     for (int m = 0; z; ++m, z >>= 1)
         if (z & 1u)
-            crc = ogg_adv(crc, m);
+            crc = crc_advance<32>(g_ogg_adv[m], crc);
     if (crc)
         atomicXor(&acc[lo], crc);
 }
@@ -235,11 +211,7 @@ __global__ __launch_bounds__(64) void k_ogg_summary(const OggStream *__restrict_
     for (uint32_t i = threadIdx.x; i < wk.pages; i += 64u)
         if (bad == kOggNoPage && acc[st.page_base + i] != pages[st.page_base + i].crc)
             bad = i;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint32_t o = shfl_xor_u32(bad, m);
-        bad = o < bad ? o : bad;
-    }
+    bad = wave_min_u32(bad);
     if (threadIdx.x != 0)
         return;
     OggSum o;
@@ -341,13 +313,7 @@ __global__ __launch_bounds__(256) void k_ogg_gather(const uint32_t *__restrict__
         if (b0 < sm.bytes) {
             // the page holding byte b0: the last delivered one with body_off <= b0
             const OggPage *pg = pages + st.page_base;
-            uint32_t lo = 0, hi = sm.pages;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (pg[mid].body_off <= b0) lo = mid;
-                else hi = mid;
-            }
-            uint32_t pi = lo;
+            uint32_t pi = last_le(pg, sm.pages, b0, &OggPage::body_off);
             OggPage p = pg[pi];
             for (int k = 0; k < 4; ++k) {
                 const uint64_t b = b0 + 4u * (uint32_t)k;
@@ -357,7 +323,7 @@ __global__ __launch_bounds__(256) void k_ogg_gather(const uint32_t *__restrict__
                     p = pg[++pi];
                 if (b + 4 <= p.body_off + p.body) { // the whole word inside one page
                     const uint64_t src = p.off + 27u + p.nseg + (b - p.body_off);
-                    q[k] = __builtin_bswap32(ogg_be32(w, nw - 1, src));
+                    q[k] = __builtin_bswap32(be32_at(w, nw - 1, src));
                 } else { // a page boundary (or the stream's end) inside the word
                     uint32_t x = 0, pj = pi;
                     OggPage pp = p;
@@ -365,7 +331,7 @@ __global__ __launch_bounds__(256) void k_ogg_gather(const uint32_t *__restrict__
                         while (b + j >= pp.body_off + pp.body && pj + 1 < sm.pages)
                             pp = pg[++pj];
                         const uint64_t src = pp.off + 27u + pp.nseg + (b + j - pp.body_off);
-                        x |= (ogg_be32(w, nw - 1, src) >> 24) << (8u * j);
+                        x |= (be32_at(w, nw - 1, src) >> 24) << (8u * j);
                     }
                     q[k] = x;
                 }
@@ -381,31 +347,8 @@ hipError_t ogg_upload_tables()
 {
     static uint32_t tab[4][256];
     static uint32_t adv[17][32];
-    for (uint32_t b = 0; b < 256; ++b) {
-        uint32_t c = b << 24;
-        for (int i = 0; i < 8; ++i)
-            c = (c & 0x80000000u) ? (c << 1) ^ 0x04C11DB7u : c << 1;
-        tab[0][b] = c;
-    }
-    for (int k = 1; k < 4; ++k)
-        for (uint32_t b = 0; b < 256; ++b) {
-            const uint32_t p = tab[k - 1][b];
-            tab[k][b] = (p << 8) ^ tab[0][p >> 24];
-        }
-    // adv[0]: one zero byte; adv[m] = adv[m-1] applied twice
-    for (int i = 0; i < 32; ++i) {
-        const uint32_t c = 1u << i;
-        adv[0][i] = (c << 8) ^ tab[0][c >> 24];
-    }
-    for (int m = 1; m < 17; ++m)
-        for (int i = 0; i < 32; ++i) {
-            const uint32_t v = adv[m - 1][i];
-            uint32_t r = 0;
-            for (int j = 0; j < 32; ++j)
-                if ((v >> j) & 1u)
-                    r ^= adv[m - 1][j];
-            adv[m][i] = r;
-        }
+    crc_build_tables<32>(0x04C11DB7u, &tab[0][0], 4);
+    crc_build_advance<32>(tab[0], &adv[0][0], 17);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_ogg_crc), tab, sizeof(tab));
     if (e == hipSuccess)
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_ogg_adv), adv, sizeof(adv));

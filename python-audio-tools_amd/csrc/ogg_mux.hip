@@ -32,8 +32,10 @@
 //                  wave, written to bytes 22-25.
 #include <hip/hip_runtime.h>
 
+#include "crc_common.h"
 #include "ogg_demux.h"
 #include "ogg_mux.h"
+#include "table_search.h"
 #include "wave.h"
 
 namespace {
@@ -43,13 +45,7 @@ __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t *ws
                                                         uint64_t *total)
 {
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = shfl_up_u64(x, d);
-        if (lane >= d)
-            x += y;
-    }
+    const uint64_t x = wave_incl_scan_u64(v, lane);
     __syncthreads(); // the previous use of wsum is over
     if (lane == 63)
         wsum[wave] = x;
@@ -68,13 +64,7 @@ __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t *ws
 // the last frame i of [0, n) with slot0 <= q (slot0 ascends, fr[0].slot0 = 0)
 __device__ __forceinline__ uint32_t owner_of(const OggMuxFrame *fr, uint32_t n, uint64_t q)
 {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (fr[mid].slot0 <= q) lo = mid;
-        else hi = mid;
-    }
-    return lo;
+    return last_le(fr, n, q, &OggMuxFrame::slot0);
 }
 
 __global__ __launch_bounds__(256) void k_ogg_plan(OggMuxParams mp,
@@ -312,15 +302,6 @@ __global__ __launch_bounds__(256) void k_ogg_split(OggMuxParams mp,
     }
 }
 
-__device__ __forceinline__ uint32_t mux_adv(const uint32_t *adv, uint32_t c, int m)
-{
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        r ^= ((c >> i) & 1u) ? adv[32 * m + i] : 0u;
-    return r;
-}
-
 __global__ __launch_bounds__(256) void k_ogg_mux_crc(OggMuxParams mp,
                                                      const OggMuxTrack *__restrict__ tracks,
                                                      const OggMuxOut *__restrict__ outs,
@@ -381,7 +362,7 @@ __global__ __launch_bounds__(256) void k_ogg_mux_crc(OggMuxParams mp,
         }
         for (int m = 0; z; ++m, z >>= 1)
             if (z & 1u)
-                acc = mux_adv(adv, acc, m);
+                acc = crc_advance<32>(adv + 32 * m, acc);
         if (lane == 63u) { // the bytes before the first block
             uint32_t hc = 0;
             for (uint32_t q = 0; q < head; ++q)
@@ -389,7 +370,7 @@ __global__ __launch_bounds__(256) void k_ogg_mux_crc(OggMuxParams mp,
             uint32_t zh = size - head;
             for (int m = 0; zh; ++m, zh >>= 1)
                 if (zh & 1u)
-                    hc = mux_adv(adv, hc, m);
+                    hc = crc_advance<32>(adv + 32 * m, hc);
             acc ^= hc;
         }
         if (lane == 0u) { // the bytes after the last block: nothing follows them
@@ -398,9 +379,7 @@ __global__ __launch_bounds__(256) void k_ogg_mux_crc(OggMuxParams mp,
                 tc = (tc << 8) ^ T[0][(tc >> 24) ^ pg[q]];
             acc ^= tc;
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1)
-            acc ^= shfl_xor_u32(acc, m);
+        acc = wave_xor_u32(acc);
         if (lane < 4u)
             out[r.off + 22u + lane] = (uint8_t)(acc >> (8u * lane));
     }

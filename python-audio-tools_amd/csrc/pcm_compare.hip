@@ -55,6 +55,8 @@
 
 #include "../../include/atgpu.h"
 #include "host_common.h"
+#include "table_search.h"
+#include "wave.h"
 
 namespace {
 
@@ -265,16 +267,6 @@ template <int FA, int FB, int PH = 0> struct ByPhase {
     }
 };
 
-__device__ __forceinline__ uint64_t wave_min(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const uint64_t o = __shfl_down(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // Batch tile `tile` -> its pair and its number within the pair.  The first
 // tiles of all pairs come first in the list, so that a mismatch near a
 // pair's start is on record before most of its other tiles are begun; the
@@ -288,14 +280,8 @@ __device__ __forceinline__ uint32_t pair_of_tile(const CmpPair *pr, uint32_t n, 
         return (uint32_t)tile;
     }
     const uint64_t rest = tile - n;
-    uint32_t l = 0, r = n; // last i with pr[i].rest0 <= rest: it has such tiles
-    while (r - l > 1) {
-        const uint32_t m = (l + r) >> 1;
-        if (pr[m].rest0 <= rest)
-            l = m;
-        else
-            r = m;
-    }
+    // the last i with pr[i].rest0 <= rest: it has such tiles
+    const uint32_t l = last_le(pr, n, rest, &CmpPair::rest0);
     *within = 1 + (rest - pr[l].rest0);
     return l;
 }
@@ -338,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void k_pcm_compare(const CmpPair *__restric
         }
         // the usual tile has no mismatch and ends at this one barrier
         if (__syncthreads_or(best != kNone)) {
-            best = wave_min(best);
+            best = wave_min_u64(best);
             if ((threadIdx.x & 63) == 0)
                 red[threadIdx.x >> 6] = best;
             __syncthreads();

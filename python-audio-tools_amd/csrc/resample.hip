@@ -42,6 +42,7 @@
 #include "../../include/atgpu.h"
 #include "host_common.h"
 #include "src_coeffs.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -114,9 +115,7 @@ __global__ __launch_bounds__(64) void k_rs_positions(const RsTrack *__restrict__
     if (active)
         ratio_inv = __longlong_as_double((long long)T.D); // 1.0 / ratio (host double bits)
     // every lane runs the block's longest track's steps; shorter ones idle
-    uint64_t steps = total;
-    for (int o = 32; o > 0; o >>= 1)
-        steps = max(steps, (uint64_t)__shfl_xor((unsigned long long)steps, o));
+    const uint64_t steps = wave_max_u64(total);
     for (uint64_t n0 = 0; n0 < steps; n0 += 64) {
         for (uint32_t k = 0; k < 64; ++k) {
             const uint64_t nn = n0 + k;

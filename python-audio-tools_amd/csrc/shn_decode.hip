@@ -43,6 +43,8 @@
 
 #include "../../include/atgpu.h"
 #include "shn_common.h"
+#include "table_search.h"
+#include "wave.h"
 
 namespace {
 
@@ -119,12 +121,7 @@ __device__ void coop_skip(shn::Bits &r, uint32_t n, uint32_t w, uint32_t lane, u
             e = map[e * 64u + l] & 0xFFu;
         }
         const uint32_t cnt = map[mine * 64u + lane] >> 8;
-        uint32_t inc = cnt;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc, d, 64);
-            if ((int)lane >= d)
-                inc += t;
-        }
+        const uint32_t inc = wave_incl_scan_u32(cnt, (int)lane);
         const uint32_t total = (uint32_t)__shfl((int)inc, 63, 64);
         if (total < n) {
             n -= total;
@@ -282,15 +279,7 @@ __global__ __launch_bounds__(64) void k_shnd_index(const uint8_t *__restrict__ d
 __device__ __forceinline__ uint32_t find_stream(const DTrack *__restrict__ tr, uint32_t n,
                                                 uint64_t slot)
 {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tr[mid].ubase <= slot)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
+    return last_le(tr, n, slot, &DTrack::ubase);
 }
 
 __global__ __launch_bounds__(64) void k_shnd_parse(const uint8_t *__restrict__ data,
@@ -332,16 +321,6 @@ __global__ __launch_bounds__(64) void k_shnd_parse(const uint8_t *__restrict__ d
 }
 
 // -------------------------------------------------------------- recon pass
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)v, d, 64);
-        if ((int)lane >= d)
-            v += t;
-    }
-    return v;
-}
-
 __device__ __forceinline__ int32_t shn_mean(int32_t half_plus_sum, int32_t n)
 {
     return half_plus_sum / n; // C division: truncates toward zero
@@ -426,14 +405,14 @@ __global__ __launch_bounds__(64) void k_shnd_recon(const uint8_t *__restrict__ d
                 x += offset;
             } else if (cmd != shn::FN_ZERO) {
                 if (cmd == shn::FN_DIFF3) {
-                    x = wave_scan(x, lane) + c3;
+                    x = wave_incl_scan_u32(x, (int)lane) + c3;
                     c3 = (uint32_t)__shfl((int)x, 63, 64);
                 }
                 if (cmd >= shn::FN_DIFF2) {
-                    x = wave_scan(x, lane) + c2;
+                    x = wave_incl_scan_u32(x, (int)lane) + c2;
                     c2 = (uint32_t)__shfl((int)x, 63, 64);
                 }
-                x = wave_scan(x, lane) + c1;
+                x = wave_incl_scan_u32(x, (int)lane) + c1;
                 c1 = (uint32_t)__shfl((int)x, 63, 64);
             }
             if (valid) {
@@ -445,8 +424,7 @@ __global__ __launch_bounds__(64) void k_shnd_recon(const uint8_t *__restrict__ d
         }
         histlen = keep;
         if (mc) {
-            for (int m = 32; m; m >>= 1)
-                total += (uint32_t)__shfl_xor((int)total, m, 64);
+            total = wave_sum_u32(total);
             const int32_t mean = shn_mean((int32_t)(L / 2u + total), (int32_t)L);
             __syncthreads();
             const int32_t next = lane + 1u < mc ? means[lane + 1u] : mean;

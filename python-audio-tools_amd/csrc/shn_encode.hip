@@ -36,6 +36,8 @@
 
 #include "../../include/atgpu.h"
 #include "shn_common.h"
+#include "table_search.h"
+#include "wave.h"
 
 namespace {
 
@@ -71,28 +73,7 @@ __device__ __forceinline__ Geom block_geom(const ETrack &T, const uint64_t *__re
 __device__ __forceinline__ uint32_t find_track(const ETrack *__restrict__ tr, uint32_t n,
                                                uint64_t u)
 {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tr[mid].unit0 <= u)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t wave_or(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v |= (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
+    return last_le(tr, n, u, &ETrack::unit0);
 }
 
 // info word of a unit
@@ -116,7 +97,7 @@ __device__ __forceinline__ uint32_t block_or(const Chan<T> &ch, Geom g, uint32_t
     uint32_t acc = 0;
     for (uint32_t i = lane; i < g.n; i += 64u)
         acc |= (uint32_t)ch.at(g.start + i);
-    return wave_or(acc);
+    return wave_or_u32(acc);
 }
 
 // What both kernels need of a unit: its shift and the three samples before
@@ -200,9 +181,9 @@ __global__ __launch_bounds__(256) void k_shn_size(const T *__restrict__ pcm,
             s2 += (uint32_t)abs(d2);
             s3 += (uint32_t)abs(d3);
         }
-        s1 = wave_add(s1);
-        s2 = wave_add(s2);
-        s3 = wave_add(s3);
+        s1 = wave_sum_u32(s1);
+        s2 = wave_sum_u32(s2);
+        s3 = wave_sum_u32(s3);
         uint32_t diff, sum;
         if (s1 < min(s2, s3)) {
             diff = 1;
@@ -232,7 +213,7 @@ __global__ __launch_bounds__(256) void k_shn_size(const T *__restrict__ pcm,
             }
             len += (fold((int32_t)r) >> w) + 1u + w;
         }
-        len = wave_add(len);
+        len = wave_sum_u32(len);
         info |= (sh << kShiftAt) | ((diff & 3u) << kDiffAt) | (energy << kEnergyAt);
         bits += 3u + shn::unsigned_bits(shn::kEnergySize, energy) + len;
     }
@@ -377,12 +358,7 @@ __global__ __launch_bounds__(256) void k_shn_pack(const T *__restrict__ pcm,
             len = (f >> w) + 1u + w;
         }
         // inclusive sum of the code lengths over the wave
-        uint32_t inc = len;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc, d, 64);
-            if ((int)lane >= d)
-                inc += t;
-        }
+        const uint32_t inc = wave_incl_scan_u32(len, (int)lane);
         if (i < g.n) {
             const uint64_t at = pos + (inc - len) + (f >> w); // past the zero run
             if (w < 32u) {

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "bits_lsb.h"
 #include "tta_common.h"
 
 namespace {
@@ -58,66 +59,6 @@ __global__ __launch_bounds__(256) void k_ttad_crc(const Frame *__restrict__ fram
     }
 }
 
-// LSB-first bit reader over bytes [pos, end) of data; words are loaded
-// aligned, and only words that hold at least one byte of the range (the
-// range is followed by the frame's 4 CRC bytes and starts inside the batch
-// buffer, so such a word lies inside the buffer)
-struct BitReader {
-    const uint32_t *words; // data as aligned words
-    uint64_t pos, end;     // next byte to load, end of payload (byte indices)
-    uint64_t acc = 0;      // loaded bits, next bit at bit 0
-    uint32_t have = 0;     // valid bits in acc
-
-    __device__ __forceinline__ void refill()
-    {
-        while (have <= 32u && pos < end) {
-            const uint32_t w = words[pos >> 2];
-            const uint32_t skip = (uint32_t)pos & 3u;       // bytes below pos in the word
-            const uint64_t left = end - pos;                // bytes still in range
-            uint32_t nb = 4u - skip;                        // bytes this word offers
-            if ((uint64_t)nb > left)
-                nb = (uint32_t)left;
-            uint32_t v = w >> (8u * skip);
-            if (nb < 4u)
-                v &= (1u << (8u * nb)) - 1u;
-            acc |= (uint64_t)v << have;
-            have += 8u * nb;
-            pos += nb;
-        }
-    }
-    // a unary run ended by a 0 bit; false when the range ends first
-    __device__ __forceinline__ bool unary(uint32_t &count)
-    {
-        count = 0;
-        for (;;) {
-            refill();
-            if (have == 0)
-                return false;
-            const uint64_t inv = ~acc;
-            const uint32_t ones = inv ? (uint32_t)__ffsll((long long)inv) - 1u : 64u;
-            if (ones < have) {
-                count += ones;
-                acc = (acc >> ones) >> 1; // ones + 1 may be 64
-                have -= ones + 1u;
-                return true;
-            }
-            count += have;
-            acc = 0;
-            have = 0;
-        }
-    }
-    __device__ __forceinline__ bool bits(uint32_t n, uint32_t &v) // n <= 32
-    {
-        refill();
-        if (have < n)
-            return false;
-        v = n ? (uint32_t)(acc & ((1ull << n) - 1ull)) : 0u;
-        acc >>= n;
-        have -= n;
-        return true;
-    }
-};
-
 constexpr uint32_t kMaxCh = 8; // Rice states kept in private memory up to here
 
 // CT: the batch's channel count when every track has 1 or 2 channels (the
@@ -135,8 +76,11 @@ __global__ __launch_bounds__(64) void k_ttad_parse(const Frame *__restrict__ fra
         return;
     const Frame fr = frames[f];
     const uint32_t C = CT ? CT : fr.channels;
-    BitReader br;
-    br.words = (const uint32_t *)data;
+    // only words that hold at least one byte of the payload are loaded (it
+    // is followed by the frame's 4 CRC bytes and starts inside the batch
+    // buffer, so such a word lies inside the buffer)
+    LsbReader<false> br;
+    br.data = data;
     br.pos = fr.byte_off;
     br.end = fr.byte_off + fr.payload;
     tta::Rice reg[CT ? CT : kMaxCh];

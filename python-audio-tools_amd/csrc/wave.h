@@ -63,6 +63,36 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     return v;
 }
 
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        uint64_t o = shfl_xor_u64(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        uint32_t o = shfl_xor_u32(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        uint64_t o = shfl_xor_u64(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v)
 {
 #pragma unroll
@@ -71,22 +101,57 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v)
     return v;
 }
 
+__device__ __forceinline__ uint32_t wave_xor_u32(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+        v ^= shfl_xor_u32(v, m);
+    return v;
+}
+
 __device__ __forceinline__ bool wave_all(bool b)
 {
     return __ballot(!b) == 0;
 }
 
+__device__ __forceinline__ uint32_t shfl_up_u32(uint32_t v, int d)
+{
+    return (uint32_t)__shfl_up((int)v, d, 64);
+}
+
+// inclusive prefix sum over the wave (T is uint32_t or uint64_t)
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        T y;
+        if constexpr (sizeof(T) == 8) y = shfl_up_u64(v, d); else y = shfl_up_u32(v, d);
+        if (lane >= d)
+            v += y;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
+{
+    return wave_incl_scan<uint32_t>(v, lane);
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v, int lane)
+{
+    return wave_incl_scan<uint64_t>(v, lane);
+}
+
 // exclusive prefix sum over the wave
 __device__ __forceinline__ uint32_t wave_excl_scan_u32(uint32_t v, int lane)
 {
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
-        if (lane >= d)
-            x += y;
-    }
-    return x - v;
+    return wave_incl_scan<uint32_t>(v, lane) - v;
+}
+
+__device__ __forceinline__ uint64_t wave_excl_scan_u64(uint64_t v, int lane)
+{
+    return wave_incl_scan<uint64_t>(v, lane) - v;
 }
 
 // ---- DPP (data-parallel primitive) forms: VALU lane exchanges with no LDS

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/atgpu.h"
+#include "bits_lsb.h"
 #include "md5_cpu.h"
 #include "wavpack_common.h"
 
@@ -47,72 +48,8 @@ namespace {
 using wv::Block;
 using wv::Params;
 
-// LSB-first bit reader over bytes [pos, end) of data.  Words are loaded
-// aligned where the whole word lies below `limit` (the batch buffer's
-// length), byte by byte otherwise; bytes outside [pos, end) are masked off,
-// so a neighbour's bytes never reach the decoder.
-struct BitReader {
-    const uint8_t *data;
-    uint64_t pos, end, limit;
-    uint64_t acc = 0;
-    uint32_t have = 0;
-
-    __device__ __forceinline__ void refill()
-    {
-        while (have <= 32u && pos < end) {
-            const uint64_t base = pos & ~3ull;
-            const uint32_t skip = (uint32_t)pos & 3u;
-            const uint64_t left = end - pos;
-            uint32_t nb = 4u - skip;
-            if ((uint64_t)nb > left)
-                nb = (uint32_t)left;
-            uint32_t v;
-            if (base + 4u <= limit) {
-                v = *(const uint32_t *)(data + base) >> (8u * skip);
-            } else {
-                v = 0;
-                for (uint32_t k = 0; k < nb; ++k)
-                    v |= (uint32_t)data[pos + k] << (8u * k);
-            }
-            if (nb < 4u)
-                v &= (1u << (8u * nb)) - 1u;
-            acc |= (uint64_t)v << have;
-            have += 8u * nb;
-            pos += nb;
-        }
-    }
-    // a run of 1 bits ended by a 0 bit; false when the range ends first
-    __device__ __forceinline__ bool unary(uint32_t &count)
-    {
-        count = 0;
-        for (;;) {
-            refill();
-            if (have == 0)
-                return false;
-            const uint64_t inv = ~acc;
-            const uint32_t ones = inv ? (uint32_t)__ffsll((long long)inv) - 1u : 64u;
-            if (ones < have) {
-                count += ones;
-                acc = (acc >> ones) >> 1;
-                have -= ones + 1u;
-                return true;
-            }
-            count += have;
-            acc = 0;
-            have = 0;
-        }
-    }
-    __device__ __forceinline__ bool bits(uint32_t n, uint32_t &v) // n <= 32
-    {
-        refill();
-        if (have < n)
-            return false;
-        v = n ? (uint32_t)(acc & ((1ull << n) - 1ull)) : 0u;
-        acc >>= n;
-        have -= n;
-        return true;
-    }
-};
+// words whole below the batch buffer's length are loaded aligned, the rest by bytes
+using BitReader = LsbReader<true>;
 
 // read_egc: an Elias-gamma code; a length beyond 32 bits is refused
 __device__ __forceinline__ bool read_egc(BitReader &br, uint32_t &value)
