@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 9
+#define ATG_ABI_VERSION 10
 
 typedef enum {
     ATG_OK = 0,
@@ -1013,6 +1013,88 @@ uint32_t atg_pcm_compare_tile_frames(void);
    shift probe); returns the number of entries written, 0 before any call
    that launched. */
 int atg_pcm_compare_kernel_times(const char **names, float *ms, int cap);
+
+/* ------------------------------------------------------------------ */
+/* The PCM converter chain of a batch conversion (track2track with      */
+/* another channel count or bits per sample).  One launch does, for     */
+/* every track of a ragged table, what the reference's PCMConverter     */
+/* stacks as readers (audiotools/__init__.py:2729-2802) on either side  */
+/* of its resampler: a channel operation (ReorderedPCMReader /          */
+/* RemaskedPCMReader / Downmixer / Averager), then BPSConverter.        */
+/* Stateless: no handle.                                                */
+/* ------------------------------------------------------------------ */
+enum {
+    ATG_CHAIN_MAP = 0,             /* output k = input map[k], or silence */
+    ATG_CHAIN_DOWNMIX = 1,         /* ATG_CONV_DOWNMIX's arithmetic, -> 2 channels */
+    ATG_CHAIN_AVERAGE = 2,         /* ATG_CONV_AVERAGE's, -> 1 channel */
+    ATG_CHAIN_DOWNMIX_AVERAGE = 3  /* Averager(Downmixer(x)), -> 1 channel */
+};
+#define ATG_CHAIN_SILENT 0xFFu /* a map entry: the output channel is silence */
+
+/* One track.  src is read as atg_pcm_view describes a source (src_frames
+   frames of in_channels channels from sample_offset on; window_offset must
+   be 0).  The channel operation gives out_channels channels at in_bps bits,
+   the bits-per-sample operation then out_bps: up is x << s, down is
+   (x >> s) ^ dither bit, identity when the two are equal.  A row that
+   reduces takes src_frames * out_channels bits of the call's dither stream
+   from bit dither_bit0 on, MSB first, in atg_pcm_convert_device's order:
+   per 4096-frame read of the stage's input (the last read short), channel
+   by channel within a read.  The output is the src_frames * out_channels
+   samples from index out_offset of the call's output buffer. */
+typedef struct {
+    atg_pcm_view src;
+    uint32_t in_channels, out_channels; /* 1..8; 2 for DOWNMIX, 1 for the averages */
+    uint32_t channel_op;                /* ATG_CHAIN_* */
+    uint32_t channel_mask;              /* the downmixes: the input's mask, 0 =
+                                           the invented mask of its channel count */
+    uint8_t map[8];                     /* MAP: per output channel an input
+                                           channel or ATG_CHAIN_SILENT */
+    uint32_t in_bps, out_bps;           /* 1..24 */
+    uint64_t out_offset;
+    uint64_t dither_bit0;
+} atg_pcm_chain_row;
+
+const char *atg_pcm_chain_last_error(void);
+
+/* Convert every row in one launch; d_out is interleaved int16 (ATG_PCM_S16,
+   rows of at most 16 output bits) or int32.  Memory contract: the kernel
+   reads only aligned 16-byte units that hold at least one sample of some
+   row's source range, so sources need only be aligned to their sample size
+   and may lie at any sample offset; it reads only the dither bytes that hold
+   a row's bits; it writes only samples inside the rows' output ranges, in
+   16-byte groups, so d_out must be 16-byte aligned and every out_offset a
+   multiple of 16 / sizeof(sample).
+   Checked before any GPU call, ATG_ERR_INVALID: rows NULL with n_rows > 0;
+   d_out NULL with output to write; d_dither NULL with a row that reduces; a
+   channel count outside 1..8 or one that does not fit the operation; an
+   unknown operation or format; a map entry at or above in_channels; a
+   downmix mask that names more channels than present; bits per sample
+   outside 1..24; ATG_PCM_S16 output for a row of more than 16 bits; a source
+   pointer off its sample size or NULL with frames; window_offset != 0; a
+   misaligned d_out or out_offset; output rows that overlap; a dither range
+   that passes dither_bytes.  ATG_ERR_CAPACITY: an output range that passes
+   out_cap_samples.  Nothing is launched for n_rows == 0 or when every row is
+   empty.  `stream` is a hipStream_t (NULL = default stream); it is
+   synchronised before the call returns. */
+atg_status atg_pcm_chain_device(const atg_pcm_chain_row *rows, uint32_t n_rows, void *d_out,
+                                atg_pcm_format out_format, uint64_t out_cap_samples,
+                                const uint8_t *d_dither, uint64_t dither_bytes, void *stream);
+
+/* The same for host memory, staged through `device`: src.d_pcm, out and
+   dither are host pointers.  Every source goes up at its own address modulo
+   16 and `out` goes up whole before the launch and comes back whole after
+   it, so only the rows' ranges of it change. */
+atg_status atg_pcm_chain_host(int device, const atg_pcm_chain_row *rows, uint32_t n_rows,
+                              void *out, atg_pcm_format out_format, uint64_t out_cap_samples,
+                              const uint8_t *dither, uint64_t dither_bytes);
+
+/* Samples per tile on a row's wider side: a tile is 8 * (tile_samples / (8 *
+   max(in_channels, out_channels))) frames (tests place lengths around it). */
+uint32_t atg_pcm_chain_tile_samples(void);
+
+/* Name ("chain") and milliseconds of the calling thread's last launch;
+   returns the number of entries written, 0 before any launch. */
+int atg_pcm_chain_kernel_times(const char **names, float *ms, int cap);
 
 /* ------------------------------------------------------------------ */
 /* ReplayGain analysis (tracktag/track2track --replay-gain).           */

@@ -14,6 +14,9 @@ find the same names with the same meaning:
   audiotools.AudioFile.convert .. reference audiotools/__init__.py:3760-3774
   audiotools.AudioFile.verify ... reference audiotools/__init__.py:3939-3970
   audiotools.FlacAudio / WaveAudio / ALACAudio (flac.py, wav.py, m4a.py)
+  audiotools.convert_files_batch  track2track's per-file convert() for a batch
+                                  of files, the PCM on the device throughout
+  audiotools.convert_pcm_batch .. PCMConverter for a batch of numpy tracks
 
 track2track's per-file step is `AudioFile.convert(target, FlacAudio, "8")`
 and trackverify's is `AudioFile.verify()`; both run through these classes,
@@ -603,3 +606,5 @@ from .shn import ShortenAudio, InvalidShorten  # noqa: E402,F401
 from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa: E402,F401
                        frame_cmp_value, compare_files_batch, compare_image_batch,
                        find_offset_batch, compare_pcm_batch)
+from .pcmconverter import convert_pcm_batch  # noqa: E402,F401
+from .convert import convert_files_batch  # noqa: E402,F401

@@ -88,6 +88,8 @@ EXPORTS = (
     "atg_pcm_bytes_kernel_times", "atg_aiff_read_info", "atg_au_read_info",
     "atg_pcm_compare_last_error", "atg_pcm_compare_device", "atg_pcm_offset_search_device",
     "atg_pcm_compare_tile_frames", "atg_pcm_compare_kernel_times",
+    "atg_pcm_chain_last_error", "atg_pcm_chain_device", "atg_pcm_chain_host",
+    "atg_pcm_chain_tile_samples", "atg_pcm_chain_kernel_times",
 )
 
 CONV_BPS, CONV_DOWNMIX, CONV_AVERAGE = 0, 1, 2
@@ -479,6 +481,17 @@ class PcmCmpResult(ctypes.Structure):
 
 
 PCM_NO_MISMATCH = (1 << 64) - 1
+
+CHAIN_MAP, CHAIN_DOWNMIX, CHAIN_AVERAGE, CHAIN_DOWNMIX_AVERAGE = range(4)
+CHAIN_SILENT = 0xFF
+
+
+class PcmChainRow(ctypes.Structure):
+    """atg_pcm_chain_row: one track of a converter-chain call"""
+    _fields_ = [("src", PcmView), ("in_channels", c_u32), ("out_channels", c_u32),
+                ("channel_op", c_u32), ("channel_mask", c_u32), ("map", ctypes.c_uint8 * 8),
+                ("in_bps", c_u32), ("out_bps", c_u32), ("out_offset", c_u64),
+                ("dither_bit0", c_u64)]
 
 
 class AiffInfo(ctypes.Structure):
@@ -885,6 +898,17 @@ def load_library():
         lib.atg_resample_kernel_times.argtypes = [
             ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
         lib.atg_resample_kernel_times.restype = ctypes.c_int
+        lib.atg_pcm_chain_last_error.restype = ctypes.c_char_p
+        lib.atg_pcm_chain_device.argtypes = [ctypes.POINTER(PcmChainRow), c_u32, P, ctypes.c_int,
+                                             c_u64, P, c_u64, P]
+        lib.atg_pcm_chain_device.restype = ctypes.c_int
+        lib.atg_pcm_chain_host.argtypes = [ctypes.c_int, ctypes.POINTER(PcmChainRow), c_u32, P,
+                                           ctypes.c_int, c_u64, P, c_u64]
+        lib.atg_pcm_chain_host.restype = ctypes.c_int
+        lib.atg_pcm_chain_tile_samples.restype = c_u32
+        lib.atg_pcm_chain_kernel_times.argtypes = [
+            ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
+        lib.atg_pcm_chain_kernel_times.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -2602,6 +2626,74 @@ def pcm_compare_kernel_times():
     names = (ctypes.c_char_p * 2)()
     ms = (ctypes.c_float * 2)()
     k = lib.atg_pcm_compare_kernel_times(names, ms, 2)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+# ------------------------------------------------- converter chain (pcm_chain.hip)
+def pcm_chain_row(src, in_channels, out_channels, in_bps, out_bps, out_offset,
+                  channel_op=CHAIN_MAP, channel_map=None, channel_mask=0, dither_bit0=0):
+    """PcmChainRow over the PcmView `src`; channel_map (MAP): per output
+    channel an input channel or None for silence, default the identity"""
+    r = PcmChainRow()
+    r.src = src
+    r.in_channels, r.out_channels = in_channels, out_channels
+    r.channel_op, r.channel_mask = channel_op, channel_mask
+    if channel_map is None:
+        channel_map = list(range(out_channels))
+    for k in range(8):
+        m = channel_map[k] if k < len(channel_map) else None
+        r.map[k] = CHAIN_SILENT if m is None else m
+    r.in_bps, r.out_bps = in_bps, out_bps
+    r.out_offset, r.dither_bit0 = out_offset, dither_bit0
+    return r
+
+
+def _chain_check(lib, st):
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_pcm_chain_last_error().decode("utf-8", "replace"))
+
+
+def pcm_chain_device(rows, d_out, out_fmt, out_cap_samples, d_dither=None, dither_bytes=0):
+    """every PcmChainRow converted in one launch, device memory in and out
+    (atg_pcm_chain_device)"""
+    lib = load_library()
+    arr = (PcmChainRow * max(1, len(rows)))(*rows)
+    _chain_check(lib, lib.atg_pcm_chain_device(
+        arr, len(rows), ctypes.c_void_p(d_out), out_fmt, out_cap_samples,
+        ctypes.c_void_p(d_dither) if d_dither else None, dither_bytes, None))
+
+
+def pcm_chain_host(rows, out, dither=b"", device=None):
+    """the same for host memory (atg_pcm_chain_host): the rows' src.d_pcm are
+    host addresses (of arrays the caller keeps alive), `out` an int16 or
+    int32 numpy array of which only the rows' ranges change"""
+    lib = load_library()
+    arr = (PcmChainRow * max(1, len(rows)))(*rows)
+    d = np.frombuffer(bytes(dither), dtype=np.uint8) if len(dither) else None
+    _chain_check(lib, lib.atg_pcm_chain_host(
+        default_device() if device is None else device, arr, len(rows),
+        out.ctypes.data_as(ctypes.c_void_p), PCM_S16 if out.dtype == np.int16 else PCM_S32,
+        len(out), d.ctypes.data_as(ctypes.c_void_p) if d is not None else None,
+        0 if d is None else len(d)))
+    return out
+
+
+def pcm_chain_tile_samples():
+    """samples per tile of the chain kernel, on a row's wider side"""
+    return int(load_library().atg_pcm_chain_tile_samples())
+
+
+def pcm_chain_tile_frames(in_channels, out_channels):
+    """PCM frames per tile of a row with these channel counts"""
+    return 8 * (pcm_chain_tile_samples() // (8 * max(in_channels, out_channels)))
+
+
+def pcm_chain_kernel_times():
+    """{"chain": ms} of this thread's last launch"""
+    lib = load_library()
+    names = (ctypes.c_char_p * 1)()
+    ms = (ctypes.c_float * 1)()
+    k = lib.atg_pcm_chain_kernel_times(names, ms, 1)
     return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 

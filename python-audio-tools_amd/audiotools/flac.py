@@ -180,6 +180,63 @@ def _set_comment(body, key, value):
     return b"".join(out)
 
 
+def finish_image(data, offsets, channels, bits_per_sample, channel_mask, interval):
+    """the encoder's .flac image -> the file from_pcm leaves: a SEEKTABLE of
+    one point per `interval` PCM frames from the encoder's frame `offsets`,
+    the WAVEFORMATEXTENSIBLE_CHANNEL_MASK comment for more than 2 channels or
+    16 bits, and the growth taken out of PADDING"""
+    blocks, frames_at = _blocks(data)
+    old_len = frames_at - 4
+    si_body = blocks[0][1]
+    total = int.from_bytes(si_body[13:18], "big") & ((1 << 36) - 1)
+    _add_block(blocks, (SEEKTABLE, _seektable_body(
+        seektable_points(offsets, total, interval))))
+    if (channels > 2 or bits_per_sample > 16) and channel_mask:
+        for i, (t, body) in enumerate(blocks):
+            if t == VORBIS_COMMENT:
+                blocks[i] = (t, _set_comment(body, u"WAVEFORMATEXTENSIBLE_CHANNEL_MASK",
+                                             u"0x%.4X" % channel_mask))
+                break
+    # update_metadata (flac.py:1389-1427): absorb the growth in PADDING
+    new_len = sum(4 + len(b) for _, b in blocks)
+    delta = new_len - old_len
+    pads = [i for i, (t, _) in enumerate(blocks) if t == PADDING]
+    if pads and delta <= sum(len(blocks[i][1]) for i in pads):
+        for i in pads:
+            plen = len(blocks[i][1])
+            if delta > 0:
+                take = min(delta, plen)
+                blocks[i] = (PADDING, b"\0" * (plen - take))
+                delta -= take
+            elif delta < 0:
+                blocks[i] = (PADDING, b"\0" * (plen - delta))
+                delta = 0
+            else:
+                break
+    # with too little padding the metadata grows and the frames move
+    return _build(blocks) + data[frames_at:]
+
+
+def target_layout(filename, channels, channel_mask):
+    """from_pcm's checks of the stream to encode -> the channel mask it
+    writes; UnsupportedChannelCount / UnsupportedChannelMask otherwise"""
+    if channels > 8:
+        raise UnsupportedChannelCount(filename, channels)
+    if int(channel_mask) == 0:
+        return _DEFAULT_MASKS.get(channels, 0)
+    if int(channel_mask) not in _VALID_MASKS:
+        raise UnsupportedChannelMask(filename, int(channel_mask))
+    return int(channel_mask)
+
+
+def padding_for(total_pcm_frames, interval):
+    """from_pcm's PADDING: room for the SEEKTABLE the frame count implies"""
+    if total_pcm_frames is None:
+        return 4096
+    expected = total_pcm_frames // interval + (1 if total_pcm_frames % interval else 0)
+    return 4096 + 4 + expected * 18
+
+
 class FlacAudio(AudioFile):
     NAME = "flac"
     SUFFIX = "flac"
@@ -280,58 +337,17 @@ class FlacAudio(AudioFile):
         from .encoders import encode_flac
         if compression is None or compression not in cls.COMPRESSION_MODES:
             compression = DEFAULT_COMPRESSION
-        if pcmreader.channels > 8:
-            raise UnsupportedChannelCount(filename, pcmreader.channels)
-        if int(pcmreader.channel_mask) == 0:
-            channel_mask = _DEFAULT_MASKS.get(pcmreader.channels, 0)
-        elif int(pcmreader.channel_mask) not in _VALID_MASKS:
-            raise UnsupportedChannelMask(filename, int(pcmreader.channel_mask))
-        else:
-            channel_mask = int(pcmreader.channel_mask)
+        channel_mask = target_layout(filename, pcmreader.channels, pcmreader.channel_mask)
         interval = pcmreader.sample_rate * 10
-        if total_pcm_frames is not None:
-            expected = total_pcm_frames // interval + (1 if total_pcm_frames % interval else 0)
-            padding_size = 4096 + 4 + expected * 18
-        else:
-            padding_size = 4096
+        padding_size = padding_for(total_pcm_frames, interval)
         try:
             offsets = (encode_flac if encoding_function is None else encoding_function)(
                 filename, pcmreader=BufferedPCMReader(pcmreader), padding_size=padding_size,
                 **COMPRESSION_PRESETS[compression])
             with open(filename, "rb") as f:
                 data = f.read()
-            blocks, frames_at = _blocks(data)
-            old_len = frames_at - 4
-            si_body = blocks[0][1]
-            total = int.from_bytes(si_body[13:18], "big") & ((1 << 36) - 1)
-            _add_block(blocks, (SEEKTABLE, _seektable_body(
-                seektable_points(offsets, total, interval))))
-            if (pcmreader.channels > 2 or pcmreader.bits_per_sample > 16) and channel_mask:
-                for i, (t, body) in enumerate(blocks):
-                    if t == VORBIS_COMMENT:
-                        blocks[i] = (t, _set_comment(body, u"WAVEFORMATEXTENSIBLE_CHANNEL_MASK",
-                                                     u"0x%.4X" % channel_mask))
-                        break
-            # update_metadata (flac.py:1389-1427): absorb the growth in PADDING
-            new_len = sum(4 + len(b) for _, b in blocks)
-            delta = new_len - old_len
-            pads = [i for i, (t, _) in enumerate(blocks) if t == PADDING]
-            if pads and delta <= sum(len(blocks[i][1]) for i in pads):
-                for i in pads:
-                    plen = len(blocks[i][1])
-                    if delta > 0:
-                        take = min(delta, plen)
-                        blocks[i] = (PADDING, b"\0" * (plen - take))
-                        delta -= take
-                    elif delta < 0:
-                        blocks[i] = (PADDING, b"\0" * (plen - delta))
-                        delta = 0
-                    else:
-                        break
-                out = _build(blocks) + data[frames_at:]
-            else:
-                # padding too small: the metadata grows and the frames move
-                out = _build(blocks) + data[frames_at:]
+            out = finish_image(data, offsets, pcmreader.channels, pcmreader.bits_per_sample,
+                               channel_mask, interval)
             with open(filename, "wb") as f:
                 f.write(out)
             return cls(filename)
