@@ -28,70 +28,6 @@ ATG_ERR_CAPACITY = -5
 PCM_S16 = 0
 PCM_S32 = 1
 
-# every function include/atgpu.h declares (tests check the .so exports them)
-EXPORTS = (
-    "atg_abi_version", "atg_last_error", "atg_engine_create", "atg_engine_create_ex",
-    "atg_engine_destroy", "atg_flac_batch_bounds", "atg_flac_encode_host",
-    "atg_flac_encode_host_async", "atg_flac_encode_host_wait",
-    "atg_flac_encode_device", "atg_flac_encode_device_async", "atg_flac_encode_wait",
-    "atg_engine_kernel_times", "atg_engine_set_host_chunk_bytes", "atg_engine_set_inflight",
-    "atg_engine_inflight", "atg_pick_device", "atg_visible_devices",
-    "atg_host_gather", "atg_replaygain_rb_factor",
-    "atg_flac_encode_frames",
-    "atg_flac_max_frames_bytes", "atg_flac_stream_header", "atg_host_alloc",
-    "atg_flac_encode_frames_batch", "atg_service_connect", "atg_service_close",
-    "atg_service_last_error", "atg_service_encode_frames",
-    "atg_host_free", "atg_device_alloc",
-    "atg_device_free", "atg_copy_to_device", "atg_copy_device", "atg_copy_to_host",
-    "atg_flac_read_metadata", "atg_decoder_create", "atg_decoder_destroy",
-    "atg_decoder_last_error", "atg_flac_decode_host", "atg_flac_decode_fetch",
-    "atg_flac_decode_device", "atg_flac_decode_device_async", "atg_flac_decode_wait",
-    "atg_decoder_kernel_times", "atg_decoder_set_inflight",
-    "atg_decoder_set_frame_hypothesis", "atg_decoder_frame_hypothesis_redos",
-    "atg_oggflac_read_info", "atg_oggflac_decode_host", "atg_oggflac_decode_device",
-    "atg_oggflac_decode_fetch",
-    "atg_oggflac_batch_bounds", "atg_oggflac_encode_device", "atg_oggflac_encode_host",
-    "atg_pcm_convert_last_error", "atg_pcm_convert_out_channels",
-    "atg_pcm_convert_device", "atg_pcm_convert_host",
-    "atg_replaygain_last_error", "atg_replaygain_device", "atg_replaygain_hist_gain",
-    "atg_replaygain_set_warmup", "atg_replaygain_fallback_tracks",
-    "atg_replaygain_bound", "atg_replaygain_rebinned_windows",
-    "atg_replaygain_multiplier", "atg_pcm_apply_gain_device", "atg_pcm_apply_gain_host",
-    "atg_alac_last_error", "atg_alac_encoder_create", "atg_alac_encoder_destroy",
-    "atg_alac_batch_bounds", "atg_alac_encode_device", "atg_alac_encode_host",
-    "atg_alac_encoder_kernel_times", "atg_alac_decoder_last_error", "atg_alac_read_info",
-    "atg_alac_decoder_create", "atg_alac_decoder_destroy", "atg_alac_decode_host",
-    "atg_alac_decode_fetch", "atg_alac_decode_device", "atg_alac_decoder_kernel_times",
-    "atg_tta_last_error", "atg_tta_encoder_create", "atg_tta_encoder_destroy",
-    "atg_tta_encode_device", "atg_tta_encode_host", "atg_tta_encoder_kernel_times",
-    "atg_tta_decoder_last_error", "atg_tta_read_info", "atg_tta_decoder_create",
-    "atg_tta_decoder_destroy", "atg_tta_decode_host", "atg_tta_decode_fetch",
-    "atg_tta_decode_device", "atg_tta_decoder_kernel_times",
-    "atg_wv_decoder_last_error", "atg_wv_read_info", "atg_wv_decoder_create",
-    "atg_wv_decoder_destroy", "atg_wv_decode_host", "atg_wv_decode_fetch",
-    "atg_wv_decode_device", "atg_wv_decoder_kernel_times",
-    "atg_wv_encoder_last_error", "atg_wv_encoder_create", "atg_wv_encoder_destroy",
-    "atg_wv_encode_device", "atg_wv_encode_host", "atg_wv_encoder_kernel_times",
-    "atg_shn_encoder_last_error", "atg_shn_encoder_create", "atg_shn_encoder_destroy",
-    "atg_shn_encode_device", "atg_shn_encode_host", "atg_shn_encoder_kernel_times",
-    "atg_shn_decoder_last_error", "atg_shn_read_info", "atg_shn_decoder_create",
-    "atg_shn_decoder_destroy", "atg_shn_decoder_set_index_walk", "atg_shn_decode_host",
-    "atg_shn_decode_fetch", "atg_shn_decode_fetch_verbatim", "atg_shn_decode_fetch_blocks",
-    "atg_shn_decode_device",
-    "atg_shn_decoder_kernel_times",
-    "atg_resample_last_error", "atg_resample_output_frames", "atg_resample_device",
-    "atg_resample_host", "atg_resample_read_sizes", "atg_resample_kernel_times",
-    "atg_accuraterip_last_error", "atg_accuraterip_device", "atg_accuraterip_host",
-    "atg_accuraterip_tile_frames",
-    "atg_pcm_bytes_last_error", "atg_pcm_unpack_device", "atg_pcm_pack_device",
-    "atg_pcm_unpack_host", "atg_pcm_pack_host", "atg_pcm_bytes_tile_samples",
-    "atg_pcm_bytes_kernel_times", "atg_aiff_read_info", "atg_au_read_info",
-    "atg_pcm_compare_last_error", "atg_pcm_compare_device", "atg_pcm_offset_search_device",
-    "atg_pcm_compare_tile_frames", "atg_pcm_compare_kernel_times",
-    "atg_pcm_chain_last_error", "atg_pcm_chain_device", "atg_pcm_chain_host",
-    "atg_pcm_chain_tile_samples", "atg_pcm_chain_kernel_times",
-)
-
 CONV_BPS, CONV_DOWNMIX, CONV_AVERAGE = 0, 1, 2
 
 c_u32, c_i32, c_u64 = ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64
@@ -530,6 +466,248 @@ class ATGError(RuntimeError):
         self.message = message
 
 
+# ---- the C ABI: one row per function include/atgpu.h declares ----------------
+# name -> (restype, argtypes).  load_library() applies the rows; EXPORTS is
+# their names; tests/test_signatures.py holds every row against the header.
+c_int, c_f64, c_str = ctypes.c_int, ctypes.c_double, ctypes.c_char_p
+P = ctypes.c_void_p
+ptr = ctypes.POINTER
+PP, P32, P64 = ptr(P), ptr(c_u32), ptr(c_u64)
+
+# the shapes many components share
+_CREATE = (c_int, (c_int, PP))
+_DESTROY = (None, (P,))
+_LAST_ERROR = (c_str, ())
+_KERNEL_TIMES = (c_int, (P, ptr(c_str), ptr(ctypes.c_float), c_int))
+_THREAD_TIMES = (c_int, _KERNEL_TIMES[1][1:])   # the handle-less components
+_TILE = (c_u32, ())
+_SET_U32 = (c_int, (P, c_u32))
+_SET_INT = (c_int, (P, c_int))
+_COPY = (c_int, (P, P, P, c_u64))
+_FETCH_PCM = (c_int, (P, P, c_u64))                 # handle, dst, cap
+_FETCH_FRAMES = (c_int, (P, P, c_u64, P, P, c_u64))  # + two per-frame arrays, cap
+
+
+def _read_info(info, *tables):
+    """..._read_info: image, len, info struct, then the tables it fills"""
+    return (c_int, (c_str, c_u64, ptr(info)) + tables)
+
+
+def _decode(tracks, results, *totals):
+    """..._decode_host / ..._decode_device: handle, data, len, tracks, n, results, totals"""
+    return (c_int, (P, P, c_u64, tracks, c_u32, results) + totals)
+
+
+# handle, options, pcm, format, tracks, n, channels, bits, rate, out, cap
+_FLAC_ENCODE = (P, ptr(FlacOptions), P, c_int, ptr(Track), c_u32, c_u32, c_u32, c_u32, P, c_u64)
+_OGGFLAC_ENCODE = (c_int, _FLAC_ENCODE[:2] + (ptr(OggFlacEncOptions),) + _FLAC_ENCODE[2:] +
+                   (ptr(OggFlacTrackResult), P, P))
+_FLAC_FRAMES = (c_int, (P, ptr(FlacOptions), P, c_int, c_u64, P, c_u64, c_u32, c_u32, c_u32,
+                        c_u64, P, c_u64, P64, P))
+_ALAC_ENCODE = (c_int, (P, ptr(AlacOptions), P, c_int, ptr(Track), c_u32, c_u32, c_u32, P,
+                        c_u64, ptr(AlacTrackResult), P))
+_TTA_ENCODE = (c_int, (P, P, c_int, ptr(Track), c_u32, c_u32, c_u32, c_u32, P, c_u64,
+                       ptr(TtaTrackResult), P, c_u64, P64))
+_WV_ENCODE = (c_int, (P, P, c_int, ptr(Track), c_u32, c_u32, c_u32, c_u32, c_u32,
+                      ptr(WvEncOptions), P, c_u64, ptr(WvTrackResult), P, c_u64, P64))
+_SHN_ENCODE = (c_int, (P, P, c_int, ptr(Track), P, c_u32, c_u32, c_u32, ptr(ShnOptions), P,
+                       c_u64, ptr(ShnTrackResult), P64))
+
+SIGNATURES = {
+    "atg_abi_version": (c_int, ()),
+    "atg_last_error": _LAST_ERROR,
+    "atg_pick_device": (c_int, ()),
+    "atg_visible_devices": (c_int, ()),
+    # engine, FLAC and Ogg FLAC encode
+    "atg_engine_create": _CREATE,
+    "atg_engine_create_ex": (c_int, (c_int, c_u32, PP)),
+    "atg_engine_destroy": _DESTROY,
+    "atg_engine_kernel_times": _KERNEL_TIMES,
+    "atg_engine_set_host_chunk_bytes": (c_int, (P, c_u64)),
+    "atg_engine_set_inflight": _SET_U32,
+    "atg_engine_inflight": (c_u32, (P,)),
+    "atg_flac_batch_bounds": (c_int, (ptr(FlacOptions), ptr(Track), c_u32, c_u32, c_u32,
+                                      P64, P64)),
+    "atg_flac_encode_host": (c_int, _FLAC_ENCODE + (ptr(TrackResult), P, P)),
+    "atg_flac_encode_host_async": (c_int, _FLAC_ENCODE + (ptr(TrackResult), P, P, P64)),
+    "atg_flac_encode_host_wait": (c_int, (P, c_u64)),
+    "atg_flac_encode_device": (c_int, _FLAC_ENCODE + (ptr(TrackResult),)),
+    "atg_flac_encode_device_async": (c_int, _FLAC_ENCODE + (P64,)),
+    "atg_flac_encode_wait": (c_int, (P, c_u64, ptr(TrackResult))),
+    "atg_flac_encode_frames": _FLAC_FRAMES,
+    "atg_flac_encode_frames_batch": (c_int, _FLAC_ENCODE[:4] + (P,) + _FLAC_ENCODE[5:] +
+                                     (P64, P64, P32)),
+    "atg_flac_max_frames_bytes": (c_u64, (ptr(FlacOptions), c_u64, P, c_u64, c_u32, c_u32)),
+    "atg_flac_stream_header": (c_u64, (ptr(FlacOptions), c_u32, c_u32, c_u32, c_u64, c_u32,
+                                       c_u32, P, P, c_u64)),
+    "atg_service_connect": (c_int, (c_int, c_int, PP)),
+    "atg_service_close": _DESTROY,
+    "atg_service_last_error": _LAST_ERROR,
+    "atg_service_encode_frames": _FLAC_FRAMES,
+    "atg_oggflac_batch_bounds": (c_int, (ptr(FlacOptions), ptr(OggFlacEncOptions), ptr(Track),
+                                         c_u32, c_u32, c_u32, P64, P64)),
+    "atg_oggflac_encode_device": _OGGFLAC_ENCODE,
+    "atg_oggflac_encode_host": _OGGFLAC_ENCODE,
+    # memory
+    "atg_host_alloc": (c_int, (c_u64, PP)),
+    "atg_host_free": (None, (P,)),
+    "atg_host_gather": (c_int, (P, PP, P64, c_u64, c_u32)),
+    "atg_device_alloc": (c_int, (P, c_u64, PP)),
+    "atg_device_free": (c_int, (P, P)),
+    "atg_copy_to_device": _COPY,
+    "atg_copy_device": _COPY,
+    "atg_copy_to_host": _COPY,
+    # FLAC and Ogg FLAC decode
+    "atg_flac_read_metadata": _read_info(StreamInfo, P, c_u32),
+    "atg_decoder_create": _CREATE,
+    "atg_decoder_destroy": _DESTROY,
+    "atg_decoder_last_error": _LAST_ERROR,
+    "atg_decoder_kernel_times": _KERNEL_TIMES,
+    "atg_decoder_set_inflight": _SET_U32,
+    "atg_decoder_set_frame_hypothesis": _SET_INT,
+    "atg_decoder_frame_hypothesis_redos": (c_u64, (P,)),
+    "atg_flac_decode_host": _decode(ptr(DecTrack), ptr(DecResult), P64, P64),
+    "atg_flac_decode_fetch": _FETCH_FRAMES,
+    "atg_flac_decode_device": _decode(ptr(DecTrack), ptr(DecResult), PP, P64),
+    "atg_flac_decode_device_async": (c_int, (P, P, c_u64, ptr(DecTrack), c_u32, P64)),
+    "atg_flac_decode_wait": (c_int, (P, c_u64, ptr(DecResult), PP, P64)),
+    "atg_oggflac_read_info": _read_info(OggFlacInfo),
+    "atg_oggflac_decode_host": _decode(ptr(OggFlacDecTrack), ptr(OggFlacDecResult), P64, P64),
+    "atg_oggflac_decode_fetch": _FETCH_FRAMES,
+    "atg_oggflac_decode_device": _decode(ptr(OggFlacDecTrack), ptr(OggFlacDecResult), PP, P64),
+    # PCM conversion, ReplayGain
+    "atg_pcm_convert_last_error": _LAST_ERROR,
+    "atg_pcm_convert_out_channels": (c_u32, (c_int, c_u32)),
+    "atg_pcm_convert_device": (c_int, (c_int, P, P, c_u64, c_u32, c_u32, c_u32, c_u32, P,
+                                       c_u64, P)),
+    "atg_pcm_convert_host": (c_int, (c_int, c_int, P, P, c_u64, c_u32, c_u32, c_u32, c_u32, P,
+                                     c_u64, c_u64)),
+    "atg_replaygain_last_error": _LAST_ERROR,
+    "atg_replaygain_device": (c_int, (P, ptr(RgTrack), c_u32, c_u32, ptr(RgResult), P,
+                                      ptr(c_f64), P)),
+    "atg_replaygain_bound": (c_int, (c_u32, ptr(c_f64))),
+    "atg_replaygain_rb_factor": (c_f64, ()),
+    "atg_replaygain_rebinned_windows": (c_u64, ()),
+    "atg_replaygain_set_warmup": (None, (c_int,)),
+    "atg_replaygain_fallback_tracks": (c_u32, ()),
+    "atg_replaygain_hist_gain": (c_int, (P, c_u32, ptr(c_f64), P)),
+    "atg_replaygain_multiplier": (c_f64, (c_f64, c_f64)),
+    "atg_pcm_apply_gain_device": (c_int, (P, P, c_u64, c_u32, c_u32, c_f64, c_u32, P, c_u64,
+                                          P)),
+    "atg_pcm_apply_gain_host": (c_int, (c_int, P, P, c_u64, c_u32, c_u32, c_f64, c_u32, P,
+                                        c_u64, c_u64)),
+    # AccurateRip
+    "atg_accuraterip_last_error": _LAST_ERROR,
+    "atg_accuraterip_device": (c_int, (P, c_int, ptr(ArTrack), c_u32, c_u32, ptr(ArResult),
+                                       P, P)),
+    "atg_accuraterip_host": (c_int, (c_int, P, c_int, c_u64, ptr(ArTrack), c_u32, c_u32,
+                                     ptr(ArResult), P)),
+    "atg_accuraterip_tile_frames": _TILE,
+    # packed PCM bytes, AIFF and Sun AU headers
+    "atg_pcm_bytes_last_error": _LAST_ERROR,
+    "atg_pcm_unpack_device": (c_int, (P, c_u64, PcmLayout, ptr(PcmRun), c_u32, P, c_int,
+                                      c_u64, P)),
+    "atg_pcm_pack_device": (c_int, (P, c_int, c_u64, PcmLayout, ptr(PcmRun), c_u32, P, c_u64,
+                                    P)),
+    "atg_pcm_unpack_host": (c_int, (c_int, P, c_u64, PcmLayout, ptr(PcmRun), c_u32, P, c_int,
+                                    c_u64)),
+    "atg_pcm_pack_host": (c_int, (c_int, P, c_int, c_u64, PcmLayout, ptr(PcmRun), c_u32, P,
+                                  c_u64)),
+    "atg_pcm_bytes_tile_samples": _TILE,
+    "atg_pcm_bytes_kernel_times": _THREAD_TIMES,
+    "atg_aiff_read_info": _read_info(AiffInfo),
+    "atg_au_read_info": _read_info(AuInfo),
+    # PCM comparison, converter chain
+    "atg_pcm_compare_last_error": _LAST_ERROR,
+    "atg_pcm_compare_device": (c_int, (ptr(PcmPair), c_u32, ptr(PcmCmpResult), P)),
+    "atg_pcm_offset_search_device": (c_int, (ptr(PcmPair), c_u32, c_u32, ptr(PcmCmpResult),
+                                             P)),
+    "atg_pcm_compare_tile_frames": _TILE,
+    "atg_pcm_compare_kernel_times": _THREAD_TIMES,
+    "atg_pcm_chain_last_error": _LAST_ERROR,
+    "atg_pcm_chain_device": (c_int, (ptr(PcmChainRow), c_u32, P, c_int, c_u64, P, c_u64, P)),
+    "atg_pcm_chain_host": (c_int, (c_int, ptr(PcmChainRow), c_u32, P, c_int, c_u64, P, c_u64)),
+    "atg_pcm_chain_tile_samples": _TILE,
+    "atg_pcm_chain_kernel_times": _THREAD_TIMES,
+    # ALAC
+    "atg_alac_last_error": _LAST_ERROR,
+    "atg_alac_encoder_create": _CREATE,
+    "atg_alac_encoder_destroy": _DESTROY,
+    "atg_alac_encoder_kernel_times": _KERNEL_TIMES,
+    "atg_alac_batch_bounds": (c_int, (P, ptr(AlacOptions), ptr(Track), c_u32, c_u32, c_u32,
+                                      P64, P64)),
+    "atg_alac_encode_device": _ALAC_ENCODE,
+    "atg_alac_encode_host": _ALAC_ENCODE,
+    "atg_alac_read_info": _read_info(AlacInfo, P, c_u32, P, c_u32, P32),
+    "atg_alac_decoder_last_error": _LAST_ERROR,
+    "atg_alac_decoder_create": _CREATE,
+    "atg_alac_decoder_destroy": _DESTROY,
+    "atg_alac_decoder_kernel_times": _KERNEL_TIMES,
+    "atg_alac_decode_host": _decode(ptr(AlacDecTrack), ptr(AlacDecResult), P64, P64),
+    "atg_alac_decode_fetch": _FETCH_FRAMES,
+    "atg_alac_decode_device": _decode(ptr(AlacDecTrack), ptr(AlacDecResult), PP, P64),
+    # True Audio
+    "atg_tta_last_error": _LAST_ERROR,
+    "atg_tta_encoder_create": _CREATE,
+    "atg_tta_encoder_destroy": _DESTROY,
+    "atg_tta_encoder_kernel_times": _KERNEL_TIMES,
+    "atg_tta_encode_device": _TTA_ENCODE,
+    "atg_tta_encode_host": _TTA_ENCODE,
+    "atg_tta_read_info": _read_info(TtaInfo, P, c_u32, P32),
+    "atg_tta_decoder_last_error": _LAST_ERROR,
+    "atg_tta_decoder_create": _CREATE,
+    "atg_tta_decoder_destroy": _DESTROY,
+    "atg_tta_decoder_kernel_times": _KERNEL_TIMES,
+    "atg_tta_decode_host": _decode(ptr(TtaDecTrack), ptr(TtaDecResult), P64),
+    "atg_tta_decode_fetch": _FETCH_PCM,
+    "atg_tta_decode_device": _decode(ptr(TtaDecTrack), ptr(TtaDecResult), PP, P64),
+    # WavPack
+    "atg_wv_read_info": _read_info(WvInfo, P, c_u32, P32),
+    "atg_wv_decoder_last_error": _LAST_ERROR,
+    "atg_wv_decoder_create": _CREATE,
+    "atg_wv_decoder_destroy": _DESTROY,
+    "atg_wv_decoder_kernel_times": _KERNEL_TIMES,
+    "atg_wv_decode_host": _decode(P, P, P64),
+    "atg_wv_decode_fetch": _FETCH_PCM,
+    "atg_wv_decode_device": _decode(P, P, PP, P64),
+    "atg_wv_encoder_last_error": _LAST_ERROR,
+    "atg_wv_encoder_create": _CREATE,
+    "atg_wv_encoder_destroy": _DESTROY,
+    "atg_wv_encoder_kernel_times": _KERNEL_TIMES,
+    "atg_wv_encode_device": _WV_ENCODE,
+    "atg_wv_encode_host": _WV_ENCODE,
+    # resampler
+    "atg_resample_last_error": _LAST_ERROR,
+    "atg_resample_output_frames": (c_u64, (c_u64, c_u32, c_u32, c_u32)),
+    "atg_resample_device": (c_int, (ptr(RsTrack), c_u32, c_u32, c_u32, P, P, c_u64, P, P, P)),
+    "atg_resample_host": (c_int, (c_int, ptr(RsTrack), c_u32, c_u32, c_u32, P, c_u64, P, c_u64,
+                                  P, P)),
+    "atg_resample_read_sizes": (ctypes.c_int64, (c_u64, c_u32, c_u32, c_u32, P, c_u64, P,
+                                                 c_u64)),
+    "atg_resample_kernel_times": _THREAD_TIMES,
+    # Shorten
+    "atg_shn_encoder_last_error": _LAST_ERROR,
+    "atg_shn_encoder_create": _CREATE,
+    "atg_shn_encoder_destroy": _DESTROY,
+    "atg_shn_encoder_kernel_times": _KERNEL_TIMES,
+    "atg_shn_encode_device": _SHN_ENCODE,
+    "atg_shn_encode_host": _SHN_ENCODE,
+    "atg_shn_read_info": _read_info(ShnInfo),
+    "atg_shn_decoder_last_error": _LAST_ERROR,
+    "atg_shn_decoder_create": _CREATE,
+    "atg_shn_decoder_destroy": _DESTROY,
+    "atg_shn_decoder_kernel_times": _KERNEL_TIMES,
+    "atg_shn_decoder_set_index_walk": _SET_INT,
+    "atg_shn_decode_host": _decode(ptr(ShnDecTrack), ptr(ShnDecResult), P64),
+    "atg_shn_decode_fetch": _FETCH_PCM,
+    "atg_shn_decode_fetch_verbatim": _FETCH_PCM,
+    "atg_shn_decode_fetch_blocks": (c_int, (P, c_u32, P, c_u64, P64)),
+    "atg_shn_decode_device": _decode(ptr(ShnDecTrack), ptr(ShnDecResult), PP, P64),
+}
+
+# every function include/atgpu.h declares (tests check the .so exports them)
+EXPORTS = tuple(SIGNATURES)
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -545,370 +723,9 @@ def load_library():
                               "`make -C python-audio-tools_amd/csrc` or "
                               "__graft_entry__.build()" % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        P = ctypes.c_void_p
-        lib.atg_abi_version.restype = ctypes.c_int
-        lib.atg_last_error.restype = ctypes.c_char_p
-        lib.atg_engine_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_engine_create.restype = ctypes.c_int
-        lib.atg_engine_create_ex.argtypes = [ctypes.c_int, c_u32, ctypes.POINTER(P)]
-        lib.atg_engine_create_ex.restype = ctypes.c_int
-        lib.atg_engine_destroy.argtypes = [P]
-        lib.atg_engine_destroy.restype = None
-        lib.atg_flac_batch_bounds.argtypes = [
-            ctypes.POINTER(FlacOptions), ctypes.POINTER(Track), c_u32, c_u32, c_u32,
-            ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
-        lib.atg_flac_batch_bounds.restype = ctypes.c_int
-        lib.atg_flac_encode_host.argtypes = [
-            P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, ctypes.POINTER(Track),
-            c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(TrackResult),
-            P, P]
-        lib.atg_flac_encode_host.restype = ctypes.c_int
-        lib.atg_oggflac_batch_bounds.argtypes = [
-            ctypes.POINTER(FlacOptions), ctypes.POINTER(OggFlacEncOptions),
-            ctypes.POINTER(Track), c_u32, c_u32, c_u32, ctypes.POINTER(c_u64),
-            ctypes.POINTER(c_u64)]
-        lib.atg_oggflac_batch_bounds.restype = ctypes.c_int
-        for name in ("atg_oggflac_encode_device", "atg_oggflac_encode_host"):
-            getattr(lib, name).argtypes = [
-                P, ctypes.POINTER(FlacOptions), ctypes.POINTER(OggFlacEncOptions), P,
-                ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32, c_u32, P, c_u64,
-                ctypes.POINTER(OggFlacTrackResult), P, P]
-            getattr(lib, name).restype = ctypes.c_int
-        lib.atg_flac_encode_host_async.argtypes = [
-            P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, ctypes.POINTER(Track),
-            c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(TrackResult),
-            P, P, ctypes.POINTER(c_u64)]
-        lib.atg_flac_encode_host_async.restype = ctypes.c_int
-        lib.atg_flac_encode_host_wait.argtypes = [P, c_u64]
-        lib.atg_flac_encode_host_wait.restype = ctypes.c_int
-        lib.atg_flac_encode_device.argtypes = [
-            P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, ctypes.POINTER(Track),
-            c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(TrackResult)]
-        lib.atg_flac_encode_device.restype = ctypes.c_int
-        lib.atg_flac_encode_device_async.argtypes = [
-            P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, ctypes.POINTER(Track),
-            c_u32, c_u32, c_u32, c_u32, P, c_u64, ctypes.POINTER(c_u64)]
-        lib.atg_flac_encode_device_async.restype = ctypes.c_int
-        lib.atg_flac_encode_wait.argtypes = [P, c_u64, ctypes.POINTER(TrackResult)]
-        lib.atg_flac_encode_wait.restype = ctypes.c_int
-        lib.atg_flac_encode_frames.argtypes = [
-            P, ctypes.POINTER(FlacOptions), P, ctypes.c_int, c_u64, P, c_u64, c_u32, c_u32,
-            c_u32, c_u64, P, c_u64, ctypes.POINTER(c_u64), P]
-        lib.atg_flac_encode_frames.restype = ctypes.c_int
-        lib.atg_flac_max_frames_bytes.argtypes = [ctypes.POINTER(FlacOptions), c_u64, P, c_u64,
-                                                  c_u32, c_u32]
-        lib.atg_flac_max_frames_bytes.restype = c_u64
-        lib.atg_flac_stream_header.argtypes = [ctypes.POINTER(FlacOptions), c_u32, c_u32, c_u32,
-                                               c_u64, c_u32, c_u32, P, P, c_u64]
-        lib.atg_flac_stream_header.restype = c_u64
-        lib.atg_host_alloc.argtypes = [c_u64, ctypes.POINTER(P)]
-        lib.atg_host_alloc.restype = ctypes.c_int
-        lib.atg_host_free.argtypes = [P]
-        lib.atg_host_free.restype = None
-        lib.atg_engine_set_host_chunk_bytes.argtypes = [P, c_u64]
-        lib.atg_engine_set_host_chunk_bytes.restype = ctypes.c_int
-        lib.atg_engine_set_inflight.argtypes = [P, c_u32]
-        lib.atg_engine_set_inflight.restype = ctypes.c_int
-        lib.atg_engine_inflight.argtypes = [P]
-        lib.atg_engine_inflight.restype = c_u32
-        lib.atg_pick_device.argtypes = []
-        lib.atg_pick_device.restype = ctypes.c_int
-        lib.atg_visible_devices.argtypes = []
-        lib.atg_visible_devices.restype = ctypes.c_int
-        lib.atg_engine_kernel_times.argtypes = [
-            P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),
-            ctypes.c_int]
-        lib.atg_engine_kernel_times.restype = ctypes.c_int
-        lib.atg_device_alloc.argtypes = [P, c_u64, ctypes.POINTER(P)]
-        lib.atg_device_alloc.restype = ctypes.c_int
-        lib.atg_device_free.argtypes = [P, P]
-        lib.atg_device_free.restype = ctypes.c_int
-        lib.atg_copy_to_device.argtypes = [P, P, P, c_u64]
-        lib.atg_copy_to_device.restype = ctypes.c_int
-        lib.atg_copy_device.argtypes = [P, P, P, c_u64]
-        lib.atg_copy_device.restype = ctypes.c_int
-        lib.atg_copy_to_host.argtypes = [P, P, P, c_u64]
-        lib.atg_copy_to_host.restype = ctypes.c_int
-        lib.atg_flac_read_metadata.argtypes = [
-            ctypes.c_char_p, c_u64, ctypes.POINTER(StreamInfo), P, c_u32]
-        lib.atg_flac_read_metadata.restype = ctypes.c_int
-        lib.atg_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_decoder_create.restype = ctypes.c_int
-        lib.atg_decoder_destroy.argtypes = [P]
-        lib.atg_decoder_destroy.restype = None
-        lib.atg_decoder_last_error.restype = ctypes.c_char_p
-        lib.atg_flac_decode_host.argtypes = [
-            P, P, c_u64, ctypes.POINTER(DecTrack), c_u32, ctypes.POINTER(DecResult),
-            ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
-        lib.atg_flac_decode_host.restype = ctypes.c_int
-        lib.atg_flac_decode_fetch.argtypes = [P, P, c_u64, P, P, c_u64]
-        lib.atg_flac_decode_fetch.restype = ctypes.c_int
-        lib.atg_flac_decode_device.argtypes = [
-            P, P, c_u64, ctypes.POINTER(DecTrack), c_u32, ctypes.POINTER(DecResult),
-            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_flac_decode_device.restype = ctypes.c_int
-        lib.atg_flac_decode_device_async.argtypes = [
-            P, P, c_u64, ctypes.POINTER(DecTrack), c_u32, ctypes.POINTER(c_u64)]
-        lib.atg_flac_decode_device_async.restype = ctypes.c_int
-        lib.atg_flac_decode_wait.argtypes = [
-            P, c_u64, ctypes.POINTER(DecResult), ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_flac_decode_wait.restype = ctypes.c_int
-        lib.atg_decoder_set_inflight.argtypes = [P, c_u32]
-        lib.atg_decoder_set_inflight.restype = ctypes.c_int
-        lib.atg_decoder_set_frame_hypothesis.argtypes = [P, ctypes.c_int]
-        lib.atg_decoder_set_frame_hypothesis.restype = ctypes.c_int
-        lib.atg_decoder_frame_hypothesis_redos.argtypes = [P]
-        lib.atg_decoder_frame_hypothesis_redos.restype = c_u64
-        lib.atg_decoder_kernel_times.argtypes = [
-            P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),
-            ctypes.c_int]
-        lib.atg_decoder_kernel_times.restype = ctypes.c_int
-        lib.atg_oggflac_read_info.argtypes = [ctypes.c_char_p, c_u64,
-                                              ctypes.POINTER(OggFlacInfo)]
-        lib.atg_oggflac_read_info.restype = ctypes.c_int
-        lib.atg_oggflac_decode_host.argtypes = [
-            P, P, c_u64, ctypes.POINTER(OggFlacDecTrack), c_u32,
-            ctypes.POINTER(OggFlacDecResult), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
-        lib.atg_oggflac_decode_host.restype = ctypes.c_int
-        lib.atg_oggflac_decode_device.argtypes = [
-            P, P, c_u64, ctypes.POINTER(OggFlacDecTrack), c_u32,
-            ctypes.POINTER(OggFlacDecResult), ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_oggflac_decode_device.restype = ctypes.c_int
-        lib.atg_oggflac_decode_fetch.argtypes = [P, P, c_u64, P, P, c_u64]
-        lib.atg_oggflac_decode_fetch.restype = ctypes.c_int
-        lib.atg_pcm_convert_last_error.restype = ctypes.c_char_p
-        lib.atg_pcm_convert_out_channels.argtypes = [ctypes.c_int, c_u32]
-        lib.atg_pcm_convert_out_channels.restype = c_u32
-        lib.atg_pcm_convert_device.argtypes = [
-            ctypes.c_int, P, P, c_u64, c_u32, c_u32, c_u32, c_u32, P, c_u64, P]
-        lib.atg_pcm_convert_device.restype = ctypes.c_int
-        lib.atg_pcm_convert_host.argtypes = [
-            ctypes.c_int, ctypes.c_int, P, P, c_u64, c_u32, c_u32, c_u32, c_u32, P, c_u64,
-            c_u64]
-        lib.atg_pcm_convert_host.restype = ctypes.c_int
-        lib.atg_accuraterip_last_error.restype = ctypes.c_char_p
-        lib.atg_accuraterip_device.argtypes = [
-            P, ctypes.c_int, ctypes.POINTER(ArTrack), c_u32, c_u32, ctypes.POINTER(ArResult),
-            P, P]
-        lib.atg_accuraterip_device.restype = ctypes.c_int
-        lib.atg_accuraterip_host.argtypes = [
-            ctypes.c_int, P, ctypes.c_int, c_u64, ctypes.POINTER(ArTrack), c_u32, c_u32,
-            ctypes.POINTER(ArResult), P]
-        lib.atg_accuraterip_host.restype = ctypes.c_int
-        lib.atg_accuraterip_tile_frames.restype = c_u32
-        lib.atg_pcm_bytes_last_error.restype = ctypes.c_char_p
-        lib.atg_pcm_unpack_device.argtypes = [
-            P, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, ctypes.c_int, c_u64, P]
-        lib.atg_pcm_unpack_device.restype = ctypes.c_int
-        lib.atg_pcm_pack_device.argtypes = [
-            P, ctypes.c_int, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, c_u64, P]
-        lib.atg_pcm_pack_device.restype = ctypes.c_int
-        lib.atg_pcm_unpack_host.argtypes = [
-            ctypes.c_int, P, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P, ctypes.c_int,
-            c_u64]
-        lib.atg_pcm_unpack_host.restype = ctypes.c_int
-        lib.atg_pcm_pack_host.argtypes = [
-            ctypes.c_int, P, ctypes.c_int, c_u64, PcmLayout, ctypes.POINTER(PcmRun), c_u32, P,
-            c_u64]
-        lib.atg_pcm_pack_host.restype = ctypes.c_int
-        lib.atg_pcm_bytes_tile_samples.restype = c_u32
-        lib.atg_pcm_bytes_kernel_times.argtypes = [P, P, ctypes.c_int]
-        lib.atg_pcm_bytes_kernel_times.restype = ctypes.c_int
-        lib.atg_pcm_compare_last_error.restype = ctypes.c_char_p
-        lib.atg_pcm_compare_device.argtypes = [
-            ctypes.POINTER(PcmPair), c_u32, ctypes.POINTER(PcmCmpResult), P]
-        lib.atg_pcm_compare_device.restype = ctypes.c_int
-        lib.atg_pcm_offset_search_device.argtypes = [
-            ctypes.POINTER(PcmPair), c_u32, c_u32, ctypes.POINTER(PcmCmpResult), P]
-        lib.atg_pcm_offset_search_device.restype = ctypes.c_int
-        lib.atg_pcm_compare_tile_frames.restype = c_u32
-        lib.atg_pcm_compare_kernel_times.argtypes = [P, P, ctypes.c_int]
-        lib.atg_pcm_compare_kernel_times.restype = ctypes.c_int
-        lib.atg_aiff_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AiffInfo)]
-        lib.atg_aiff_read_info.restype = ctypes.c_int
-        lib.atg_au_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AuInfo)]
-        lib.atg_au_read_info.restype = ctypes.c_int
-        lib.atg_replaygain_last_error.restype = ctypes.c_char_p
-        lib.atg_replaygain_device.argtypes = [
-            P, ctypes.POINTER(RgTrack), c_u32, c_u32, ctypes.POINTER(RgResult), P,
-            ctypes.POINTER(ctypes.c_double), P]
-        lib.atg_replaygain_device.restype = ctypes.c_int
-        lib.atg_replaygain_hist_gain.argtypes = [P, c_u32, ctypes.POINTER(ctypes.c_double), P]
-        lib.atg_replaygain_hist_gain.restype = ctypes.c_int
-        lib.atg_replaygain_multiplier.argtypes = [ctypes.c_double, ctypes.c_double]
-        lib.atg_replaygain_multiplier.restype = ctypes.c_double
-        lib.atg_pcm_apply_gain_device.argtypes = [
-            P, P, c_u64, c_u32, c_u32, ctypes.c_double, c_u32, P, c_u64, P]
-        lib.atg_pcm_apply_gain_device.restype = ctypes.c_int
-        lib.atg_pcm_apply_gain_host.argtypes = [
-            ctypes.c_int, P, P, c_u64, c_u32, c_u32, ctypes.c_double, c_u32, P, c_u64, c_u64]
-        lib.atg_pcm_apply_gain_host.restype = ctypes.c_int
-        lib.atg_alac_last_error.restype = ctypes.c_char_p
-        lib.atg_alac_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_alac_encoder_create.restype = ctypes.c_int
-        lib.atg_alac_encoder_destroy.argtypes = [P]
-        lib.atg_alac_encoder_destroy.restype = None
-        lib.atg_alac_batch_bounds.argtypes = [
-            P, ctypes.POINTER(AlacOptions), ctypes.POINTER(Track), c_u32, c_u32, c_u32,
-            ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
-        lib.atg_alac_batch_bounds.restype = ctypes.c_int
-        lib.atg_alac_encode_device.argtypes = [
-            P, ctypes.POINTER(AlacOptions), P, ctypes.c_int, ctypes.POINTER(Track), c_u32,
-            c_u32, c_u32, P, c_u64, ctypes.POINTER(AlacTrackResult), P]
-        lib.atg_alac_encode_device.restype = ctypes.c_int
-        lib.atg_alac_encode_host.argtypes = [
-            P, ctypes.POINTER(AlacOptions), P, ctypes.c_int, ctypes.POINTER(Track), c_u32,
-            c_u32, c_u32, P, c_u64, ctypes.POINTER(AlacTrackResult), P]
-        lib.atg_alac_encode_host.restype = ctypes.c_int
-        lib.atg_alac_encoder_kernel_times.argtypes = [
-            P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-        lib.atg_alac_encoder_kernel_times.restype = ctypes.c_int
-        lib.atg_alac_decoder_last_error.restype = ctypes.c_char_p
-        lib.atg_alac_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(AlacInfo), P,
-                                           c_u32, P, c_u32, ctypes.POINTER(c_u32)]
-        lib.atg_alac_read_info.restype = ctypes.c_int
-        lib.atg_alac_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_alac_decoder_create.restype = ctypes.c_int
-        lib.atg_alac_decoder_destroy.argtypes = [P]
-        lib.atg_alac_decoder_destroy.restype = None
-        lib.atg_alac_decode_host.argtypes = [
-            P, P, c_u64, ctypes.POINTER(AlacDecTrack), c_u32, ctypes.POINTER(AlacDecResult),
-            ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]
-        lib.atg_alac_decode_host.restype = ctypes.c_int
-        lib.atg_alac_decode_fetch.argtypes = [P, P, c_u64, P, P, c_u64]
-        lib.atg_alac_decode_fetch.restype = ctypes.c_int
-        lib.atg_alac_decode_device.argtypes = [
-            P, P, c_u64, ctypes.POINTER(AlacDecTrack), c_u32, ctypes.POINTER(AlacDecResult),
-            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_alac_decode_device.restype = ctypes.c_int
-        lib.atg_alac_decoder_kernel_times.argtypes = [
-            P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-        lib.atg_alac_decoder_kernel_times.restype = ctypes.c_int
-        KT = [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-        lib.atg_tta_last_error.restype = ctypes.c_char_p
-        lib.atg_tta_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_tta_encoder_create.restype = ctypes.c_int
-        lib.atg_tta_encoder_destroy.argtypes = [P]
-        lib.atg_tta_encoder_destroy.restype = None
-        for fn in (lib.atg_tta_encode_device, lib.atg_tta_encode_host):
-            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32,
-                           c_u32, P, c_u64, ctypes.POINTER(TtaTrackResult), P, c_u64,
-                           ctypes.POINTER(c_u64)]
-            fn.restype = ctypes.c_int
-        lib.atg_tta_encoder_kernel_times.argtypes = KT
-        lib.atg_tta_encoder_kernel_times.restype = ctypes.c_int
-        lib.atg_tta_decoder_last_error.restype = ctypes.c_char_p
-        lib.atg_tta_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(TtaInfo), P,
-                                          c_u32, ctypes.POINTER(c_u32)]
-        lib.atg_tta_read_info.restype = ctypes.c_int
-        lib.atg_tta_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_tta_decoder_create.restype = ctypes.c_int
-        lib.atg_tta_decoder_destroy.argtypes = [P]
-        lib.atg_tta_decoder_destroy.restype = None
-        lib.atg_tta_decode_host.argtypes = [
-            P, P, c_u64, ctypes.POINTER(TtaDecTrack), c_u32, ctypes.POINTER(TtaDecResult),
-            ctypes.POINTER(c_u64)]
-        lib.atg_tta_decode_host.restype = ctypes.c_int
-        lib.atg_tta_decode_fetch.argtypes = [P, P, c_u64]
-        lib.atg_tta_decode_fetch.restype = ctypes.c_int
-        lib.atg_tta_decode_device.argtypes = [
-            P, P, c_u64, ctypes.POINTER(TtaDecTrack), c_u32, ctypes.POINTER(TtaDecResult),
-            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_tta_decode_device.restype = ctypes.c_int
-        lib.atg_tta_decoder_kernel_times.argtypes = KT
-        lib.atg_tta_decoder_kernel_times.restype = ctypes.c_int
-        lib.atg_wv_decoder_last_error.restype = ctypes.c_char_p
-        lib.atg_wv_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(WvInfo), P,
-                                         c_u32, ctypes.POINTER(c_u32)]
-        lib.atg_wv_read_info.restype = ctypes.c_int
-        lib.atg_wv_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_wv_decoder_create.restype = ctypes.c_int
-        lib.atg_wv_decoder_destroy.argtypes = [P]
-        lib.atg_wv_decoder_destroy.restype = None
-        lib.atg_wv_decode_host.argtypes = [P, P, c_u64, P, c_u32, P, ctypes.POINTER(c_u64)]
-        lib.atg_wv_decode_host.restype = ctypes.c_int
-        lib.atg_wv_decode_fetch.argtypes = [P, P, c_u64]
-        lib.atg_wv_decode_fetch.restype = ctypes.c_int
-        lib.atg_wv_decode_device.argtypes = [P, P, c_u64, P, c_u32, P, ctypes.POINTER(P),
-                                             ctypes.POINTER(c_u64)]
-        lib.atg_wv_decode_device.restype = ctypes.c_int
-        lib.atg_wv_decoder_kernel_times.argtypes = KT
-        lib.atg_wv_decoder_kernel_times.restype = ctypes.c_int
-        lib.atg_wv_encoder_last_error.restype = ctypes.c_char_p
-        lib.atg_wv_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_wv_encoder_create.restype = ctypes.c_int
-        lib.atg_wv_encoder_destroy.argtypes = [P]
-        lib.atg_wv_encoder_destroy.restype = None
-        for fn in (lib.atg_wv_encode_device, lib.atg_wv_encode_host):
-            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), c_u32, c_u32, c_u32,
-                           c_u32, c_u32, ctypes.POINTER(WvEncOptions), P, c_u64,
-                           ctypes.POINTER(WvTrackResult), P, c_u64, ctypes.POINTER(c_u64)]
-            fn.restype = ctypes.c_int
-        lib.atg_wv_encoder_kernel_times.argtypes = KT
-        lib.atg_wv_encoder_kernel_times.restype = ctypes.c_int
-        lib.atg_shn_encoder_last_error.restype = ctypes.c_char_p
-        lib.atg_shn_encoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_shn_encoder_create.restype = ctypes.c_int
-        lib.atg_shn_encoder_destroy.argtypes = [P]
-        lib.atg_shn_encoder_destroy.restype = None
-        for fn in (lib.atg_shn_encode_device, lib.atg_shn_encode_host):
-            fn.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(Track), P, c_u32, c_u32, c_u32,
-                           ctypes.POINTER(ShnOptions), P, c_u64,
-                           ctypes.POINTER(ShnTrackResult), ctypes.POINTER(c_u64)]
-            fn.restype = ctypes.c_int
-        lib.atg_shn_encoder_kernel_times.argtypes = KT
-        lib.atg_shn_encoder_kernel_times.restype = ctypes.c_int
-        lib.atg_shn_decoder_last_error.restype = ctypes.c_char_p
-        lib.atg_shn_read_info.argtypes = [ctypes.c_char_p, c_u64, ctypes.POINTER(ShnInfo)]
-        lib.atg_shn_read_info.restype = ctypes.c_int
-        lib.atg_shn_decoder_create.argtypes = [ctypes.c_int, ctypes.POINTER(P)]
-        lib.atg_shn_decoder_create.restype = ctypes.c_int
-        lib.atg_shn_decoder_destroy.argtypes = [P]
-        lib.atg_shn_decoder_destroy.restype = None
-        lib.atg_shn_decoder_set_index_walk.argtypes = [P, ctypes.c_int]
-        lib.atg_shn_decoder_set_index_walk.restype = ctypes.c_int
-        lib.atg_shn_decode_host.argtypes = [
-            P, P, c_u64, ctypes.POINTER(ShnDecTrack), c_u32, ctypes.POINTER(ShnDecResult),
-            ctypes.POINTER(c_u64)]
-        lib.atg_shn_decode_host.restype = ctypes.c_int
-        lib.atg_shn_decode_fetch.argtypes = [P, P, c_u64]
-        lib.atg_shn_decode_fetch.restype = ctypes.c_int
-        lib.atg_shn_decode_fetch_verbatim.argtypes = [P, P, c_u64]
-        lib.atg_shn_decode_fetch_verbatim.restype = ctypes.c_int
-        lib.atg_shn_decode_fetch_blocks.argtypes = [P, c_u32, P, c_u64, ctypes.POINTER(c_u64)]
-        lib.atg_shn_decode_fetch_blocks.restype = ctypes.c_int
-        lib.atg_shn_decode_device.argtypes = [
-            P, P, c_u64, ctypes.POINTER(ShnDecTrack), c_u32, ctypes.POINTER(ShnDecResult),
-            ctypes.POINTER(P), ctypes.POINTER(c_u64)]
-        lib.atg_shn_decode_device.restype = ctypes.c_int
-        lib.atg_shn_decoder_kernel_times.argtypes = KT
-        lib.atg_shn_decoder_kernel_times.restype = ctypes.c_int
-        lib.atg_resample_last_error.restype = ctypes.c_char_p
-        lib.atg_resample_output_frames.argtypes = [c_u64, c_u32, c_u32, c_u32]
-        lib.atg_resample_output_frames.restype = c_u64
-        lib.atg_resample_device.argtypes = [
-            ctypes.POINTER(RsTrack), c_u32, c_u32, c_u32, P, P, c_u64, P, P, P]
-        lib.atg_resample_device.restype = ctypes.c_int
-        lib.atg_resample_host.argtypes = [
-            ctypes.c_int, ctypes.POINTER(RsTrack), c_u32, c_u32, c_u32, P, c_u64, P, c_u64,
-            P, P]
-        lib.atg_resample_host.restype = ctypes.c_int
-        lib.atg_resample_read_sizes.argtypes = [c_u64, c_u32, c_u32, c_u32, P, c_u64, P, c_u64]
-        lib.atg_resample_read_sizes.restype = ctypes.c_int64
-        lib.atg_resample_kernel_times.argtypes = [
-            ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-        lib.atg_resample_kernel_times.restype = ctypes.c_int
-        lib.atg_pcm_chain_last_error.restype = ctypes.c_char_p
-        lib.atg_pcm_chain_device.argtypes = [ctypes.POINTER(PcmChainRow), c_u32, P, ctypes.c_int,
-                                             c_u64, P, c_u64, P]
-        lib.atg_pcm_chain_device.restype = ctypes.c_int
-        lib.atg_pcm_chain_host.argtypes = [ctypes.c_int, ctypes.POINTER(PcmChainRow), c_u32, P,
-                                           ctypes.c_int, c_u64, P, c_u64]
-        lib.atg_pcm_chain_host.restype = ctypes.c_int
-        lib.atg_pcm_chain_tile_samples.restype = c_u32
-        lib.atg_pcm_chain_kernel_times.argtypes = [
-            ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-        lib.atg_pcm_chain_kernel_times.restype = ctypes.c_int
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
@@ -1004,9 +821,31 @@ class _Handle(object):
     def _error(self, status):
         return ATGError(status, getattr(self.lib, self._last_error)().decode("utf-8", "replace"))
 
-    def _check(self, status):
+    def _check(self, status, need=None):
+        """raise for a failed call; with `need` (the c_u64 an encode call
+        fills) the error carries .needed, the output bytes the call asks for"""
         if status != ATG_OK:
-            raise self._error(status)
+            err = self._error(status)
+            if need is not None:
+                err.needed = need.value
+            raise err
+
+    def _encode_retry(self, call, cap, out=None, retry=True):
+        """a host encode whose output size is known only once it ran:
+        call(out pointer, cap, need reference) -> status runs into `out`, or
+        into cap bytes made here, and, if it reports ATG_ERR_CAPACITY and
+        `retry` holds, once more with the size it asked for -> out"""
+        need = c_u64()
+        buf, retry = out, retry and out is None
+        for _ in range(2):
+            if out is None:
+                buf = np.empty(max(4, cap), dtype=np.uint8)
+            st = call(buf.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(need))
+            if st != ATG_ERR_CAPACITY or need.value <= cap or not retry:
+                break
+            cap = need.value
+        self._check(st, need)
+        return buf
 
     def close(self):
         if self.handle:
@@ -1032,6 +871,82 @@ class TrackTable(object):
 
     def __init__(self, tracks):
         self.arr, self.n, self._keep = _track_array(tracks)
+
+
+def _tracks(tracks):
+    """a TrackTable or an iterable of tracks -> what _track_array gives"""
+    if isinstance(tracks, TrackTable):
+        return tracks.arr, tracks.n, tracks._keep
+    return _track_array(tracks)
+
+
+def _host_pcm(pcm):
+    """host PCM -> (contiguous array, PCM_S16 or PCM_S32)"""
+    pcm = np.ascontiguousarray(pcm)
+    if pcm.dtype == np.int16:
+        return pcm, PCM_S16
+    if pcm.dtype == np.int32:
+        return pcm, PCM_S32
+    raise TypeError("pcm must be int16 or int32")
+
+
+class _DecoderHandle(_Handle):
+    """what the decoder classes share.  A subclass names its track and result
+    structs (_track, _result), its ..._decode_device function and, where the
+    C side has a plain one, its ..._decode_fetch function; its host decode
+    goes through _decode_pair."""
+
+    _track = _result = None
+    _decode_device = _decode_fetch = None
+
+    def __init__(self, device=0):
+        # a decode and the fetch of its PCM are two calls: held across the
+        # pair, so that threads sharing the process-wide decoder do not
+        # fetch each other's batch
+        self._pair = threading.Lock()
+        super().__init__(device)
+
+    def _decode_pair(self, host, track_t, result_t, n_totals, data, tracks, fetch):
+        """a host-memory decode (images 4-byte aligned in data): `host`, the
+        ..._decode_host function, then fetch(results, *totals), the step that
+        brings the batch to host memory, both under the pair lock.  totals
+        are the n_totals counts the C call reports (samples[, frames])
+        -> what fetch returns"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = len(tracks)
+        arr = (track_t * max(1, n))(*tracks)
+        res = (result_t * max(1, n))()
+        totals = [c_u64() for _ in range(n_totals)]
+        with self._pair:
+            self._check(host(self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n,
+                             res, *[ctypes.byref(t) for t in totals]))
+            return fetch([res[i] for i in range(n)], *[t.value for t in totals])
+
+    def _on_device(self, call, track_t, result_t, d_data, nbytes, tracks):
+        n = len(tracks)
+        arr = (track_t * max(1, n))(*tracks)
+        res = (result_t * max(1, n))()
+        dp = ctypes.c_void_p()
+        ns = c_u64()
+        self._check(call(self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res,
+                         ctypes.byref(dp), ctypes.byref(ns)))
+        return [res[i] for i in range(n)], dp.value, ns.value
+
+    def decode_device(self, d_data, nbytes, tracks):
+        """decode a batch already in device memory -> ([results], device
+        pointer of the int32 PCM, interleaved samples).  The PCM stays in the
+        decoder's buffer until its next call (fetch() copies it out): one
+        thread at a time, no lock"""
+        return self._on_device(getattr(self.lib, self._decode_device), self._track,
+                               self._result, d_data, nbytes, tracks)
+
+    def fetch(self, n_samples, out=None):
+        """the last decode's PCM (n_samples int32) to host memory, into
+        `out` if given"""
+        pcm = np.empty(max(1, n_samples), dtype=np.int32) if out is None else out
+        self._check(getattr(self.lib, self._decode_fetch)(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
+        return pcm[:n_samples]
 
 
 class HostJob:
@@ -1117,13 +1032,7 @@ class Engine(_Handle):
         without staging.
         Returns (out: uint8 array, results: list of TrackResult,
                  frame_offsets: uint64 array, frame_pcm: uint32 array)."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype == np.int16:
-            fmt = PCM_S16
-        elif pcm.dtype == np.int32:
-            fmt = PCM_S32
-        else:
-            raise TypeError("pcm must be int16 or int32")
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         nf, nb = self.bounds(options, tracks, channels, bits_per_sample)
         arr, n, keep = _track_array(tracks)
@@ -1147,13 +1056,7 @@ class Engine(_Handle):
         HostJob whose wait() gives encode()'s (out, results, frame_offsets,
         frame_pcm).  The job keeps pcm, out and the result arrays alive
         until it is waited; jobs overlap in submission order."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype == np.int16:
-            fmt = PCM_S16
-        elif pcm.dtype == np.int32:
-            fmt = PCM_S32
-        else:
-            raise TypeError("pcm must be int16 or int32")
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         nf, nb = self.bounds(options, tracks, channels, bits_per_sample)
         arr, n, keep = _track_array(tracks)
@@ -1178,10 +1081,7 @@ class Engine(_Handle):
         """encode a batch whose PCM is already in device memory; the .flac
         images stay in device memory at d_out.  Returns the TrackResults.
         `tracks` may be a TrackTable (prepared once, reused across calls)."""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         res = (TrackResult * max(1, n))()
         _check(self.lib, self.lib.atg_flac_encode_device(
             self.handle, ctypes.byref(options), ctypes.c_void_p(d_pcm), fmt, arr, n,
@@ -1203,13 +1103,7 @@ class Engine(_Handle):
         (atg_oggflac_encode_host).  pcm as encode().
         Returns (out: uint8 array, results: list of OggFlacTrackResult,
                  frame_page_offsets: uint64 array, frame_pcm: uint32 array)."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype == np.int16:
-            fmt = PCM_S16
-        elif pcm.dtype == np.int32:
-            fmt = PCM_S32
-        else:
-            raise TypeError("pcm must be int16 or int32")
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         nf, nb = self.oggflac_bounds(options, ogg_options, tracks, channels, bits_per_sample)
         arr, n, keep = _track_array(tracks)
@@ -1229,10 +1123,7 @@ class Engine(_Handle):
         """as encode_device, to Ogg FLAC images (atg_oggflac_encode_device).
         Returns (results, frame_page_offsets, frame_pcm); the two arrays are
         filled when n_frames (oggflac_bounds' frame count) is given."""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         res = (OggFlacTrackResult * max(1, n))()
         offs = np.zeros(max(1, n_frames), dtype=np.uint64)
         fpcm = np.zeros(max(1, n_frames), dtype=np.uint32)
@@ -1247,10 +1138,7 @@ class Engine(_Handle):
     def encode_device_async(self, options, d_pcm, fmt, tracks, channels, bits_per_sample,
                             sample_rate, d_out, out_cap):
         """enqueue a device-memory batch; -> (ticket, n_tracks) for wait()"""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         t = c_u64()
         _check(self.lib, self.lib.atg_flac_encode_device_async(
             self.handle, ctypes.byref(options), ctypes.c_void_p(d_pcm), fmt, arr, n,
@@ -1270,13 +1158,7 @@ class Engine(_Handle):
         """one track's PCM (host numpy int16 / int32, interleaved) as FLAC
         frames only, numbered from first_frame_number (atg_flac_encode_frames)
         -> (frame bytes: uint8 array, per-frame byte counts: uint32 array)"""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype == np.int16:
-            fmt = PCM_S16
-        elif pcm.dtype == np.int32:
-            fmt = PCM_S32
-        else:
-            raise TypeError("pcm must be int16 or int32")
+        pcm, fmt = _host_pcm(pcm)
         frames = len(pcm) // channels
         fs = None if frame_sizes is None else np.ascontiguousarray(frame_sizes, dtype=np.uint32)
         fs_p = fs.ctypes.data_as(ctypes.c_void_p) if fs is not None else None
@@ -1428,11 +1310,12 @@ def dec_track(offset, nbytes, si):
     return t
 
 
-class Decoder(_Handle):
+class Decoder(_DecoderHandle):
     """one libatgpu FLAC decoder (HIP stream + workspace) on one device"""
 
     _create, _destroy = "atg_decoder_create", "atg_decoder_destroy"
     _last_error, _kernel_times = "atg_decoder_last_error", "atg_decoder_kernel_times"
+    _track, _result, _decode_device = DecTrack, DecResult, "atg_flac_decode_device"
 
     def __init__(self, device=0):
         super().__init__(device)
@@ -1456,36 +1339,27 @@ class Decoder(_Handle):
         stream; tracks: list of DecTrack.  -> (pcm int32 array, [DecResult],
         frame byte offsets (uint64), frame block sizes (uint32)); pcm is
         None when fetch_pcm is false (results carry the PCM MD5s)"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (DecTrack * max(1, n))(*tracks)
-        res = (DecResult * max(1, n))()
-        ns, nf = c_u64(), c_u64()
-        self._check(self.lib.atg_flac_decode_host(
-            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-            ctypes.byref(ns), ctypes.byref(nf)))
-        pcm = np.empty(max(1, ns.value), dtype=np.int32) if fetch_pcm else None
-        offs = np.empty(max(1, nf.value), dtype=np.uint64)
-        bss = np.empty(max(1, nf.value), dtype=np.uint32)
-        self._check(self.lib.atg_flac_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p) if fetch_pcm else None,
-            ns.value, offs.ctypes.data_as(ctypes.c_void_p),
-            bss.ctypes.data_as(ctypes.c_void_p), nf.value))
-        return (pcm[:ns.value] if fetch_pcm else None, [res[i] for i in range(n)],
-                offs[:nf.value], bss[:nf.value])
+        def fetch(res, ns, nf):
+            pcm, offs, bss = self._fetch_frames(self.lib.atg_flac_decode_fetch, ns, nf,
+                                                fetch_pcm, True)
+            return pcm, res, offs, bss
 
-    def decode_device(self, d_data, nbytes, tracks):
-        """decode a batch already in device memory -> ([DecResult],
-        device pointer of the int32 PCM, interleaved samples)"""
-        n = len(tracks)
-        arr = (DecTrack * max(1, n))(*tracks)
-        res = (DecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_flac_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
+        return self._decode_pair(self.lib.atg_flac_decode_host, DecTrack, DecResult, 2, data,
+                                 tracks, fetch)
+
+    def _fetch_frames(self, call, ns, nf, fetch_pcm, fetch_offsets):
+        """atg_flac_decode_fetch / atg_oggflac_decode_fetch: the last batch's
+        ns samples (or None) and its nf frames' byte offsets (or None) and
+        block sizes"""
+        pcm = np.empty(max(1, ns), dtype=np.int32) if fetch_pcm else None
+        offs = np.empty(max(1, nf), dtype=np.uint64) if fetch_offsets else None
+        bss = np.empty(max(1, nf), dtype=np.uint32)
+        self._check(call(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p) if fetch_pcm else None, ns,
+            offs.ctypes.data_as(ctypes.c_void_p) if fetch_offsets else None,
+            bss.ctypes.data_as(ctypes.c_void_p), nf))
+        return (pcm[:ns] if fetch_pcm else None, offs[:nf] if fetch_offsets else None,
+                bss[:nf])
 
     def decode_device_async(self, d_data, nbytes, tracks):
         """enqueue a device-resident batch (three may be in flight) -> ticket;
@@ -1512,34 +1386,19 @@ class Decoder(_Handle):
         """decode a batch of Ogg FLAC images in host memory.  data: bytes-like
         holding every image; tracks: list of OggFlacDecTrack.  -> (pcm int32
         array, [OggFlacDecResult], frame block sizes (uint32))"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (OggFlacDecTrack * max(1, n))(*tracks)
-        res = (OggFlacDecResult * max(1, n))()
-        ns, nf = c_u64(), c_u64()
-        self._check(self.lib.atg_oggflac_decode_host(
-            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-            ctypes.byref(ns), ctypes.byref(nf)))
-        pcm = np.empty(max(1, ns.value), dtype=np.int32) if fetch_pcm else None
-        bss = np.empty(max(1, nf.value), dtype=np.uint32)
-        self._check(self.lib.atg_oggflac_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p) if fetch_pcm else None, ns.value,
-            None, bss.ctypes.data_as(ctypes.c_void_p), nf.value))
-        return (pcm[:ns.value] if fetch_pcm else None, [res[i] for i in range(n)],
-                bss[:nf.value])
+        def fetch(res, ns, nf):
+            pcm, _, bss = self._fetch_frames(self.lib.atg_oggflac_decode_fetch, ns, nf,
+                                             fetch_pcm, False)
+            return pcm, res, bss
+
+        return self._decode_pair(self.lib.atg_oggflac_decode_host, OggFlacDecTrack,
+                                 OggFlacDecResult, 2, data, tracks, fetch)
 
     def decode_oggflac_device(self, d_data, nbytes, tracks):
         """decode a batch of Ogg FLAC images already in device memory ->
         ([OggFlacDecResult], device pointer of the int32 PCM, interleaved samples)"""
-        n = len(tracks)
-        arr = (OggFlacDecTrack * max(1, n))(*tracks)
-        res = (OggFlacDecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_oggflac_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
+        return self._on_device(self.lib.atg_oggflac_decode_device, OggFlacDecTrack,
+                               OggFlacDecResult, d_data, nbytes, tracks)
 
 
 def oggflac_read_info(data):
@@ -1558,17 +1417,24 @@ def oggflac_dec_track(offset, nbytes):
     return t
 
 
-def oggflac_pack(images):
+def pack_images(images):
     """whole images -> (batch buffer with every image 4-byte aligned and room
-    to read the last word, [OggFlacDecTrack])"""
-    parts, tracks, pos = [], [], 0
+    to read the last word, [(offset, bytes)] of the images in it): what every
+    decoder's host-memory batch takes"""
+    parts, spans, pos = [], [], 0
     for img in images:
         img = bytes(img)
-        tracks.append(oggflac_dec_track(pos, len(img)))
+        spans.append((pos, len(img)))
         pad = (-len(img)) % 4
         parts.append(img + bytes(pad))
         pos += len(img) + pad
-    return b"".join(parts), tracks
+    return b"".join(parts), spans
+
+
+def oggflac_pack(images):
+    """pack_images with the images' [OggFlacDecTrack]"""
+    data, spans = pack_images(images)
+    return data, [oggflac_dec_track(offset, nbytes) for offset, nbytes in spans]
 
 
 class AlacEncoder(_Handle):
@@ -1595,10 +1461,7 @@ class AlacEncoder(_Handle):
     def encode(self, options, pcm, tracks, channels, bits_per_sample):
         """host PCM (int16 for 16-bit, int32 otherwise) -> (out bytes array,
         [AlacTrackResult], frameset byte sizes uint32 array)"""
-        pcm = np.ascontiguousarray(pcm)
-        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
-        if pcm.dtype not in (np.int16, np.int32):
-            raise TypeError("pcm must be int16 or int32")
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         nf, nb = self.bounds(options, tracks, channels, bits_per_sample)
         arr, n, keep = _track_array(tracks)
@@ -1613,10 +1476,7 @@ class AlacEncoder(_Handle):
 
     def encode_device(self, options, d_pcm, fmt, tracks, channels, bits_per_sample, d_out,
                       out_cap, frameset_bytes=None):
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         res = (AlacTrackResult * max(1, n))()
         self._check(self.lib.atg_alac_encode_device(
             self.handle, ctypes.byref(options), ctypes.c_void_p(d_pcm), fmt, arr, n, channels,
@@ -1672,41 +1532,27 @@ def alac_dec_track(offset, nbytes, info, start=None, remaining=None, frameset_by
     return t
 
 
-class AlacDecoder(_Handle):
+class AlacDecoder(_DecoderHandle):
     """one libatgpu ALAC decoder (HIP stream + workspace) on one device"""
 
     _create, _destroy = "atg_alac_decoder_create", "atg_alac_decoder_destroy"
     _last_error, _kernel_times = "atg_alac_decoder_last_error", "atg_alac_decoder_kernel_times"
+    _track, _result, _decode_device = AlacDecTrack, AlacDecResult, "atg_alac_decode_device"
 
     def decode(self, data, tracks):
         """decode a batch in host memory (images 4-byte aligned in data)
         -> (pcm int32, [AlacDecResult], frameset frames, frameset offsets)"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (AlacDecTrack * max(1, n))(*tracks)
-        res = (AlacDecResult * max(1, n))()
-        ns, nf = c_u64(), c_u64()
-        self._check(self.lib.atg_alac_decode_host(
-            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-            ctypes.byref(ns), ctypes.byref(nf)))
-        pcm = np.empty(max(1, ns.value), dtype=np.int32)
-        ff = np.empty(max(1, nf.value), dtype=np.uint32)
-        fo = np.empty(max(1, nf.value), dtype=np.uint64)
-        self._check(self.lib.atg_alac_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns.value,
-            ff.ctypes.data_as(ctypes.c_void_p), fo.ctypes.data_as(ctypes.c_void_p), nf.value))
-        return pcm[:ns.value], [res[i] for i in range(n)], ff[:nf.value], fo[:nf.value]
+        def fetch(res, ns, nf):
+            pcm = np.empty(max(1, ns), dtype=np.int32)
+            ff = np.empty(max(1, nf), dtype=np.uint32)
+            fo = np.empty(max(1, nf), dtype=np.uint64)
+            self._check(self.lib.atg_alac_decode_fetch(
+                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns,
+                ff.ctypes.data_as(ctypes.c_void_p), fo.ctypes.data_as(ctypes.c_void_p), nf))
+            return pcm[:ns], res, ff[:nf], fo[:nf]
 
-    def decode_device(self, d_data, nbytes, tracks):
-        n = len(tracks)
-        arr = (AlacDecTrack * max(1, n))(*tracks)
-        res = (AlacDecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_alac_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
+        return self._decode_pair(self.lib.atg_alac_decode_host, AlacDecTrack, AlacDecResult, 2,
+                                 data, tracks, fetch)
 
 
 class TtaEncoder(_Handle):
@@ -1726,10 +1572,7 @@ class TtaEncoder(_Handle):
         [TtaTrackResult], frame byte sizes uint32 array).  A TTA frame has no
         size bound, so the first call offers the raw PCM size and a call
         that reports ATG_ERR_CAPACITY is repeated with the size it asks for."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype not in (np.int16, np.int32):
-            raise TypeError("pcm must be int16 or int32")
-        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         arr, n, keep = _track_array(tracks)
         nf = self.frame_count(tracks, sample_rate)
@@ -1737,27 +1580,17 @@ class TtaEncoder(_Handle):
         fsb = np.zeros(max(1, nf), dtype=np.uint32)
         cap = int(out_cap) if out_cap is not None else \
             pcm.size * ((bits_per_sample + 7) // 8) + 64 * nf + 16 * n + 64
-        need = c_u64()
-        for _ in range(2):
-            out = np.empty(max(1, cap), dtype=np.uint8)
-            st = self.lib.atg_tta_encode_host(
-                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
-                bits_per_sample, sample_rate, out.ctypes.data_as(ctypes.c_void_p), cap, res,
-                fsb.ctypes.data_as(ctypes.c_void_p), len(fsb), ctypes.byref(need))
-            if st != ATG_ERR_CAPACITY or need.value <= cap:
-                break
-            cap = need.value
-        self._check(st)
+        out = self._encode_retry(lambda out, cap, need: self.lib.atg_tta_encode_host(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
+            bits_per_sample, sample_rate, out, cap, res, fsb.ctypes.data_as(ctypes.c_void_p),
+            len(fsb), need), cap)
         return out, [res[i] for i in range(n)], fsb[:nf]
 
     def encode_device(self, d_pcm, fmt, tracks, channels, bits_per_sample, sample_rate, d_out,
                       out_cap, frame_bytes=None):
         """-> ([TtaTrackResult], bytes needed); raises ATGError with status
         ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         res = (TtaTrackResult * max(1, n))()
         need = c_u64()
         st = self.lib.atg_tta_encode_device(
@@ -1765,10 +1598,7 @@ class TtaEncoder(_Handle):
             sample_rate, ctypes.c_void_p(d_out), out_cap, res,
             frame_bytes.ctypes.data_as(ctypes.c_void_p) if frame_bytes is not None else None,
             len(frame_bytes) if frame_bytes is not None else 0, ctypes.byref(need))
-        if st != ATG_OK:
-            err = self._error(st)
-            err.needed = need.value
-            raise err
+        self._check(st, need)
         return [res[i] for i in range(n)], need.value
 
 
@@ -1806,45 +1636,19 @@ def tta_dec_track(offset, nbytes, info, frame_bytes, first_frame=0):
     return t
 
 
-class TtaDecoder(_Handle):
+class TtaDecoder(_DecoderHandle):
     """one libatgpu True Audio decoder (HIP stream + workspace) on one device"""
 
     _create, _destroy = "atg_tta_decoder_create", "atg_tta_decoder_destroy"
     _last_error, _kernel_times = "atg_tta_decoder_last_error", "atg_tta_decoder_kernel_times"
+    _track, _result = TtaDecTrack, TtaDecResult
+    _decode_device, _decode_fetch = "atg_tta_decode_device", "atg_tta_decode_fetch"
 
     def decode(self, data, tracks):
         """decode a batch in host memory (images 4-byte aligned in data)
         -> (pcm int32, [TtaDecResult])"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (TtaDecTrack * max(1, n))(*tracks)
-        res = (TtaDecResult * max(1, n))()
-        ns = c_u64()
-        self._check(self.lib.atg_tta_decode_host(
-            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-            ctypes.byref(ns)))
-        pcm = np.empty(max(1, ns.value), dtype=np.int32)
-        self._check(self.lib.atg_tta_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns.value))
-        return pcm[:ns.value], [res[i] for i in range(n)]
-
-    def decode_device(self, d_data, nbytes, tracks):
-        n = len(tracks)
-        arr = (TtaDecTrack * max(1, n))(*tracks)
-        res = (TtaDecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_tta_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
-
-    def fetch(self, n_samples):
-        """the last decode's PCM (n_samples int32) to host memory"""
-        pcm = np.empty(max(1, n_samples), dtype=np.int32)
-        self._check(self.lib.atg_tta_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
-        return pcm[:n_samples]
+        return self._decode_pair(self.lib.atg_tta_decode_host, TtaDecTrack, TtaDecResult, 1,
+                                 data, tracks, lambda res, ns: (self.fetch(ns), res))
 
 
 def wv_read_info(data):
@@ -1889,55 +1693,19 @@ def wv_dec_track(offset, nbytes, info, blocks, first_set=0, check_md5=None):
     return t
 
 
-class WvDecoder(_Handle):
+class WvDecoder(_DecoderHandle):
     """one libatgpu WavPack decoder (HIP stream + workspace) on one device"""
 
     _create, _destroy = "atg_wv_decoder_create", "atg_wv_decoder_destroy"
     _last_error, _kernel_times = "atg_wv_decoder_last_error", "atg_wv_decoder_kernel_times"
-
-    def __init__(self, device=0):
-        # a decode and the fetch of its PCM are two calls: held across the
-        # pair, so that threads sharing the process-wide decoder do not
-        # fetch each other's batch
-        self._pair = threading.Lock()
-        super().__init__(device)
+    _track, _result = WvDecTrack, WvDecResult
+    _decode_device, _decode_fetch = "atg_wv_decode_device", "atg_wv_decode_fetch"
 
     def decode(self, data, tracks, pcm_out=None):
         """decode a batch in host memory (images 4-byte aligned in data)
         -> (pcm int32, [WvDecResult]); pcm_out: an int32 array to fetch into"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (WvDecTrack * max(1, n))(*tracks)
-        res = (WvDecResult * max(1, n))()
-        ns = c_u64()
-        with self._pair:
-            self._check(self.lib.atg_wv_decode_host(
-                self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-                ctypes.byref(ns)))
-            pcm = np.empty(max(1, ns.value), dtype=np.int32) if pcm_out is None else pcm_out
-            self._check(self.lib.atg_wv_decode_fetch(
-                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), ns.value))
-        return pcm[:ns.value], [res[i] for i in range(n)]
-
-    def decode_device(self, d_data, nbytes, tracks):
-        """images in device memory; the PCM stays in the decoder's buffer until
-        its next call (fetch() copies it out): one thread at a time"""
-        n = len(tracks)
-        arr = (WvDecTrack * max(1, n))(*tracks)
-        res = (WvDecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_wv_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
-
-    def fetch(self, n_samples):
-        """the last decode's PCM (n_samples int32) to host memory"""
-        pcm = np.empty(max(1, n_samples), dtype=np.int32)
-        self._check(self.lib.atg_wv_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
-        return pcm[:n_samples]
+        return self._decode_pair(self.lib.atg_wv_decode_host, WvDecTrack, WvDecResult, 1, data,
+                                 tracks, lambda res, ns: (self.fetch(ns, pcm_out), res))
 
 
 class WvEncoder(_Handle):
@@ -1971,44 +1739,25 @@ class WvEncoder(_Handle):
         and a call that reports ATG_ERR_CAPACITY is repeated with the size
         it asks for.  With `out` (a uint8 array) given there is one call into
         it; an ATGError carries .needed."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype not in (np.int16, np.int32):
-            raise TypeError("pcm must be int16 or int32")
-        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        pcm, fmt = _host_pcm(pcm)
         tracks = list(tracks)
         arr, n, keep = _track_array(tracks)
         nb = self.block_count(tracks, channels, channel_mask, opts.block_size)
         res = (WvTrackResult * max(1, n))()
         bsb = np.zeros(max(1, nb), dtype=np.uint32)
-        given = out is not None
-        cap = len(out) if given else \
+        cap = len(out) if out is not None else \
             pcm.size * ((bits_per_sample + 7) // 8) + 320 * nb + 128 * n + 64
-        need = c_u64()
-        for _ in range(2):
-            if not given:
-                out = np.empty(max(1, cap), dtype=np.uint8)
-            st = self.lib.atg_wv_encode_host(
-                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
-                channel_mask, bits_per_sample, sample_rate, ctypes.byref(opts),
-                out.ctypes.data_as(ctypes.c_void_p), cap, res,
-                bsb.ctypes.data_as(ctypes.c_void_p), len(bsb), ctypes.byref(need))
-            if st != ATG_ERR_CAPACITY or need.value <= cap or given:
-                break
-            cap = need.value
-        if st != ATG_OK:
-            err = self._error(st)
-            err.needed = need.value
-            raise err
+        out = self._encode_retry(lambda out, cap, need: self.lib.atg_wv_encode_host(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, n, channels,
+            channel_mask, bits_per_sample, sample_rate, ctypes.byref(opts), out, cap, res,
+            bsb.ctypes.data_as(ctypes.c_void_p), len(bsb), need), cap, out=out)
         return out, [res[i] for i in range(n)], bsb[:nb]
 
     def encode_device(self, opts, d_pcm, fmt, tracks, channels, channel_mask, bits_per_sample,
                       sample_rate, d_out, out_cap, block_bytes=None):
         """-> ([WvTrackResult], bytes needed); raises ATGError with status
         ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         res = (WvTrackResult * max(1, n))()
         need = c_u64()
         st = self.lib.atg_wv_encode_device(
@@ -2016,10 +1765,7 @@ class WvEncoder(_Handle):
             bits_per_sample, sample_rate, ctypes.byref(opts), ctypes.c_void_p(d_out), out_cap,
             res, block_bytes.ctypes.data_as(ctypes.c_void_p) if block_bytes is not None else None,
             len(block_bytes) if block_bytes is not None else 0, ctypes.byref(need))
-        if st != ATG_OK:
-            err = self._error(st)
-            err.needed = need.value
-            raise err
+        self._check(st, need)
         return [res[i] for i in range(n)], need.value
 
 
@@ -2070,29 +1816,16 @@ class ShnEncoder(_Handle):
         Sizes are known only after the length pass, so the first call offers
         the raw PCM size and a call that reports ATG_ERR_CAPACITY is repeated
         with the size it asks for."""
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype not in (np.int16, np.int32):
-            raise TypeError("pcm must be int16 or int32")
-        fmt = PCM_S16 if pcm.dtype == np.int16 else PCM_S32
+        pcm, fmt = _host_pcm(pcm)
         arr, n, keep = _track_array(tracks)
         extra, keep2 = _shn_extra(n, headers, footers)
         opts = ShnOptions(int(block_size), int(bool(is_big_endian)), int(bool(signed_samples)), 0)
         res = (ShnTrackResult * max(1, n))()
         cap = int(out_cap) if out_cap is not None else pcm.size * 2 + 64 * n + 64
-        need = c_u64()
-        for _ in range(2):
-            out = np.empty(max(4, cap), dtype=np.uint8)
-            st = self.lib.atg_shn_encode_host(
-                self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, extra, n, channels,
-                bits_per_sample, ctypes.byref(opts), out.ctypes.data_as(ctypes.c_void_p), cap,
-                res, ctypes.byref(need))
-            if st != ATG_ERR_CAPACITY or need.value <= cap or out_cap is not None:
-                break
-            cap = need.value
-        if st != ATG_OK:
-            err = self._error(st)
-            err.needed = need.value
-            raise err
+        out = self._encode_retry(lambda out, cap, need: self.lib.atg_shn_encode_host(
+            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), fmt, arr, extra, n, channels,
+            bits_per_sample, ctypes.byref(opts), out, cap, res, need), cap,
+            retry=out_cap is None)
         return out, [res[i] for i in range(n)]
 
     def encode_device(self, d_pcm, fmt, tracks, channels, bits_per_sample, d_out, out_cap,
@@ -2100,10 +1833,7 @@ class ShnEncoder(_Handle):
                       footers=None):
         """-> ([ShnTrackResult], bytes needed); raises ATGError with status
         ATG_ERR_CAPACITY (and .needed) when out_cap is too small"""
-        if isinstance(tracks, TrackTable):
-            arr, n = tracks.arr, tracks.n
-        else:
-            arr, n, keep = _track_array(tracks)
+        arr, n, keep = _tracks(tracks)
         extra, keep2 = _shn_extra(n, headers, footers)
         opts = ShnOptions(int(block_size), int(bool(is_big_endian)), int(bool(signed_samples)), 0)
         res = (ShnTrackResult * max(1, n))()
@@ -2111,10 +1841,7 @@ class ShnEncoder(_Handle):
         st = self.lib.atg_shn_encode_device(
             self.handle, ctypes.c_void_p(d_pcm), fmt, arr, extra, n, channels, bits_per_sample,
             ctypes.byref(opts), ctypes.c_void_p(d_out), out_cap, res, ctypes.byref(need))
-        if st != ATG_OK:
-            err = self._error(st)
-            err.needed = need.value
-            raise err
+        self._check(st, need)
         return [res[i] for i in range(n)], need.value
 
 
@@ -2134,48 +1861,32 @@ def shn_dec_track(offset, nbytes, info):
                        info.block_length, info.max_lpc, info.mean_count, 0)
 
 
-class ShnDecoder(_Handle):
+class ShnDecoder(_DecoderHandle):
     """one libatgpu Shorten decoder (HIP stream + workspace) on one device"""
 
     _create, _destroy = "atg_shn_decoder_create", "atg_shn_decoder_destroy"
     _last_error, _kernel_times = "atg_shn_decoder_last_error", "atg_shn_decoder_kernel_times"
+    _track, _result = ShnDecTrack, ShnDecResult
+    _decode_device, _decode_fetch = "atg_shn_decode_device", "atg_shn_decode_fetch"
 
     def set_index_walk(self, cooperative):
         """the index pass: the wave-cooperative code walk (default) or the
         lane-serial one"""
         self._check(self.lib.atg_shn_decoder_set_index_walk(self.handle, int(bool(cooperative))))
 
-    def decode(self, data, tracks):
+    def decode(self, data, tracks, blocks=False):
         """decode a batch in host memory (images 4-byte aligned in data)
-        -> (pcm int32, [ShnDecResult], VERBATIM bytes)"""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        n = len(tracks)
-        arr = (ShnDecTrack * max(1, n))(*tracks)
-        res = (ShnDecResult * max(1, n))()
-        ns = c_u64()
-        self._check(self.lib.atg_shn_decode_host(
-            self.handle, buf.ctypes.data_as(ctypes.c_void_p), len(buf), arr, n, res,
-            ctypes.byref(ns)))
-        res = [res[i] for i in range(n)]
-        return self.fetch(ns.value), res, self.fetch_verbatim(res)
+        -> (pcm int32, [ShnDecResult], VERBATIM bytes); with blocks, also the
+        list of every stream's fetch_blocks(), read before another thread's
+        decode can replace them"""
+        def fetch(res, ns):
+            out = (self.fetch(ns), res, self.fetch_verbatim(res))
+            if blocks:
+                out += ([self.fetch_blocks(k) for k in range(len(res))],)
+            return out
 
-    def decode_device(self, d_data, nbytes, tracks):
-        n = len(tracks)
-        arr = (ShnDecTrack * max(1, n))(*tracks)
-        res = (ShnDecResult * max(1, n))()
-        dp = ctypes.c_void_p()
-        ns = c_u64()
-        self._check(self.lib.atg_shn_decode_device(
-            self.handle, ctypes.c_void_p(d_data), nbytes, arr, n, res, ctypes.byref(dp),
-            ctypes.byref(ns)))
-        return [res[i] for i in range(n)], dp.value, ns.value
-
-    def fetch(self, n_samples):
-        """the last decode's PCM (n_samples int32) to host memory"""
-        pcm = np.empty(max(1, n_samples), dtype=np.int32)
-        self._check(self.lib.atg_shn_decode_fetch(
-            self.handle, pcm.ctypes.data_as(ctypes.c_void_p), n_samples))
-        return pcm[:n_samples]
+        return self._decode_pair(self.lib.atg_shn_decode_host, ShnDecTrack, ShnDecResult, 1,
+                                 data, tracks, fetch)
 
     def fetch_blocks(self, track):
         """the frame counts of the sets of channels stream `track` of the

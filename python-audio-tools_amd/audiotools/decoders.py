@@ -58,6 +58,27 @@ def _metadata_error(rc):
     return IOError("EOF while reading metadata")
 
 
+def _file_bytes(file):
+    """bytes as they are, a file object's from its position on"""
+    if isinstance(file, (bytes, bytearray, memoryview)):
+        return bytes(file)
+    if hasattr(file, "read"):
+        return file.read()
+    raise TypeError("file must be a file object or bytes")
+
+
+def _check_open(decoder, doing):
+    if decoder._closed:
+        raise ValueError("cannot %s closed stream" % doing)
+
+
+def _seek_offset(decoder, pcm_frame_offset):
+    """the offset of a seek() as an int, checked as every decoder checks it"""
+    _check_open(decoder, "seek")
+    pcm_frame_offset = int(pcm_frame_offset)
+    if pcm_frame_offset < 0:
+        raise ValueError("cannot seek to negative value")
+    return pcm_frame_offset
 
 
 def decode_flac_batch(images):
@@ -79,15 +100,12 @@ def decode_flac_batch(images):
 
     def shard(i):
         t0, t1 = ranges[i]
-        parts, tracks, pos = [], [], 0
-        for si, body in zip(infos[t0:t1], bodies[t0:t1]):
-            pad = (-len(body)) % 4
-            tracks.append(_atgpu.dec_track(pos, len(body), si))
-            parts.append(body + b"\0" * pad)
-            pos += len(body) + pad
+        data, spans = _atgpu.pack_images(bodies[t0:t1])
+        tracks = [_atgpu.dec_track(offset, nbytes, si)
+                  for (offset, nbytes), si in zip(spans, infos[t0:t1])]
         dec = (_atgpu.decoder() if len(ranges) == 1
                else _atgpu.shard_object("decoder", i, devs[i]))
-        return dec.decode(b"".join(parts), tracks)
+        return dec.decode(data, tracks)
 
     out = []
     for (t0, t1), (pcm_i32, res, _, _) in zip(ranges, _atgpu.run_shards(shard, len(ranges))):
@@ -169,10 +187,10 @@ class ALACDecoder(object):
     def _decode(self):
         if self._decoded:
             return
-        pad = (-len(self._data)) % 4
+        data, _ = _atgpu.pack_images([self._data])
         track = _atgpu.alac_dec_track(0, len(self._data), self._info, start=self._pos,
                                       remaining=self._remaining, frameset_bytes=self._hint())
-        pcm_i32, res, ff, _ = _atgpu.alac_decoder().decode(self._data + b"\0" * pad, [track])
+        pcm_i32, res, ff, _ = _atgpu.alac_decoder().decode(data, [track])
         r = res[0]
         self._pcm = pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * self.channels]
         self._fs = [int(x) for x in ff[r.first_frameset:r.first_frameset + r.n_framesets]]
@@ -182,8 +200,7 @@ class ALACDecoder(object):
         self._decoded = True
 
     def read(self, pcm_frames):
-        if self._closed:
-            raise ValueError("cannot read closed stream")
+        _check_open(self, "read")
         if self._remaining == 0:
             return pcm.empty_framelist(self.channels, self.bits_per_sample)
         self._decode()
@@ -200,11 +217,7 @@ class ALACDecoder(object):
         raise _alac_read_error(self._status)
 
     def seek(self, pcm_frame_offset):
-        if self._closed:
-            raise ValueError("cannot seek closed stream")
-        pcm_frame_offset = int(pcm_frame_offset)
-        if pcm_frame_offset < 0:
-            raise ValueError("cannot seek to negative value")
+        pcm_frame_offset = _seek_offset(self, pcm_frame_offset)
         best = None
         for entry in self._seektable:
             if entry[0] <= pcm_frame_offset:
@@ -226,18 +239,16 @@ def decode_alac_batch(images):
     """decode a list of M4A/ALAC images (bytes) in one GPU batch
     -> list of (status, AlacInfo, int32 interleaved PCM); status is an
     ATG_AD_* code (0 = every frame up to total_frames decoded)"""
-    parts, tracks, infos, pos = [], [], [], 0
-    for img in images:
+    images = list(images)
+    data, spans = _atgpu.pack_images(images)
+    tracks, infos = [], []
+    for img, (offset, nbytes) in zip(images, spans):
         st, info, _, sizes = _atgpu.alac_read_info(img)
         if st:
             raise _alac_init_error(st)
-        img = bytes(img)
-        pad = (-len(img)) % 4
-        tracks.append(_atgpu.alac_dec_track(pos, len(img), info, frameset_bytes=sizes))
-        parts.append(img + b"\0" * pad)
+        tracks.append(_atgpu.alac_dec_track(offset, nbytes, info, frameset_bytes=sizes))
         infos.append(info)
-        pos += len(img) + pad
-    pcm_i32, res, _, _ = _atgpu.alac_decoder().decode(b"".join(parts), tracks)
+    pcm_i32, res, _, _ = _atgpu.alac_decoder().decode(data, tracks)
     out = []
     for info, r in zip(infos, res):
         out.append((r.status, info,
@@ -274,12 +285,7 @@ class TTADecoder(object):
     """
 
     def __init__(self, file):
-        if isinstance(file, (bytes, bytearray, memoryview)):
-            data = bytes(file)
-        elif hasattr(file, "read"):
-            data = file.read()
-        else:
-            raise TypeError("file must be a file object or bytes")
+        data = _file_bytes(file)
         st, info, sizes = _atgpu.tta_read_info(data)
         if st:
             raise _tta_init_error(st, info.stage)
@@ -301,9 +307,9 @@ class TTADecoder(object):
         """the frames from the current one on, in one GPU call"""
         if self._decoded_from is not None and self._decoded_from <= self._frame:
             return
-        pad = (-len(self._data)) % 4
+        data, _ = _atgpu.pack_images([self._data])
         track = _atgpu.tta_dec_track(0, len(self._data), self._info, self._sizes, self._frame)
-        pcm_i32, res = _atgpu.tta_decoder().decode(self._data + b"\0" * pad, [track])
+        pcm_i32, res = _atgpu.tta_decoder().decode(data, [track])
         r = res[0]
         self._pcm = pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * self.channels]
         self._good = r.n_frames
@@ -311,8 +317,7 @@ class TTADecoder(object):
         self._decoded_from = self._frame
 
     def read(self, pcm_frames):
-        if self._closed:
-            raise ValueError("cannot read closed stream")
+        _check_open(self, "read")
         if self._remaining == 0:
             return pcm.empty_framelist(self.channels, self.bits_per_sample)
         self._decode()
@@ -327,11 +332,7 @@ class TTADecoder(object):
                                    self.bits_per_sample)
 
     def seek(self, pcm_frame_offset):
-        if self._closed:
-            raise ValueError("cannot seek closed stream")
-        pcm_frame_offset = int(pcm_frame_offset)
-        if pcm_frame_offset < 0:
-            raise ValueError("cannot seek to negative value")
+        pcm_frame_offset = _seek_offset(self, pcm_frame_offset)
         # skip whole frames while the next boundary is still short of the
         # offset (the reference compares with <, so an offset on a boundary
         # stops one frame early)
@@ -358,18 +359,16 @@ def decode_tta_batch(images):
     -> list of (status, TtaInfo, int32 interleaved PCM, first bad frame or
     None); status is an ATG_TD_* code (0 = every frame decoded), the PCM ends
     before the first bad frame"""
-    parts, tracks, infos, pos = [], [], [], 0
-    for img in images:
+    images = list(images)
+    data, spans = _atgpu.pack_images(images)
+    tracks, infos = [], []
+    for img, (offset, nbytes) in zip(images, spans):
         st, info, sizes = _atgpu.tta_read_info(img)
         if st:
             raise _tta_init_error(st, info.stage)
-        img = bytes(img)
-        pad = (-len(img)) % 4
-        tracks.append(_atgpu.tta_dec_track(pos, len(img), info, sizes))
-        parts.append(img + b"\0" * pad)
+        tracks.append(_atgpu.tta_dec_track(offset, nbytes, info, sizes))
         infos.append(info)
-        pos += len(img) + pad
-    pcm_i32, res = _atgpu.tta_decoder().decode(b"".join(parts), tracks)
+    pcm_i32, res = _atgpu.tta_decoder().decode(data, tracks)
     out = []
     for info, r in zip(infos, res):
         out.append((r.status, info,
@@ -402,12 +401,7 @@ class SHNDecoder(object):
     """
 
     def __init__(self, file):
-        if isinstance(file, (bytes, bytearray, memoryview)):
-            data = bytes(file)
-        elif hasattr(file, "read"):
-            data = file.read()
-        else:
-            raise TypeError("file must be a file object or bytes")
+        data = _file_bytes(file)
         st, info = _atgpu.shn_read_info(data)
         if st:
             raise _shn_error(_atgpu.SHN_HEADER_ERRORS, st)
@@ -428,8 +422,7 @@ class SHNDecoder(object):
         return self._decoded
 
     def read(self, pcm_frames=None):
-        if self._closed:
-            raise ValueError("cannot read closed stream")
+        _check_open(self, "read")
         status, _, samples, _, _, lengths = self._decode()
         if self._frame >= len(lengths):
             if status != _atgpu.SHN_END_OF_STREAM:
@@ -458,26 +451,24 @@ def decode_shn_batch(images, details=False):
     bytes); status is an ATG_SHN_* code (1 = the stream ended with QUIT), the
     PCM ends before the first incomplete set of channels.  With details, each
     tuple ends with the frame counts of the stream's sets of channels."""
-    parts, tracks, infos, pos = [], [], [], 0
-    for img in images:
-        img = bytes(img)
+    images = list(images)
+    data, spans = _atgpu.pack_images(images)
+    tracks, infos = [], []
+    for img, (offset, nbytes) in zip(images, spans):
         st, info = _atgpu.shn_read_info(img)
         if st:
             raise _shn_error(_atgpu.SHN_HEADER_ERRORS, st)
-        pad = (-len(img)) % 4
-        tracks.append(_atgpu.shn_dec_track(pos, len(img), info))
-        parts.append(img + b"\0" * pad)
+        tracks.append(_atgpu.shn_dec_track(offset, nbytes, info))
         infos.append(info)
-        pos += len(img) + pad
-    dec = _atgpu.shn_decoder()
-    pcm_i32, res, verb = dec.decode(b"".join(parts), tracks)
+    # the block lengths are read inside the decoder's locked decode-and-fetch
+    pcm_i32, res, verb, *lengths = _atgpu.shn_decoder().decode(data, tracks, blocks=details)
     out = []
     for k, (info, r) in enumerate(zip(infos, res)):
         v = verb[r.verbatim_offset:r.verbatim_offset + r.header_bytes + r.footer_bytes].tobytes()
         one = (r.status, info, pcm_i32[r.pcm_offset:r.pcm_offset + r.pcm_frames * info.channels],
                v[:r.header_bytes], v[r.header_bytes:])
         if details:
-            one += ([int(x) for x in dec.fetch_blocks(k)],)
+            one += ([int(x) for x in lengths[0][k]],)
         out.append(one)
     return out
 
@@ -511,12 +502,7 @@ class WavPackDecoder(object):
     """
 
     def __init__(self, file):
-        if isinstance(file, (bytes, bytearray, memoryview)):
-            data = bytes(file)
-        elif hasattr(file, "read"):
-            data = file.read()
-        else:
-            raise TypeError("file must be a file object or bytes")
+        data = _file_bytes(file)
         st, info, blocks = _atgpu.wv_read_info(data)
         if st:
             raise _wv_error(st)
@@ -546,12 +532,12 @@ class WavPackDecoder(object):
         """the sets from the current one on, in one GPU call"""
         if self._decoded_from is not None and self._decoded_from <= self._set:
             return
-        pad = (-len(self._data)) % 4
+        data, _ = _atgpu.pack_images([self._data])
         # 8-bit samples are hashed as unsigned bytes (WavPackDecoder_update_md5sum)
         check = 2 if (self._check_md5 and self._set == 0) else 0
         track = _atgpu.wv_dec_track(0, len(self._data), self._info, self._blocks, self._set,
                                     check_md5=check)
-        pcm_i32, res = _atgpu.wv_decoder().decode(self._data + b"\0" * pad, [track])
+        pcm_i32, res = _atgpu.wv_decoder().decode(data, [track])
         r = res[0]
         self._pcm = pcm_i32[r.sample_offset:r.sample_offset + r.pcm_frames * self.channels]
         self._good = r.n_sets
@@ -564,8 +550,7 @@ class WavPackDecoder(object):
             self._starts.append(self._starts[-1] + self._sets[k][1] * self.channels)
 
     def read(self, pcm_frames):
-        if self._closed:
-            raise ValueError("cannot read closed stream")
+        _check_open(self, "read")
         if self._remaining == 0:
             if self._check_md5 and self._info.has_md5:
                 self._check_md5 = False
@@ -584,11 +569,7 @@ class WavPackDecoder(object):
         return pcm.FrameList._wrap(self._pcm[a:b].copy(), self.channels, self.bits_per_sample)
 
     def seek(self, pcm_frame_offset):
-        if self._closed:
-            raise ValueError("cannot seek closed stream")
-        pcm_frame_offset = int(pcm_frame_offset)
-        if pcm_frame_offset < 0:
-            raise ValueError("cannot seek to negative value")
+        pcm_frame_offset = _seek_offset(self, pcm_frame_offset)
         best, best_set = 0, 0
         for k, (index, samples, initial) in enumerate(self._sets):
             if initial and samples:
@@ -615,19 +596,17 @@ def decode_wavpack_batch(images, md5_mode=1):
     where there is one, agrees), the PCM ends before the first bad set.  An
     image the reference's decoder would not open has its status, no info
     (None) and no PCM."""
-    parts, tracks, infos, pos = [], [], [], 0
+    images = list(images)
+    infos, tables = [], []
     for img in images:
-        img = bytes(img)
         st, info, blocks = _atgpu.wv_read_info(img)
-        if st:
-            infos.append((st, None))
-            continue
-        pad = (-len(img)) % 4
-        tracks.append(_atgpu.wv_dec_track(pos, len(img), info, blocks, check_md5=md5_mode))
-        parts.append(img + b"\0" * pad)
-        infos.append((0, info))
-        pos += len(img) + pad
-    pcm_i32, res = _atgpu.wv_decoder().decode(b"".join(parts), tracks)
+        infos.append((st, None if st else info))
+        tables.append(blocks)
+    good = [k for k, (st, _) in enumerate(infos) if not st]
+    data, spans = _atgpu.pack_images([images[k] for k in good])
+    tracks = [_atgpu.wv_dec_track(offset, nbytes, infos[k][1], tables[k], check_md5=md5_mode)
+              for k, (offset, nbytes) in zip(good, spans)]
+    pcm_i32, res = _atgpu.wv_decoder().decode(data, tracks)
     out, k = [], 0
     for st, info in infos:
         if info is None:
@@ -770,8 +749,7 @@ class OggFlacDecoder(object):
         self._closed = False
 
     def read(self, pcm_frames=None):
-        if self._closed:
-            raise ValueError("cannot read closed stream")
+        _check_open(self, "read")
         if self._finalized:
             return pcm.empty_framelist(self.channels, self.bits_per_sample)
         if self._frame < len(self._sizes):

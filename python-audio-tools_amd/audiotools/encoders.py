@@ -98,6 +98,53 @@ def _frame_sizes_or_none(sizes, block_size):
     return np.asarray(sizes, dtype=np.uint32)
 
 
+_SHARED_NAMES = {"channels": "channels", "channel_mask": "channel mask",
+                 "bits_per_sample": "bits-per-sample", "sample_rate": "sample rate"}
+
+
+def _shared_format(pcmreaders, attrs):
+    """the values of `attrs` that every reader of a batch must share, as ints
+    (a channel mask may be an object); ValueError where one differs"""
+    fmt = tuple(int(getattr(pcmreaders[0], a)) for a in attrs)
+    for r in pcmreaders:
+        if tuple(int(getattr(r, a)) for a in attrs) != fmt:
+            names = [_SHARED_NAMES[a] for a in attrs]
+            raise ValueError("all pcmreaders of a batch must share %s and %s" %
+                             (", ".join(names[:-1]), names[-1]))
+    return fmt
+
+
+def _drain(pcmreaders, block_size, channels, bits_per_sample, irregular=None):
+    """every reader drained as _collect drains it, in order -> (one PCM array,
+    int16 up to 16 bits per sample and int32 above, [(first frame, frames,
+    read sizes or None for plain blocking)]).  With `irregular`, that
+    exception is raised after a reader whose reads were not plain blocking."""
+    parts, tracks, start = [], [], 0
+    for r in pcmreaders:
+        samples, sizes = _collect(r, block_size)
+        sizes = _frame_sizes_or_none(sizes, block_size)
+        if sizes is not None and irregular is not None:
+            raise irregular
+        frames = len(samples) // channels
+        tracks.append((start, frames, sizes))
+        parts.append(samples)
+        start += frames
+    pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    return pcm.astype(np.int16 if bits_per_sample <= 16 else np.int32, copy=False), tracks
+
+
+def _write_images(files, out, results):
+    """image k of `out` (results[k].out_offset, .bytes) to files[k]: an open
+    file object, or a name, opened when its turn comes"""
+    for f, res in zip(files, results):
+        image = memoryview(out[res.out_offset:res.out_offset + res.bytes])
+        if isinstance(f, str):
+            with open(f, "wb") as g:
+                g.write(image)
+        else:
+            f.write(image)
+
+
 def _flac_batch(filenames, pcmreaders, block_size, flac_args, encode):
     """what encode_flac_batch and encode_oggflac_batch share: the readers
     drained to one PCM array, the tracks sharded over the node's GPUs,
@@ -110,25 +157,12 @@ def _flac_batch(filenames, pcmreaders, block_size, flac_args, encode):
         raise ValueError("filenames and pcmreaders differ in length")
     if not pcmreaders:
         return []
-    r0 = pcmreaders[0]
-    channels, bps, rate = r0.channels, r0.bits_per_sample, r0.sample_rate
-    for r in pcmreaders:
-        if (r.channels, r.bits_per_sample, r.sample_rate) != (channels, bps, rate):
-            raise ValueError("all pcmreaders of a batch must share channels, "
-                             "bits-per-sample and sample rate")
+    channels, bps, rate = _shared_format(pcmreaders,
+                                         ("channels", "bits_per_sample", "sample_rate"))
     files = [open(fn, "wb") for fn in filenames]
     try:
         opts = _atgpu.make_options(block_size, *flac_args)
-        parts, tracks, start = [], [], 0
-        for r in pcmreaders:
-            samples, sizes = _collect(r, block_size)
-            frames = len(samples) // channels
-            tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
-            parts.append(samples)
-            start += frames
-        pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-        if bps <= 16:
-            pcm = pcm.astype(np.int16)
+        pcm, tracks = _drain(pcmreaders, block_size, channels, bps)
         # the tracks sharded over the node's GPUs (contiguous groups balanced
         # by frames, one engine per device, _atgpu.batch_devices)
         devs = _atgpu.batch_devices()
@@ -148,8 +182,8 @@ def _flac_batch(filenames, pcmreaders, block_size, flac_args, encode):
         lists = []
         for (t0, t1), (out, results, offsets, pcm_frames) in zip(
                 ranges, _atgpu.run_shards(shard, len(ranges))):
-            for f, res in zip(files[t0:t1], results):
-                f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+            _write_images(files[t0:t1], out, results)
+            for res in results:
                 lo, n = res.first_frame, res.n_frames
                 lists.append([(int(offsets[lo + i]), int(pcm_frames[lo + i]))
                               for i in range(n)])
@@ -237,31 +271,17 @@ def encode_alac_batch(files, pcmreaders, block_size, initial_history, history_mu
     # frame: both refused here
     if not (0 <= minimum_interlacing_leftweight <= maximum_interlacing_leftweight <= 255):
         raise ValueError("interlacing leftweights must satisfy 0 <= minimum <= maximum <= 255")
-    r0 = pcmreaders[0]
-    channels, bps = r0.channels, r0.bits_per_sample
-    if bps not in (16, 24):
+    if pcmreaders[0].bits_per_sample not in (16, 24):
         raise ValueError("bits per sample must be 16 or 24")
-    for r in pcmreaders:
-        if (r.channels, r.bits_per_sample) != (channels, bps):
-            raise ValueError("all pcmreaders of a batch must share channels and "
-                             "bits-per-sample")
-    parts, tracks, start = [], [], 0
-    for r in pcmreaders:
-        samples, sizes = _collect(r, block_size)
-        frames = len(samples) // channels
-        tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
-        parts.append(samples)
-        start += frames
-    pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    if bps <= 16:
-        pcm = pcm.astype(np.int16)
+    channels, bps = _shared_format(pcmreaders, ("channels", "bits_per_sample"))
+    pcm, tracks = _drain(pcmreaders, block_size, channels, bps)
     enc = _atgpu.alac_encoder()
     opts = enc.options(block_size, initial_history, history_multiplier, maximum_k,
                        minimum_interlacing_leftweight, maximum_interlacing_leftweight)
     out, results, fsb = enc.encode(opts, pcm, tracks, channels, bps)
+    _write_images(files, out, results)
     logs = []
-    for f, res in zip(files, results):
-        f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+    for res in results:
         lo = res.first_frameset
         logs.append(([int(x) for x in fsb[lo:lo + res.n_framesets]], int(res.pcm_frames)))
     for r in pcmreaders:
@@ -298,34 +318,19 @@ def encode_tta_batch(files, pcmreaders):
         raise ValueError("files and pcmreaders differ in length")
     if not pcmreaders:
         return []
-    r0 = pcmreaders[0]
-    channels, bps, rate = r0.channels, r0.bits_per_sample, r0.sample_rate
-    if bps not in (8, 16, 24):
+    if pcmreaders[0].bits_per_sample not in (8, 16, 24):
         raise ValueError("bits per sample must be 8, 16 or 24")
-    for r in pcmreaders:
-        if (r.channels, r.bits_per_sample, r.sample_rate) != (channels, bps, rate):
-            raise ValueError("all pcmreaders of a batch must share channels, "
-                             "bits-per-sample and sample rate")
+    channels, bps, rate = _shared_format(pcmreaders,
+                                         ("channels", "bits_per_sample", "sample_rate"))
     block_size = tta_block_size(rate)
     if block_size < 1:
         raise ValueError("sample rate too low for a TTA frame")
-    parts, tracks, start = [], [], 0
-    for r in pcmreaders:
-        # every read is one TTA frame, a short read a short frame
-        # (tta.c:70-82)
-        samples, sizes = _collect(r, block_size)
-        frames = len(samples) // channels
-        tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
-        parts.append(samples)
-        start += frames
-    pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    pcm = pcm.astype(np.int16 if bps <= 16 else np.int32)
+    # every read is one TTA frame, a short read a short frame (tta.c:70-82)
+    pcm, tracks = _drain(pcmreaders, block_size, channels, bps)
     out, results, fsb = _atgpu.tta_encoder().encode(pcm, tracks, channels, bps, rate)
-    logs = []
-    for f, res in zip(files, results):
-        f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
-        lo = res.first_frame
-        logs.append([int(x) for x in fsb[lo:lo + res.n_frames]])
+    _write_images(files, out, results)
+    logs = [[int(x) for x in fsb[res.first_frame:res.first_frame + res.n_frames]]
+            for res in results]
     for r in pcmreaders:
         r.close()
     return logs
@@ -353,30 +358,17 @@ def encode_shn_batch(filenames, pcmreaders, is_big_endian, signed_samples, heade
         raise ValueError("filenames and pcmreaders differ in length")
     if not pcmreaders:
         return
-    channels, bps = pcmreaders[0].channels, pcmreaders[0].bits_per_sample
-    if bps not in (8, 16):
+    if pcmreaders[0].bits_per_sample not in (8, 16):
         raise ValueError("unsupported bits per sample")
-    for r in pcmreaders:
-        if (r.channels, r.bits_per_sample) != (channels, bps):
-            raise ValueError("all pcmreaders of a batch must share channels and "
-                             "bits-per-sample")
+    channels, bps = _shared_format(pcmreaders, ("channels", "bits_per_sample"))
     block_size = int(block_size)
-    parts, tracks, start = [], [], 0
-    for r in pcmreaders:
-        # a read that returns another length than the last becomes a
-        # BLOCKSIZE command (shn.c:213-218)
-        samples, sizes = _collect(r, block_size)
-        frames = len(samples) // channels
-        tracks.append((start, frames, _frame_sizes_or_none(sizes, block_size)))
-        parts.append(samples)
-        start += frames
-    pcm = (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)).astype(np.int16)
+    # a read that returns another length than the last becomes a BLOCKSIZE
+    # command (shn.c:213-218)
+    pcm, tracks = _drain(pcmreaders, block_size, channels, bps)
     out, results = _atgpu.shn_encoder().encode(
         pcm, tracks, channels, bps, block_size, is_big_endian, signed_samples,
         headers=list(header_data), footers=None if footer_data is None else list(footer_data))
-    for name, res in zip(filenames, results):
-        with open(name, "wb") as f:
-            f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
+    _write_images(filenames, out, results)
     for r in pcmreaders:
         r.close()
 
@@ -411,30 +403,16 @@ def encode_wavpack_batch(filenames, pcmreaders, block_size, total_pcm_frames=0,
               else [total_pcm_frames] * len(pcmreaders))
     if len(totals) != len(pcmreaders):
         raise ValueError("total_pcm_frames and pcmreaders differ in length")
-    r0 = pcmreaders[0]
-    fmt = (r0.channels, int(r0.channel_mask), r0.bits_per_sample, r0.sample_rate)
-    channels, mask, bps, rate = fmt
-    for r in pcmreaders:
-        if (r.channels, int(r.channel_mask), r.bits_per_sample, r.sample_rate) != fmt:
-            raise ValueError("all pcmreaders of a batch must share channels, channel mask, "
-                             "bits-per-sample and sample rate")
+    channels, mask, bps, rate = _shared_format(
+        pcmreaders, ("channels", "channel_mask", "bits_per_sample", "sample_rate"))
     block_size = int(block_size)
     if block_size < 1:
         raise ValueError("block size must be at least 1")
     files = [open(fn, "wb") for fn in filenames]
     try:
-        parts, tracks, start = [], [], 0
-        for r in pcmreaders:
-            samples, sizes = _collect(r, block_size)
-            if _frame_sizes_or_none(sizes, block_size) is not None:
-                raise ValueError("WavPack is encoded from whole blocks: every read but the "
-                                 "last must return block_size frames")
-            frames = len(samples) // channels
-            tracks.append((start, frames))
-            parts.append(samples)
-            start += frames
-        pcm = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-        pcm = pcm.astype(np.int16 if bps <= 16 else np.int32)
+        pcm, tracks = _drain(pcmreaders, block_size, channels, bps, irregular=ValueError(
+            "WavPack is encoded from whole blocks: every read but the last must return "
+            "block_size frames"))
         enc = _atgpu.wv_encoder()
         opts = enc.options(block_size, correlation_passes, false_stereo, wasted_bits,
                            joint_stereo)
@@ -444,18 +422,16 @@ def encode_wavpack_batch(filenames, pcmreaders, block_size, total_pcm_frames=0,
             if err.status in (_atgpu.ATG_ERR_INVALID, _atgpu.ATG_ERR_UNSUPPORTED):
                 raise ValueError(err.message)
             raise
-        for f, res, total in zip(files, results, totals):
-            image = out[res.out_offset:res.out_offset + res.bytes]
+        for res, total in zip(results, totals):
             if total and int(total) != res.pcm_frames:
                 # the declared total stays in every header: the reference
                 # fixes the field up only when it was given as 0
-                image = image.copy()
-                pos = 0
+                pos = res.out_offset
                 for size in list(bsb[res.first_block:res.first_block + res.n_blocks]) + [50]:
-                    image[pos + 12:pos + 16] = np.frombuffer(
+                    out[pos + 12:pos + 16] = np.frombuffer(
                         (int(total) & 0xFFFFFFFF).to_bytes(4, "little"), dtype=np.uint8)
                     pos += int(size)
-            f.write(memoryview(image))
+        _write_images(files, out, results)
         for r in pcmreaders:
             r.close()
     finally:
@@ -658,9 +634,8 @@ def encode_flac_files_batch(filenames, sources, block_size, max_lpc_order,
 
         written = []
         for (t0, t1), (out, results) in zip(ranges, _atgpu.run_shards(shard, len(ranges))):
-            for f, res, i in zip(files[t0:t1], results, infos[t0:t1]):
-                f.write(memoryview(out[res.out_offset:res.out_offset + res.bytes]))
-                written.append((int(res.bytes), i.frames))
+            _write_images(files[t0:t1], out, results)
+            written += [(int(res.bytes), i.frames) for res, i in zip(results, infos[t0:t1])]
         return written
     finally:
         for f in files:

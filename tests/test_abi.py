@@ -56,7 +56,7 @@ def test_engine_create_fails_loudly_without_gpu():
     assert e.value.status == _atgpu.ATG_ERR_DEVICE
 
 
-# the eight handle classes with the C functions of their components
+# the ten handle classes with the C functions of their components
 HANDLES = [
     (_atgpu.Engine, "atg_engine", "atg_last_error"),
     (_atgpu.Decoder, "atg_decoder", "atg_decoder_last_error"),
@@ -66,6 +66,8 @@ HANDLES = [
     (_atgpu.TtaDecoder, "atg_tta_decoder", "atg_tta_decoder_last_error"),
     (_atgpu.WvDecoder, "atg_wv_decoder", "atg_wv_decoder_last_error"),
     (_atgpu.WvEncoder, "atg_wv_encoder", "atg_wv_encoder_last_error"),
+    (_atgpu.ShnEncoder, "atg_shn_encoder", "atg_shn_encoder_last_error"),
+    (_atgpu.ShnDecoder, "atg_shn_decoder", "atg_shn_decoder_last_error"),
 ]
 HANDLE_IDS = [h[0].__name__ for h in HANDLES]
 
