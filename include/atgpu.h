@@ -1891,4 +1891,7 @@ int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float
 #ifdef __cplusplus
 }
 #endif
+
+/* DVD-Audio: AOB sector demux and its packed-PCM codec, a block of its own */
+#include "atgpu_dvda.h"
 #endif

@@ -708,6 +708,44 @@ SIGNATURES = {
 # every function include/atgpu.h declares (tests check the .so exports them)
 EXPORTS = tuple(SIGNATURES)
 
+
+# ---- DVD-Audio (include/atgpu_dvda.h, a header of its own that atgpu.h includes)
+class AobTitle(ctypes.Structure):
+    _fields_ = [("byte_offset", c_u64), ("n_sectors", c_u32), ("reserved", c_u32)]
+
+
+class AobSector(ctypes.Structure):
+    _fields_ = [("payload_offset", ctypes.c_uint16), ("payload_length", ctypes.c_uint16),
+                ("status", ctypes.c_uint8), ("codec_id", ctypes.c_uint8),
+                ("group_1_bps", ctypes.c_uint8), ("group_1_rate", ctypes.c_uint8),
+                ("channel_assignment", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 7)]
+
+
+class AobResult(ctypes.Structure):
+    _fields_ = [("status", c_i32), ("stop_sector", c_u32), ("sample_rate", c_u32),
+                ("bits_per_sample", c_u32), ("channels", c_u32), ("channel_mask", c_u32),
+                ("channel_assignment", c_u32), ("reserved", c_u32), ("good_frames", c_u64),
+                ("sample_offset", c_u64)]
+
+
+AOB_SECTOR_BYTES = 2048
+(DVDA_OK, DVDA_BAD_SECTOR, DVDA_EOF, DVDA_UNKNOWN_CODEC, DVDA_MLP,
+ DVDA_UNSUPPORTED) = range(6)
+
+# the prototypes of include/atgpu_dvda.h, applied by load_library() with the
+# table above
+DVDA_SIGNATURES = {
+    "atg_aob_last_error": _LAST_ERROR,
+    "atg_aob_scan_device": (c_int, (P, c_u64, ptr(AobTitle), c_u32, c_int, ptr(AobResult), P64,
+                                    ptr(AobSector), c_u64, P)),
+    "atg_aob_decode_device": (c_int, (P, c_u64, ptr(AobTitle), c_u32, P, c_int, c_u64,
+                                      ptr(AobResult), P)),
+    "atg_aob_decode_host": (c_int, (c_int, P, c_u64, ptr(AobTitle), c_u32, P, c_int, c_u64,
+                                    ptr(AobResult))),
+    "atg_aob_tile_frames": _TILE,
+    "atg_aob_kernel_times": _THREAD_TIMES,
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -723,7 +761,7 @@ def load_library():
                               "`make -C python-audio-tools_amd/csrc` or "
                               "__graft_entry__.build()" % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -2282,6 +2320,80 @@ def pcm_bytes_kernel_times():
     names = (ctypes.c_char_p * 1)()
     ms = (ctypes.c_float * 1)()
     k = lib.atg_pcm_bytes_kernel_times(names, ms, 1)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+# ------------------------------------------------- DVD-Audio AOB (aob_decode.hip)
+def aob_titles(titles):
+    """[(byte_offset, n_sectors)] -> (AobTitle array, count)"""
+    titles = list(titles)
+    arr = (AobTitle * max(1, len(titles)))()
+    for i, (off, n) in enumerate(titles):
+        arr[i].byte_offset, arr[i].n_sectors = off, n
+    return arr, len(titles)
+
+
+def _aob_check(lib, st):
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_aob_last_error().decode("utf-8", "replace"))
+
+
+def aob_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_sectors=False):
+    """sector and layout passes over AOB bytes in device memory
+    (atg_aob_scan_device): ([AobResult], total_samples) with sample_offset
+    laid out for `fmt`, and the AobSector table of all titles' sectors in
+    order as a third item when want_sectors"""
+    lib = load_library()
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (AobResult * max(1, n))()
+    total = ctypes.c_uint64()
+    n_sec = sum(arr[i].n_sectors for i in range(n))
+    sec = (AobSector * max(1, n_sec))() if want_sectors else None
+    _aob_check(lib, lib.atg_aob_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                            ctypes.byref(total), sec, n_sec, None))
+    out = (list(res[:n]), total.value)
+    return out + (list(sec[:n_sec]),) if want_sectors else out
+
+
+def aob_decode_device(d_bytes, bytes_cap, titles, d_pcm, fmt, pcm_cap_samples):
+    """all three passes into d_pcm (atg_aob_decode_device): [AobResult]; raises
+    ATGError(ATG_ERR_CAPACITY) when pcm_cap_samples is too small"""
+    lib = load_library()
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (AobResult * max(1, n))()
+    _aob_check(lib, lib.atg_aob_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
+                                              ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
+                                              None))
+    return list(res[:n])
+
+
+def aob_decode_host(data, titles, fmt=PCM_S32, device=None):
+    """AOB bytes in host memory -> ([AobResult], int16 / int32 numpy array),
+    staged through `device`.  The array is sized from the sectors' byte count,
+    which bounds the samples of any layout."""
+    lib = load_library()
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (AobResult * max(1, n))()
+    cap = sum(arr[i].n_sectors for i in range(n)) * (AOB_SECTOR_BYTES // 2) + 8 * n
+    out = np.zeros(cap, dtype=np.int16 if fmt == PCM_S16 else np.int32)
+    _aob_check(lib, lib.atg_aob_decode_host(
+        default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
+        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap, res))
+    return list(res[:n]), out
+
+
+def aob_tile_frames():
+    """PCM frames per tile of the PCM pass"""
+    return int(load_library().atg_aob_tile_frames())
+
+
+def aob_kernel_times():
+    """{"sectors", "layout", "pcm": ms} of this thread's last call"""
+    lib = load_library()
+    names = (ctypes.c_char_p * 3)()
+    ms = (ctypes.c_float * 3)()
+    k = lib.atg_aob_kernel_times(names, ms, 3)
     return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 

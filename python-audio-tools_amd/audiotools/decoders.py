@@ -37,7 +37,8 @@ kernels wavpack_decode.hip), `OggFlacDecoder` / `decode_oggflac_batch` for
 Ogg FLAC (src/ogg.c, src/decoders/oggflac.c; ogg_demux.hip and
 flac_decode.hip).  `decode_pcm_batch` reads the uncompressed containers (RIFF
 WAVE, AIFF, Sun AU) in a batch, their samples unpacked on the GPU
-(pcm_bytes.hip).
+(pcm_bytes.hip).  `DVDA_Title` / `decode_dvda_batch` read DVD-Audio titles
+(reference src/decoders/aob.c, aobpcm.c; GPU kernels aob_decode.hip).
 There is no CPU decoding path.
 """
 
@@ -765,3 +766,148 @@ class OggFlacDecoder(object):
 
     def close(self):
         self._closed = True
+
+
+# ------------------------------------------------------------------ DVD-Audio
+class DvdaBatch(object):
+    """decode_dvda_batch's answer with the PCM left on the device: .results
+    (one AobResult per title: status, stop_sector, sample_rate,
+    bits_per_sample, channels, channel_mask, channel_assignment, good_frames,
+    sample_offset) and .d_pcm, interleaved int32 in device memory, title i's
+    samples from index results[i].sample_offset; close() frees it"""
+
+    def __init__(self, results, d_pcm, total_samples):
+        self.results, self.d_pcm, self.total_samples = results, d_pcm, total_samples
+
+    def close(self):
+        if self.d_pcm:
+            _atgpu.engine().device_free(self.d_pcm)
+            self.d_pcm = None
+
+
+def _dvda_range(title):
+    """a DVDATitle, or (audio_ts, titleset, start_sector, end_sector) ->
+    (AOB list, start sector)"""
+    from . import dvda
+    if isinstance(title, tuple):
+        audio_ts, titleset, start, end = title
+    else:
+        audio_ts, titleset = title.dvdaudio.audio_ts_path, title.titleset
+        start, end = title.tracks[0].first_sector, title.tracks[-1].last_sector
+    if end < start:
+        raise ValueError("end_sector is before start_sector")
+    return dvda.find_aobs(audio_ts, titleset), start
+
+
+def decode_dvda_batch(titles, on_device=False):
+    """decode DVD-Audio titles in one GPU batch.  titles: audiotools.dvda
+    DVDATitle objects, or (audio_ts, titleset, start_sector, end_sector)
+    tuples.  As in the reference, end_sector does not bound the reads (aob.c
+    reads on into the following sectors of the titleset): a title runs from
+    start_sector to the last sector of the titleset's AOB files, and
+    end_sector is taken for interface parity only.  The host reads that
+    sector range alone, across the ATS_XX_1..9.AOB boundaries.
+    -> per title (AobResult, int32 interleaved PCM of its good_frames), or
+    with on_device a DvdaBatch that keeps the PCM in device memory."""
+    from . import dvda
+    parts, table, pos = [], [], 0
+    for title in titles:
+        aobs, start = _dvda_range(title)
+        data = dvda.read_sectors(aobs, start)
+        table.append((pos, len(data) // _atgpu.AOB_SECTOR_BYTES))
+        parts.append(data)
+        pos += len(data)
+    data = np.frombuffer(b"".join(parts), dtype=np.uint8)
+    eng = _atgpu.engine()
+    d_bytes = eng.device_alloc(max(16, data.nbytes))
+    d_pcm = None
+    try:
+        if data.nbytes:
+            eng.copy_to_device(d_bytes, data)
+        _, total = _atgpu.aob_scan_device(d_bytes, data.nbytes, table, _atgpu.PCM_S32)
+        d_pcm = eng.device_alloc(max(16, 4 * total))
+        res = _atgpu.aob_decode_device(d_bytes, data.nbytes, table, d_pcm, _atgpu.PCM_S32, total)
+        if on_device:
+            batch, d_pcm = DvdaBatch(res, d_pcm, total), None
+            return batch
+        out = eng.copy_to_host(np.empty(max(1, total), dtype=np.int32), d_pcm)
+        return [(r, out[r.sample_offset:r.sample_offset + r.good_frames * r.channels])
+                for r in res]
+    finally:
+        eng.device_free(d_bytes)
+        if d_pcm:
+            eng.device_free(d_pcm)
+
+
+class DVDA_Title(object):
+    """reference src/decoders/aob.c DVDA_Title(audio_ts, titleset,
+    start_sector, end_sector), decoded on the GPU (aob_decode.hip):
+
+      .sample_rate .bits_per_sample .channels .channel_mask
+                         0 until the first next_track(), as in the reference
+      .pcm_frames        frames left in the current track
+      .next_track(pts_ticks)
+                         the next track holds round(pts_ticks * sample_rate /
+                         90000) frames; ValueError "current track has not
+                         been exhausted" before the current one is read out,
+                         IOError for a bad first sector, ValueError for an
+                         unknown codec ID, for MLP (not supported yet) and
+                         for stream attributes the reference asserts on
+      .read(n)           up to n frames of the track as a pcm.FrameList, an
+                         empty one once it is exhausted; IOError "I/O reading
+                         PCM packet" for a read that needs bytes of the
+                         sector the title stops at, after the whole frames
+                         before it have been delivered
+      .close()           no effect, as in the reference
+
+    The title is decoded on the device once, at the first next_track();
+    tracks are consecutive windows of it.  There is no read-ahead: an error
+    surfaces at the read that needs the bad sector.  end_sector does not
+    bound the reads (see decode_dvda_batch).  IOError when the titleset's
+    AOB files cannot be found."""
+
+    def __init__(self, audio_ts, titleset, start_sector, end_sector, cdrom=None):
+        if cdrom is not None:
+            raise ValueError("CPPM-protected discs are not supported: cdrom must be None")
+        self._title = (audio_ts, int(titleset), int(start_sector), int(end_sector))
+        _dvda_range(self._title)     # IOError now, as the reference's constructor
+        self.sample_rate = self.bits_per_sample = self.channels = self.channel_mask = 0
+        self.pcm_frames = 0
+        self._result = self._pcm = None
+        self._pos = 0
+
+    def next_track(self, pts_ticks):
+        if self.pcm_frames:
+            raise ValueError("current track has not been exhausted")
+        if self._result is None:
+            r, samples = decode_dvda_batch([self._title])[0]
+            if r.status == _atgpu.DVDA_BAD_SECTOR and r.stop_sector == 0:
+                raise IOError("I/O error reading initialization packet")
+            if r.status == _atgpu.DVDA_UNKNOWN_CODEC:
+                raise ValueError("unknown codec ID")
+            if r.status == _atgpu.DVDA_MLP:
+                raise ValueError("MLP titles are not supported yet")
+            if r.status not in (_atgpu.DVDA_OK, _atgpu.DVDA_BAD_SECTOR):
+                raise ValueError("unsupported DVD-Audio stream attributes")
+            self._result, self._pcm = r, samples
+            self.sample_rate, self.bits_per_sample = r.sample_rate, r.bits_per_sample
+            self.channels, self.channel_mask = r.channels, r.channel_mask
+        from .dvda import track_frames
+        self.pcm_frames = track_frames(pts_ticks, self.sample_rate)
+
+    def read(self, pcm_frames=4096):
+        if not self.pcm_frames:
+            return pcm.empty_framelist(self.channels, self.bits_per_sample)
+        have = self._result.good_frames - self._pos
+        if have <= 0:
+            raise IOError("I/O reading PCM packet")
+        n = min(max(1, int(pcm_frames)), self.pcm_frames, have)
+        a = self._pos * self.channels
+        self._pos += n
+        self.pcm_frames -= n
+        return pcm.FrameList._wrap(self._pcm[a:a + n * self.channels].copy(), self.channels,
+                                   self.bits_per_sample)
+
+    def close(self):
+        """does nothing, as in the reference: the tracks that follow stay
+        readable after a caller closes the reader of one track"""
