@@ -1894,4 +1894,6 @@ int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float
 
 /* DVD-Audio: AOB sector demux and its packed-PCM codec, a block of its own */
 #include "atgpu_dvda.h"
+/* MLP titles of DVD-Audio discs, on the same title table */
+#include "atgpu_mlp.h"
 #endif

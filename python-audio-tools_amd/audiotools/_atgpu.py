@@ -746,6 +746,41 @@ DVDA_SIGNATURES = {
     "atg_aob_kernel_times": _THREAD_TIMES,
 }
 
+
+# ---- MLP titles (include/atgpu_mlp.h, included by atgpu.h after atgpu_dvda.h)
+class MlpResult(ctypes.Structure):
+    _fields_ = [("status", c_i32), ("stop_sector", c_u32), ("stop_unit", c_u32),
+                ("access_units", c_u32), ("sample_rate", c_u32), ("bits_per_sample", c_u32),
+                ("channels", c_u32), ("channel_mask", c_u32), ("channel_assignment", c_u32),
+                ("substreams", c_u32), ("good_frames", c_u64), ("sample_offset", c_u64)]
+
+
+class MlpUnit(ctypes.Structure):
+    _fields_ = [("offset", c_u64), ("end_sector", c_u32), ("size", ctypes.c_uint16),
+                ("data_start", ctypes.c_uint16), ("substream_end", ctypes.c_uint16 * 2),
+                ("substream_flags", ctypes.c_uint8 * 2), ("flags", ctypes.c_uint8),
+                ("status", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 8)]
+
+
+(MLP_OK, MLP_NOT_MLP, MLP_NO_MAJOR_SYNC, MLP_BAD_SECTOR, MLP_EOF, MLP_IO_ERROR,
+ MLP_INVALID_MAJOR_SYNC, MLP_INVALID_EXTRAWORD, MLP_INVALID_RESTART_HEADER,
+ MLP_INVALID_DECODING_PARAMETERS, MLP_INVALID_MATRIX_PARAMETERS,
+ MLP_INVALID_CHANNEL_PARAMETERS, MLP_INVALID_BLOCK_DATA, MLP_INVALID_FILTER_PARAMETERS,
+ MLP_PARITY_MISMATCH, MLP_CRC8_MISMATCH, MLP_UNSUPPORTED) = range(17)
+MLP_MAX_UNIT_FRAMES = 4096
+
+# the prototypes of include/atgpu_mlp.h, applied by load_library() as well
+MLP_SIGNATURES = {
+    "atg_mlp_last_error": _LAST_ERROR,
+    "atg_mlp_scan_device": (c_int, (P, c_u64, ptr(AobTitle), c_u32, c_int, ptr(MlpResult), P64,
+                                    ptr(MlpUnit), c_u64, P)),
+    "atg_mlp_decode_device": (c_int, (P, c_u64, ptr(AobTitle), c_u32, P, c_int, c_u64,
+                                      ptr(MlpResult), P)),
+    "atg_mlp_decode_host": (c_int, (c_int, P, c_u64, ptr(AobTitle), c_u32, P, c_int, c_u64,
+                                    ptr(MlpResult))),
+    "atg_mlp_kernel_times": _THREAD_TIMES,
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -761,7 +796,8 @@ def load_library():
                               "`make -C python-audio-tools_amd/csrc` or "
                               "__graft_entry__.build()" % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()):
+        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()) +
+                                          list(MLP_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -2394,6 +2430,67 @@ def aob_kernel_times():
     names = (ctypes.c_char_p * 3)()
     ms = (ctypes.c_float * 3)()
     k = lib.atg_aob_kernel_times(names, ms, 3)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+# ------------------------------------------------- MLP titles (mlp_decode.hip)
+def _mlp_check(lib, st):
+    if st != ATG_OK:
+        raise ATGError(st, lib.atg_mlp_last_error().decode("utf-8", "replace"))
+
+
+def mlp_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_units=False):
+    """every pass that writes no PCM over AOB bytes in device memory
+    (atg_mlp_scan_device): ([MlpResult], total_samples) with sample_offset
+    laid out for `fmt`, and the MlpUnit table of all titles' access units in
+    order as a third item when want_units (a sizing call comes first)"""
+    lib = load_library()
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (MlpResult * max(1, n))()
+    total = ctypes.c_uint64()
+    _mlp_check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                            ctypes.byref(total), None, 0, None))
+    if not want_units:
+        return list(res[:n]), total.value
+    n_units = sum(res[i].access_units for i in range(n))
+    units = (MlpUnit * max(1, n_units))()
+    _mlp_check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                            ctypes.byref(total), units, n_units, None))
+    return list(res[:n]), total.value, list(units[:n_units])
+
+
+def mlp_decode_device(d_bytes, bytes_cap, titles, d_pcm, fmt, pcm_cap_samples):
+    """all passes into d_pcm (atg_mlp_decode_device): [MlpResult]; raises
+    ATGError(ATG_ERR_CAPACITY) when pcm_cap_samples is too small"""
+    lib = load_library()
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (MlpResult * max(1, n))()
+    _mlp_check(lib, lib.atg_mlp_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
+                                              ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
+                                              None))
+    return list(res[:n])
+
+
+def mlp_decode_host(data, titles, cap_samples, fmt=PCM_S32, device=None):
+    """AOB bytes in host memory -> ([MlpResult], int16 / int32 numpy array of
+    cap_samples samples), staged through `device`"""
+    lib = load_library()
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
+    res = (MlpResult * max(1, n))()
+    out = np.zeros(max(1, cap_samples), dtype=np.int16 if fmt == PCM_S16 else np.int32)
+    _mlp_check(lib, lib.atg_mlp_decode_host(
+        default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
+        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap_samples, res))
+    return list(res[:n]), out
+
+
+def mlp_kernel_times():
+    """{pass name: ms} of this thread's last MLP call"""
+    lib = load_library()
+    names = (ctypes.c_char_p * 10)()
+    ms = (ctypes.c_float * 10)()
+    k = lib.atg_mlp_kernel_times(names, ms, 10)
     return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 

@@ -769,11 +769,56 @@ class OggFlacDecoder(object):
 
 
 # ------------------------------------------------------------------ DVD-Audio
+class DvdaResult(object):
+    """one title of decode_dvda_batch: the fields of the C ABI's
+    atg_aob_result (status, stop_sector, sample_rate, bits_per_sample,
+    channels, channel_mask, channel_assignment, good_frames, sample_offset)
+    and, for a title whose status is DVDA_MLP, those of atg_mlp_result that
+    it adds: mlp_status (ATG_MLP_*; None for a PCM title), stop_unit,
+    access_units, substreams"""
+
+    FIELDS = ("status", "stop_sector", "sample_rate", "bits_per_sample", "channels",
+              "channel_mask", "channel_assignment", "good_frames", "sample_offset")
+
+    def __init__(self, r, mlp=None, sample_base=0):
+        src = r if mlp is None else mlp
+        for f in self.FIELDS:
+            setattr(self, f, int(getattr(src, f)))
+        self.status = int(r.status)
+        self.sample_offset += sample_base
+        self.mlp_status = None if mlp is None else int(mlp.status)
+        self.stop_unit = 0 if mlp is None else int(mlp.stop_unit)
+        self.access_units = 0 if mlp is None else int(mlp.access_units)
+        self.substreams = 0 if mlp is None else int(mlp.substreams)
+
+    @property
+    def decodes(self):
+        """the title has stream attributes and may have frames"""
+        return bool(self.sample_rate) and (
+            self.status in (_atgpu.DVDA_OK, _atgpu.DVDA_BAD_SECTOR) or self.mlp_status is not None)
+
+
+# the reference's mlp_python_exception / mlp_python_exception_msg per status
+MLP_ERRORS = {
+    _atgpu.MLP_IO_ERROR: (IOError, "I/O error reading MLP stream"),
+    _atgpu.MLP_INVALID_MAJOR_SYNC: (ValueError, "invalid MLP major sync"),
+    _atgpu.MLP_INVALID_EXTRAWORD: (ValueError,
+                                   "invalid extraword present value in substream info"),
+    _atgpu.MLP_INVALID_RESTART_HEADER: (ValueError, "invalid MLP restart header"),
+    _atgpu.MLP_INVALID_DECODING_PARAMETERS: (ValueError, "invalid MLP decoding parameters"),
+    _atgpu.MLP_INVALID_MATRIX_PARAMETERS: (ValueError, "invalid MLP matrix parameters"),
+    _atgpu.MLP_INVALID_CHANNEL_PARAMETERS: (ValueError, "invalid MLP channel parameters"),
+    _atgpu.MLP_INVALID_BLOCK_DATA: (ValueError, "invalid MLP block data"),
+    _atgpu.MLP_INVALID_FILTER_PARAMETERS: (ValueError, "invalid MLP filter parameters"),
+    _atgpu.MLP_PARITY_MISMATCH: (ValueError, "parity mismatch decoding MLP substream"),
+    _atgpu.MLP_CRC8_MISMATCH: (ValueError, "CRC8 mismatch decoding MLP substream"),
+    _atgpu.MLP_UNSUPPORTED: (ValueError, "MLP stream outside the decoder's limits"),
+}
+
+
 class DvdaBatch(object):
     """decode_dvda_batch's answer with the PCM left on the device: .results
-    (one AobResult per title: status, stop_sector, sample_rate,
-    bits_per_sample, channels, channel_mask, channel_assignment, good_frames,
-    sample_offset) and .d_pcm, interleaved int32 in device memory, title i's
+    (one DvdaResult per title) and .d_pcm, interleaved int32 in device memory, title i's
     samples from index results[i].sample_offset; close() frees it"""
 
     def __init__(self, results, d_pcm, total_samples):
@@ -807,7 +852,10 @@ def decode_dvda_batch(titles, on_device=False):
     start_sector to the last sector of the titleset's AOB files, and
     end_sector is taken for interface parity only.  The host reads that
     sector range alone, across the ATS_XX_1..9.AOB boundaries.
-    -> per title (AobResult, int32 interleaved PCM of its good_frames), or
+    Titles whose first sector is MLP (status DVDA_MLP) go through the MLP
+    calls (mlp_decode.hip) in the same batch; their samples follow the PCM
+    titles' in the one output buffer.
+    -> per title (DvdaResult, int32 interleaved PCM of its good_frames), or
     with on_device a DvdaBatch that keeps the PCM in device memory."""
     from . import dvda
     parts, table, pos = [], [], 0
@@ -824,9 +872,19 @@ def decode_dvda_batch(titles, on_device=False):
     try:
         if data.nbytes:
             eng.copy_to_device(d_bytes, data)
-        _, total = _atgpu.aob_scan_device(d_bytes, data.nbytes, table, _atgpu.PCM_S32)
+        scan, n_pcm = _atgpu.aob_scan_device(d_bytes, data.nbytes, table, _atgpu.PCM_S32)
+        mlp = [i for i, r in enumerate(scan) if r.status == _atgpu.DVDA_MLP]
+        mlp_table = [table[i] for i in mlp]
+        n_mlp = _atgpu.mlp_scan_device(d_bytes, data.nbytes, mlp_table, _atgpu.PCM_S32)[1] \
+            if mlp else 0
+        total = n_pcm + n_mlp       # n_pcm is a multiple of 4: 16-byte aligned
         d_pcm = eng.device_alloc(max(16, 4 * total))
-        res = _atgpu.aob_decode_device(d_bytes, data.nbytes, table, d_pcm, _atgpu.PCM_S32, total)
+        res = [DvdaResult(r) for r in _atgpu.aob_decode_device(
+            d_bytes, data.nbytes, table, d_pcm, _atgpu.PCM_S32, n_pcm)]
+        if mlp:
+            for i, m in zip(mlp, _atgpu.mlp_decode_device(
+                    d_bytes, data.nbytes, mlp_table, d_pcm + 4 * n_pcm, _atgpu.PCM_S32, n_mlp)):
+                res[i] = DvdaResult(res[i], m, n_pcm)
         if on_device:
             batch, d_pcm = DvdaBatch(res, d_pcm, total), None
             return batch
@@ -851,15 +909,20 @@ class DVDA_Title(object):
                          90000) frames; ValueError "current track has not
                          been exhausted" before the current one is read out,
                          IOError for a bad first sector, ValueError for an
-                         unknown codec ID, for MLP (not supported yet) and
-                         for stream attributes the reference asserts on
+                         unknown codec ID, for an MLP stream that does not
+                         start with a major sync and for stream attributes
+                         the reference asserts on
       .read(n)           up to n frames of the track as a pcm.FrameList, an
                          empty one once it is exhausted; IOError "I/O reading
                          PCM packet" for a read that needs bytes of the
                          sector the title stops at, after the whole frames
-                         before it have been delivered
+                         before it have been delivered; for an MLP title
+                         "I/O reading MLP packet", or the reference's own
+                         message and exception type for the access unit that
+                         fails (MLP_ERRORS)
       .close()           no effect, as in the reference
 
+    PCM and MLP titles alike (aob_decode.hip, mlp_decode.hip).
     The title is decoded on the device once, at the first next_track();
     tracks are consecutive windows of it.  There is no read-ahead: an error
     surfaces at the read that needs the bad sector.  end_sector does not
@@ -885,9 +948,9 @@ class DVDA_Title(object):
                 raise IOError("I/O error reading initialization packet")
             if r.status == _atgpu.DVDA_UNKNOWN_CODEC:
                 raise ValueError("unknown codec ID")
-            if r.status == _atgpu.DVDA_MLP:
-                raise ValueError("MLP titles are not supported yet")
-            if r.status not in (_atgpu.DVDA_OK, _atgpu.DVDA_BAD_SECTOR):
+            if r.mlp_status == _atgpu.MLP_NO_MAJOR_SYNC:
+                raise ValueError("MLP stream does not start with a major sync")
+            if not r.decodes:
                 raise ValueError("unsupported DVD-Audio stream attributes")
             self._result, self._pcm = r, samples
             self.sample_rate, self.bits_per_sample = r.sample_rate, r.bits_per_sample
@@ -900,7 +963,11 @@ class DVDA_Title(object):
             return pcm.empty_framelist(self.channels, self.bits_per_sample)
         have = self._result.good_frames - self._pos
         if have <= 0:
-            raise IOError("I/O reading PCM packet")
+            if self._result.mlp_status is None:
+                raise IOError("I/O reading PCM packet")
+            kind, text = MLP_ERRORS.get(self._result.mlp_status,
+                                        (IOError, "I/O reading MLP packet"))
+            raise kind(text)
         n = min(max(1, int(pcm_frames)), self.pcm_frames, have)
         a = self._pos * self.channels
         self._pos += n

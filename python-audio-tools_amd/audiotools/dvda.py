@@ -372,9 +372,11 @@ def tracks_to_flac_batch(tracks, targets, compression=None):
         for k, (track, target) in enumerate(zip(tracks, targets)):
             i = next(i for i, x in enumerate(titles) if x is track.title)
             r = batch.results[i]
-            if r.status not in (_atgpu.DVDA_OK, _atgpu.DVDA_BAD_SECTOR) or not r.sample_rate:
+            if not r.decodes:
+                why = DVDA_STATUS_TEXT[r.status] if r.mlp_status is None else \
+                    "MLP status %d" % r.mlp_status
                 results[k] = DecodingError("title %d of titleset %d does not decode: %s" % (
-                    track.title.title, track.titleset, DVDA_STATUS_TEXT[r.status]))
+                    track.title.title, track.titleset, why))
                 continue
             start = sum(track_frames(t.pts_length, r.sample_rate)
                         for t in track.title.tracks[:track.title.tracks.index(track)])
@@ -424,6 +426,6 @@ DVDA_STATUS_TEXT = {
     _atgpu.DVDA_BAD_SECTOR: "bad sector",
     _atgpu.DVDA_EOF: "no sectors",
     _atgpu.DVDA_UNKNOWN_CODEC: "unknown codec ID",
-    _atgpu.DVDA_MLP: "MLP titles are not supported yet",
+    _atgpu.DVDA_MLP: "an MLP title",
     _atgpu.DVDA_UNSUPPORTED: "unsupported PCM stream attributes",
 }

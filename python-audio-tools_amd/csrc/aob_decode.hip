@@ -30,6 +30,7 @@
 
 #include "../../include/atgpu.h"
 #include "aob_common.h"
+#include "aob_passes.h"
 #include "host_common.h"
 #include "table_search.h"
 #include "wave.h"
@@ -46,18 +47,6 @@ const char *const kStageNames[kStages] = {"sectors", "layout", "pcm"};
 thread_local float g_aob_ms[kStages] = {};
 thread_local int g_aob_n = 0;
 
-// a title on the device: its sectors are rows [sec0, sec0 + n_sectors) of
-// the sector and prefix tables
-struct AobTitle {
-    uint64_t byte_offset;
-    uint32_t n_sectors;
-    uint32_t sec0;
-};
-
-struct AobPrefix {
-    uint64_t start; // payload bytes of the title before this sector
-};
-
 // a title with PCM to write: its tiles are [tile0, next run's tile0)
 struct AobRun {
     uint64_t byte_offset, sample_offset, chunks, tile0;
@@ -66,69 +55,17 @@ struct AobRun {
 
 __constant__ AobInverse24 c_inv24 = aob_inverse24();
 
-__global__ __launch_bounds__(kAobBlock) void k_aob_sectors(const uint8_t *__restrict__ bytes,
-                                                           const AobTitle *__restrict__ titles,
-                                                           uint32_t n_titles, uint32_t n_sectors,
-                                                           atg_aob_sector *__restrict__ sectors)
-{
-    for (uint32_t g = blockIdx.x * kAobBlock + threadIdx.x; g < n_sectors;
-         g += gridDim.x * kAobBlock) {
-        const AobTitle t = titles[last_le(titles, n_titles, g, &AobTitle::sec0)];
-        const atg_aob_sector r =
-            aob_walk_sector(bytes + t.byte_offset + (uint64_t)(g - t.sec0) * kAobSector);
-        static_assert(sizeof(atg_aob_sector) == 16, "one 16-byte store per record");
-        *reinterpret_cast<uint4 *>(sectors + g) = *reinterpret_cast<const uint4 *>(&r);
-    }
-}
-
 __global__ __launch_bounds__(kAobBlock) void k_aob_layout(const AobTitle *__restrict__ titles,
                                                           const atg_aob_sector *__restrict__ sectors,
                                                           AobPrefix *__restrict__ prefix,
                                                           atg_aob_result *__restrict__ results)
 {
-    constexpr uint32_t kWaves = kAobBlock / 64;
-    __shared__ uint32_t s_bad[kWaves];
-    __shared__ uint64_t s_sum[kWaves];
     const AobTitle t = titles[blockIdx.x];
-    const atg_aob_sector *sec = sectors + t.sec0;
-    AobPrefix *pre = prefix + t.sec0;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-
-    // a lane's sectors ascend, so its first bad one is its lowest
-    uint32_t bad = t.n_sectors;
-    for (uint32_t i = tid; i < t.n_sectors; i += kAobBlock)
-        if (sec[i].status) {
-            bad = i;
-            break;
-        }
-    bad = wave_min_u32(bad);
-    if (lane == 0)
-        s_bad[wave] = bad;
-    __syncthreads();
-    bad = s_bad[0];
-    for (uint32_t w = 1; w < kWaves; ++w)
-        bad = min(bad, s_bad[w]);
-
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < bad; base += kAobBlock) {
-        const uint32_t i = base + tid;
-        const uint64_t v = i < bad ? sec[i].payload_length : 0;
-        const uint64_t incl = wave_incl_scan_u64(v, (int)lane);
-        __syncthreads(); // the previous round's s_sum has been read
-        if (lane == 63)
-            s_sum[wave] = incl;
-        __syncthreads();
-        uint64_t before = 0, total = 0;
-        for (uint32_t w = 0; w < kWaves; ++w) {
-            before += w < wave ? s_sum[w] : 0;
-            total += s_sum[w];
-        }
-        if (i < bad)
-            pre[i].start = carry + before + incl - v;
-        carry += total;
-    }
-    if (tid == 0)
-        results[blockIdx.x] = aob_title_result(sec, t.n_sectors, bad, carry);
+    uint32_t bad;
+    uint64_t carry;
+    aob_layout_title(t, sectors + t.sec0, prefix + t.sec0, &bad, &carry);
+    if (threadIdx.x == 0)
+        results[blockIdx.x] = aob_title_result(sectors + t.sec0, t.n_sectors, bad, carry);
 }
 
 // sample n of the tile from its staged stream bytes
@@ -240,39 +177,12 @@ struct AobCtx {
 constexpr int kMaxDevices = 64;
 AobCtx g_ctxs[kMaxDevices];
 
-// every check that needs no GPU.  aligned == true: the device entries'
-// alignment rules; the host entry stages into buffers that hold them.
 atg_status check_args(bool aligned, const void *bytes, uint64_t bytes_cap,
                       const atg_aob_title *titles, uint32_t n, int format,
                       const atg_aob_result *results, uint64_t *n_sectors)
 {
-    if (n && (!bytes || !titles || !results))
-        return g_aob_err.fail(ATG_ERR_INVALID, "NULL argument");
-    if (format != ATG_PCM_S16 && format != ATG_PCM_S32)
-        return g_aob_err.fail(ATG_ERR_INVALID, "unknown PCM format");
-    if (aligned && n && ((uintptr_t)bytes & 15u))
-        return g_aob_err.fail(ATG_ERR_INVALID, "the AOB buffer must be 16-byte aligned");
-    if (n > ATG_AOB_MAX_TITLES)
-        return g_aob_err.fail(ATG_ERR_UNSUPPORTED, "more than ATG_AOB_MAX_TITLES titles");
-    if (bytes_cap > ATG_AOB_MAX_BATCH_BYTES)
-        return g_aob_err.fail(ATG_ERR_UNSUPPORTED, "more than ATG_AOB_MAX_BATCH_BYTES bytes");
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const atg_aob_title &t = titles[i];
-        if (t.byte_offset & 15u)
-            return g_aob_err.fail(ATG_ERR_INVALID, "byte_offset must be a multiple of 16");
-        if (t.n_sectors > ATG_AOB_MAX_TITLE_SECTORS)
-            return g_aob_err.fail(ATG_ERR_UNSUPPORTED,
-                                  "a title of more than ATG_AOB_MAX_TITLE_SECTORS sectors");
-        if (t.byte_offset > bytes_cap ||
-            t.n_sectors > (bytes_cap - t.byte_offset) / ATG_AOB_SECTOR_BYTES)
-            return g_aob_err.fail(ATG_ERR_CAPACITY, "a title's sectors pass bytes_cap");
-        total += t.n_sectors;
-    }
-    if (total > 0x7FFFFFFFull)
-        return g_aob_err.fail(ATG_ERR_UNSUPPORTED, "more than 2^31 - 1 sectors in one batch");
-    *n_sectors = total;
-    return ATG_OK;
+    return aob_check_args(g_aob_err, aligned, bytes, bytes_cap, titles, n, format, results,
+                          n_sectors);
 }
 
 atg_status pick_device(const void *d_ptr, AobCtx **ctx)
