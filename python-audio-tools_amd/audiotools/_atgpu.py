@@ -781,6 +781,12 @@ MLP_SIGNATURES = {
     "atg_mlp_kernel_times": _THREAD_TIMES,
 }
 
+# ---- test probes (include/atgpu_probe.h, included by atgpu.h last)
+PROBE_SIGNATURES = {
+    # engine, options, pcm, format, tracks, n, channels, bits, sums, cap, window_n, window
+    "atg_flac_lpc_probe_host": (c_int, _FLAC_ENCODE[:8] + (P, c_u64, c_u32, P)),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -797,7 +803,8 @@ def load_library():
                               "__graft_entry__.build()" % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()) +
-                                          list(MLP_SIGNATURES.items())):
+                                          list(MLP_SIGNATURES.items()) +
+                                          list(PROBE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -1162,6 +1169,27 @@ class Engine(_Handle):
             channels, bits_per_sample, sample_rate, ctypes.c_void_p(d_out),
             out_cap, res))
         return [res[i] for i in range(n)]
+
+    def lpc_probe(self, options, pcm, tracks, channels, bits_per_sample, window_n=0):
+        """test probe (atg_flac_lpc_probe_host): the LPC analysis kernel's raw
+        autocorrelation sums for a batch held in host memory.
+        Returns (sums: float64 array [frames, candidates, max_lpc_order + 1],
+        frames in track order; window: float64 array of window_n values, the
+        table the kernel read for frames of window_n samples, or None)."""
+        pcm, fmt = _host_pcm(pcm)
+        tracks = list(tracks)
+        nf, _nb = self.bounds(options, tracks, channels, bits_per_sample)
+        arr, n, _keep = _track_array(tracks)
+        ncand = 4 if channels == 2 and (options.mid_side or options.adaptive_mid_side) \
+            else channels
+        sums = np.zeros((nf, ncand, options.max_lpc_order + 1), dtype=np.float64)
+        window = np.zeros(window_n, dtype=np.float64) if window_n else None
+        _check(self.lib, self.lib.atg_flac_lpc_probe_host(
+            self.handle, ctypes.byref(options), pcm.ctypes.data_as(ctypes.c_void_p), fmt,
+            arr, n, channels, bits_per_sample, sums.ctypes.data_as(ctypes.c_void_p),
+            sums.size, window_n,
+            window.ctypes.data_as(ctypes.c_void_p) if window_n else None))
+        return sums, window
 
     def oggflac_bounds(self, options, ogg_options, tracks, channels, bits_per_sample):
         arr, n, _keep = _track_array(tracks)

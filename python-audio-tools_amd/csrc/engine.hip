@@ -973,7 +973,7 @@ atg_status enqueue_batch(atg_engine *e, EncSlot &sl, const std::shared_ptr<Plan>
     HIP_TRY(hipEventRecord(ev[0], s_pre));
     HIP_TRY(launch_lpc_analyze(p, d_pcm, fmt, dfr, (const double *)e->windows.p,
                                (int16_t *)sl.coef.p, (int8_t *)sl.shift.p, (uint8_t *)sl.est.p,
-                               s_pre));
+                               nullptr, s_pre));
     HIP_TRY(hipEventRecord(ev[1], s_pre));
     HIP_TRY(hipStreamWaitEvent(e->s_main, ev[1], 0));
     // MD5 chains (a serial hash per track, high-priority waves) on the slot's
@@ -2096,6 +2096,87 @@ atg_status atg_flac_encode_device(atg_engine *e, const atg_flac_options *opts,
     if (st != ATG_OK)
         return st;
     return atg_flac_encode_wait(e, t, results);
+}
+
+namespace {
+// the probe's own device buffers, freed on every way out
+struct ProbeBufs {
+    DevBuf pcm, frames, coef, shift, est, sums;
+    ~ProbeBufs()
+    {
+        for (DevBuf *b : {&pcm, &frames, &coef, &shift, &est, &sums})
+            b->release();
+    }
+};
+} // namespace
+
+atg_status atg_flac_lpc_probe_host(atg_engine *e, const atg_flac_options *opts, const void *pcm,
+                                   atg_pcm_format format, const atg_track *tracks,
+                                   uint32_t n_tracks, uint32_t channels, uint32_t bps,
+                                   double *sums, uint64_t sums_cap, uint32_t window_n,
+                                   double *window)
+{
+    ATG_HANDLE_LOCK(e);
+    if (!e || !pcm || !tracks || !n_tracks || !sums)
+        return g_err.fail(ATG_ERR_INVALID, "NULL argument");
+    if (format == ATG_PCM_S16 && bps > 16)
+        return g_err.fail(ATG_ERR_INVALID, "S16 container with bits_per_sample > 16");
+    if (!engine_idle(e))
+        return g_err.fail(ATG_ERR_INVALID, "the engine has work in flight: wait for it first");
+    Plan pl;
+    atg_status st = make_plan(opts, tracks, n_tracks, channels, bps, 44100, pl);
+    if (st != ATG_OK)
+        return st;
+    FlacParams &p = pl.p;
+    if (!p.try_lpc)
+        return g_err.fail(ATG_ERR_INVALID, "the options disable LPC subframes");
+    const size_t nf = pl.frames.size();
+    const uint32_t M = p.max_lpc_order, K = lpc_probe_lags(p) + 1u;
+    const uint64_t rows = (uint64_t)nf * p.n_cand;
+    if (rows * (M + 1u) > sums_cap)
+        return g_err.fail(ATG_ERR_CAPACITY, "sums buffer too small for this batch");
+    uint64_t pcm_frames = 0;
+    for (uint32_t t = 0; t < n_tracks; ++t)
+        pcm_frames = std::max<uint64_t>(pcm_frames, tracks[t].pcm_offset + tracks[t].pcm_frames);
+    const size_t pcm_bytes = (size_t)pcm_frames * channels * (format == ATG_PCM_S16 ? 2u : 4u);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->s_main;
+    st = prepare_windows(e, pl, s);
+    if (st != ATG_OK)
+        return st;
+    ProbeBufs b;
+    HIP_TRY(b.pcm.ensure(pcm_bytes));
+    HIP_TRY(b.frames.ensure(nf * sizeof(FrameInfo)));
+    HIP_TRY(b.coef.ensure(rows * p.coef_stride * sizeof(int16_t)));
+    HIP_TRY(b.shift.ensure(rows * std::max<uint32_t>(1, M)));
+    HIP_TRY(b.est.ensure(rows));
+    HIP_TRY(b.sums.ensure(rows * K * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(b.pcm.p, pcm, pcm_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b.frames.p, pl.frames.data(), nf * sizeof(FrameInfo),
+                           hipMemcpyHostToDevice, s));
+    // lanes of waves without a frame long enough for LPC write nothing
+    HIP_TRY(hipMemsetAsync(b.sums.p, 0, rows * K * sizeof(double), s));
+    HIP_TRY(launch_lpc_analyze(p, b.pcm.p, (int)format, (const FrameInfo *)b.frames.p,
+                               (const double *)e->windows.p, (int16_t *)b.coef.p,
+                               (int8_t *)b.shift.p, (uint8_t *)b.est.p, (double *)b.sums.p, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<double> raw(rows * K);
+    HIP_TRY(hipMemcpy(raw.data(), b.sums.p, raw.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (window) {
+        // the table the kernel read, back from device memory
+        auto it = e->win_off.find(window_n);
+        if (it == e->win_off.end())
+            return g_err.fail(ATG_ERR_INVALID, "no frame of window_n samples has been analysed");
+        HIP_TRY(hipMemcpy(window, (const double *)e->windows.p + it->second,
+                          (size_t)window_n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    // frame ids -> track order, the instantiation's K sums -> max_lpc_order + 1
+    for (size_t pos = 0; pos < nf; ++pos)
+        for (uint32_t c = 0; c < p.n_cand; ++c)
+            std::memcpy(sums + (pos * p.n_cand + c) * (M + 1u),
+                        raw.data() + ((size_t)pl.order[pos] * p.n_cand + c) * K,
+                        (M + 1u) * sizeof(double));
+    return ATG_OK;
 }
 
 atg_status atg_flac_encode_host_async(atg_engine *e, const atg_flac_options *opts,

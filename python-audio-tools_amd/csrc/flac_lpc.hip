@@ -9,6 +9,12 @@
 // This file is compiled with -ffp-contract=off and `#pragma clang fp
 // contract(off)`, so every product is rounded before its add.
 //
+// The one exception is explicit: where the Tukey window is exactly 1.0 for a
+// sample and the LAGS samples before it, x[n] is the integer sample, every
+// product is exact, and __builtin_fma(hist, x, acc) gives the bits of the
+// rounded multiply and rounded add (lpc_flat.h).  Such "flat groups" skip the
+// window multiply and the LAGS+1 products; nothing is contracted implicitly.
+//
 // Mapping: one lane = one subframe candidate of one frame; the candidates of
 // a frame sit in adjacent lanes (16 frames per wave for stereo mid/side).  Each lane streams its samples once
 // and keeps all LAGS+1 accumulators plus a circular history of the last
@@ -28,6 +34,7 @@
 
 #include "flac_dev.h"
 #include "launch.h"
+#include "lpc_flat.h"
 #include "pcm_read.h"
 #include "residual.h"
 #include "wave.h"
@@ -87,15 +94,69 @@ __device__ __forceinline__ void quantize_store(const double (&lp)[LAGS],
     *shift_out = (int8_t)(shift >= 0 ? shift : 0);
 }
 
+// The K accumulator chains over one group of K samples.  FLAT: every sample of
+// the group and the K-1 before it are unwindowed integers (lpc_flat.h), the
+// products are exact and one explicit fused multiply-add per term gives the
+// reference's bits; otherwise a rounded multiply, then a rounded add.
+template <int K, bool FLAT>
+__device__ __forceinline__ void lag_chains(const double (&xv)[K], double (&acc)[K],
+                                           double (&hist)[K])
+{
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        const double x = xv[u];
+        hist[u] = x;
+#pragma unroll
+        for (int L = 0; L < K; ++L) {
+            if (FLAT) {
+                acc[L] = __builtin_fma(hist[(u - L + K) % K], x, acc[L]);
+            } else {
+                const double prod = hist[(u - L + K) % K] * x;
+                acc[L] = acc[L] + prod;
+            }
+        }
+    }
+}
+
 // Autocorrelation of one candidate, streamed K samples at a time: all loads
 // of a group are issued together (indices clamped, no branches), then the K
 // accumulator chains run.  Positions past this lane's N contribute x = 0, which adds +-0.0
 // to accumulators that are never -0.0 (exact no-op).
+//
+// One span [j0, jend) of it.  FLAT: every group of the span is a flat group;
+// the loaded window value is 1.0 there, so x is the sample either way and
+// only the chains differ.  Lanes with n_loop == 0 carry x = 0 through a flat
+// span too: fma(0, 0, acc) is acc.
+template <int MODE, typename T, int K, bool FLAT>
+__device__ __forceinline__ void autocorr_span(const T *__restrict__ src,
+                                              const double *__restrict__ win, uint32_t ch,
+                                              uint32_t cand, uint32_t n_loop, uint32_t nlast,
+                                              uint32_t &j0, uint32_t jend, int32_t (&sv)[K],
+                                              double (&wv)[K], double (&acc)[K],
+                                              double (&hist)[K])
+{
+    for (; j0 < jend; j0 += K) {
+        double xv[K];
+#pragma unroll
+        for (int u = 0; u < K; ++u)
+            xv[u] = (j0 + (uint32_t)u < n_loop) ? (double)sv[u] * wv[u] : 0.0;
+#pragma unroll
+        for (int u = 0; u < K; ++u) {
+            const uint32_t j = min(j0 + K + (uint32_t)u, nlast);
+            sv[u] = cand_at<MODE>(src, j, ch, cand);
+            wv[u] = win[j];
+        }
+        lag_chains<K, FLAT>(xv, acc, hist);
+    }
+}
+
+// `flat` is wave-uniform, and empty unless the active lanes share one N and
+// the candidates are narrow enough: the walk is taper, flat span, taper.
 template <int MODE, typename T, int K>
 __device__ __forceinline__ void autocorr(const T *__restrict__ src, const double *__restrict__ win,
                                          uint32_t ch, uint32_t cand, uint32_t n_loop,
-                                         uint32_t nlast, uint32_t n_max, double (&acc)[K],
-                                         double (&hist)[K])
+                                         uint32_t nlast, uint32_t n_max, LpcFlatRange flat,
+                                         double (&acc)[K], double (&hist)[K])
 {
     // software pipeline: the loads of group g+1 are in flight while the
     // chains of group g run
@@ -107,27 +168,78 @@ __device__ __forceinline__ void autocorr(const T *__restrict__ src, const double
         sv[u] = cand_at<MODE>(src, j, ch, cand);
         wv[u] = win[j];
     }
-    for (uint32_t j0 = 0; j0 < n_max; j0 += K) {
+    uint32_t j0 = 0;
+    // (PCM_MS16 comes here only with mixed N, the uniform case being the hot
+    // path's: one tapered walk)
+    if (MODE != PCM_MS16) {
+        // first flat group's start and the last one's end, on the group grid
+        const uint32_t k0 = min((flat.lo + K - 1u) / K * K, n_max);
+        const uint32_t k1 = min(max(flat.hi / K * K, k0), n_max);
+        autocorr_span<MODE, T, K, false>(src, win, ch, cand, n_loop, nlast, j0, k0, sv, wv, acc,
+                                         hist);
+        autocorr_span<MODE, T, K, true>(src, win, ch, cand, n_loop, nlast, j0, k1, sv, wv, acc,
+                                        hist);
+    }
+    autocorr_span<MODE, T, K, false>(src, win, ch, cand, n_loop, nlast, j0, n_max, sv, wv, acc,
+                                     hist);
+}
+
+// One span [j0, jend) of the hot path in groups of 4K samples: K dwordx4
+// loads (4 pairs each) per lane, all issued before the first is used (left
+// to the compiler, they came two at a time, each pair waited before the next
+// was issued: K/2 memory round trips per group).  FLAT: every group of the
+// span is a flat group -- no window load or multiply, one FMA per term.
+template <int K, bool FLAT>
+__device__ __forceinline__ void ms16_span4(const uint4 *__restrict__ q4,
+                                           const double *__restrict__ win, uint32_t wts, int gsh,
+                                           uint32_t &j0, uint32_t jend, double (&acc)[K],
+                                           double (&hist)[K])
+{
+    for (; j0 + 4u * K <= jend; j0 += 4u * K) {
+        uint32_t pv[4 * K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const uint4 v = q4[(j0 >> 2) + (uint32_t)i];
+            pv[4 * i] = v.x;
+            pv[4 * i + 1] = v.y;
+            pv[4 * i + 2] = v.z;
+            pv[4 * i + 3] = v.w;
+        }
+#pragma unroll
+        for (int i = 0; i < 4 * K; ++i)
+            asm volatile("" : "+v"(pv[i]));
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+            double xv[K];
+#pragma unroll
+            for (int u = 0; u < K; ++u) {
+                const int v = __builtin_amdgcn_sdot2(
+                    __builtin_bit_cast(short2_t, pv[sub * K + u]),
+                    __builtin_bit_cast(short2_t, wts), 0, false);
+                xv[u] = FLAT ? (double)(v >> gsh)
+                             : (double)(v >> gsh) * win[j0 + (uint32_t)(sub * K + u)];
+            }
+            lag_chains<K, FLAT>(xv, acc, hist);
+        }
+    }
+}
+
+// The same in groups of K samples, one dword load per sample.
+template <int K, bool FLAT>
+__device__ __forceinline__ void ms16_span1(const uint32_t *__restrict__ pairs,
+                                           const double *__restrict__ win, uint32_t wts, int gsh,
+                                           uint32_t &j0, uint32_t jend, double (&acc)[K],
+                                           double (&hist)[K])
+{
+    for (; j0 + K <= jend; j0 += K) {
         double xv[K];
 #pragma unroll
-        for (int u = 0; u < K; ++u)
-            xv[u] = (j0 + (uint32_t)u < n_loop) ? (double)sv[u] * wv[u] : 0.0;
-#pragma unroll
         for (int u = 0; u < K; ++u) {
-            const uint32_t j = min(j0 + K + (uint32_t)u, nlast);
-            sv[u] = cand_at<MODE>(src, j, ch, cand);
-            wv[u] = win[j];
+            const int v = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, pairs[j0 + u]),
+                                                 __builtin_bit_cast(short2_t, wts), 0, false);
+            xv[u] = FLAT ? (double)(v >> gsh) : (double)(v >> gsh) * win[j0 + u];
         }
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            const double x = xv[u];
-            hist[u] = x;
-#pragma unroll
-            for (int L = 0; L < K; ++L) {
-                const double prod = hist[(u - L + K) % K] * x;
-                acc[L] = acc[L] + prod;
-            }
-        }
+        lag_chains<K, FLAT>(xv, acc, hist);
     }
 }
 
@@ -137,77 +249,39 @@ __device__ __forceinline__ void autocorr(const T *__restrict__ src, const double
 // weights and a shift: L (1,0)>>0, R (0,1)>>0, mid (1,1)>>1, side (1,-1)>>0.
 // Full groups of K samples use immediate-offset loads; only the last
 // partial group clamps and masks.
+//
+// Groups (4K samples with VEC4, then K) that lie wholly inside the FMA range
+// of this block length, with the margin of this instantiation's largest lag
+// K - 1, are flat groups: the walk is taper, flat span, taper.  The last,
+// partial group holds sample N - 1, which is never flat.
 template <int K, bool VEC4>
 __device__ __forceinline__ void autocorr_ms16(const uint32_t *__restrict__ pairs,
                                               const double *__restrict__ win, uint32_t cand,
                                               uint32_t N, double (&acc)[K], double (&hist)[K])
 {
+    const LpcFlatRange flat = lpc_flat_range(N, (uint32_t)K - 1u);
     const uint32_t wts = cand == 0u ? 0x00000001u : cand == 1u ? 0x00010000u
                        : cand == 2u ? 0x00010001u : 0xFFFF0001u;
     const int gsh = cand == 2u ? 1 : 0;
     const uint32_t nfull = N / K * K;
     uint32_t j0 = 0;
     if (VEC4) {
-        // groups of 4K samples: K dwordx4 loads (4 pairs each) per lane,
-        // all issued before the first is used (left to the compiler, they
-        // came two at a time, each pair waited before the next was issued:
-        // K/2 memory round trips per group)
+        constexpr uint32_t G = 4u * K;
         const uint4 *__restrict__ q4 = (const uint4 *)pairs;
-        for (; j0 + 4u * K <= N; j0 += 4u * K) {
-            uint32_t pv[4 * K];
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const uint4 v = q4[(j0 >> 2) + (uint32_t)i];
-                pv[4 * i] = v.x;
-                pv[4 * i + 1] = v.y;
-                pv[4 * i + 2] = v.z;
-                pv[4 * i + 3] = v.w;
-            }
-#pragma unroll
-            for (int i = 0; i < 4 * K; ++i)
-                asm volatile("" : "+v"(pv[i]));
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) {
-                double xv[K];
-#pragma unroll
-                for (int u = 0; u < K; ++u) {
-                    const int v = __builtin_amdgcn_sdot2(
-                        __builtin_bit_cast(short2_t, pv[sub * K + u]),
-                        __builtin_bit_cast(short2_t, wts), 0, false);
-                    xv[u] = (double)(v >> gsh) * win[j0 + (uint32_t)(sub * K + u)];
-                }
-#pragma unroll
-                for (int u = 0; u < K; ++u) {
-                    const double x = xv[u];
-                    hist[u] = x;
-#pragma unroll
-                    for (int L = 0; L < K; ++L) {
-                        const double prod = hist[(u - L + K) % K] * x;
-                        acc[L] = acc[L] + prod;
-                    }
-                }
-            }
-        }
+        const uint32_t nvec = N / G * G;
+        // first flat group's start and the last one's end, on the group grid
+        const uint32_t g0 = min((flat.lo + G - 1u) / G * G, nvec);
+        const uint32_t g1 = min(max(flat.hi / G * G, g0), nvec);
+        ms16_span4<K, false>(q4, win, wts, gsh, j0, g0, acc, hist);
+        ms16_span4<K, true>(q4, win, wts, gsh, j0, g1, acc, hist);
+        ms16_span4<K, false>(q4, win, wts, gsh, j0, nvec, acc, hist);
     }
-    for (; j0 < nfull; j0 += K) {
-        double xv[K];
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            const int v = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, pairs[j0 + u]),
-                                                 __builtin_bit_cast(short2_t, wts), 0, false);
-            xv[u] = (double)(v >> gsh) * win[j0 + u];
-        }
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            const double x = xv[u];
-            hist[u] = x;
-#pragma unroll
-            for (int L = 0; L < K; ++L) {
-                const double prod = hist[(u - L + K) % K] * x;
-                acc[L] = acc[L] + prod;
-            }
-        }
-    }
+    // j0 is a multiple of K here
+    const uint32_t k0 = min(max((flat.lo + K - 1u) / K * K, j0), nfull);
+    const uint32_t k1 = min(max(flat.hi / K * K, k0), nfull);
+    ms16_span1<K, false>(pairs, win, wts, gsh, j0, k0, acc, hist);
+    ms16_span1<K, true>(pairs, win, wts, gsh, j0, k1, acc, hist);
+    ms16_span1<K, false>(pairs, win, wts, gsh, j0, nfull, acc, hist);
     if (j0 < N) {
         double xv[K];
 #pragma unroll
@@ -217,16 +291,7 @@ __device__ __forceinline__ void autocorr_ms16(const uint32_t *__restrict__ pairs
                                                  __builtin_bit_cast(short2_t, wts), 0, false);
             xv[u] = j0 + (uint32_t)u < N ? (double)(v >> gsh) * win[j] : 0.0;
         }
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            const double x = xv[u];
-            hist[u] = x;
-#pragma unroll
-            for (int L = 0; L < K; ++L) {
-                const double prod = hist[(u - L + K) % K] * x;
-                acc[L] = acc[L] + prod;
-            }
-        }
+        lag_chains<K, false>(xv, acc, hist);
     }
 }
 
@@ -235,7 +300,7 @@ __global__ __launch_bounds__(64) void k_lpc_analyze(
     FlacParams p, const T *__restrict__ pcm,
     const FrameInfo *__restrict__ frames, const double *__restrict__ windows,
     int16_t *__restrict__ coef_tab, int8_t *__restrict__ shift_tab,
-    uint8_t *__restrict__ est_tab)
+    uint8_t *__restrict__ est_tab, double *__restrict__ probe)
 {
     constexpr int K = LAGS + 1;
     // lanes [c*k, c*k + c) = the c candidates of one frame: they read the
@@ -278,15 +343,36 @@ __global__ __launch_bounds__(64) void k_lpc_analyze(
             autocorr_ms16<K, true>((const uint32_t *)src, wu, cand, n_first, acc, hist);
         else
             autocorr_ms16<K, false>((const uint32_t *)src, wu, cand, n_first, acc, hist);
-    } else switch (mode) {
-    case PCM_MS16:
-        autocorr<PCM_MS16, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, acc, hist);
-        break;
-    case PCM_MS:
-        autocorr<PCM_MS, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, acc, hist);
-        break;
-    default:
-        autocorr<PCM_CH, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, acc, hist);
+    } else {
+        // the general path takes flat groups only when the active lanes share
+        // one N and the widest candidate (the side channel has one bit more)
+        // keeps its products exact; otherwise the range is empty
+        const uint32_t width = p.bps + (ms ? 1u : 0u);
+        LpcFlatRange gflat = {0u, 0u};
+        if (uniform_n && width <= LPC_FLAT_MAX_BITS)
+            gflat = lpc_flat_range(n_first, (uint32_t)LAGS);
+        switch (mode) {
+        case PCM_MS16:
+            autocorr<PCM_MS16, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, gflat, acc,
+                                     hist);
+            break;
+        case PCM_MS:
+            autocorr<PCM_MS, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, gflat, acc,
+                                   hist);
+            break;
+        default:
+            autocorr<PCM_CH, T, K>(src, win, p.channels, cand, n_loop, nlast, n_max, gflat, acc,
+                                   hist);
+        }
+    }
+    // test probe (atg_flac_lpc_probe_host): the raw sums of every active lane
+    if (probe) {
+        if (active) {
+            double *__restrict__ row = probe + ((size_t)f * p.n_cand + cand) * (size_t)K;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                row[k] = acc[k];
+        }
     }
     if (!do_lpc)
         return;
@@ -364,12 +450,12 @@ __global__ __launch_bounds__(64) void k_lpc_analyze(
 template <typename T, int LAGS>
 static hipError_t launch_t(const FlacParams &p, const T *pcm, const FrameInfo *frames,
                            const double *windows, int16_t *coef_tab,
-                           int8_t *shift_tab, uint8_t *est_tab, hipStream_t s)
+                           int8_t *shift_tab, uint8_t *est_tab, double *probe, hipStream_t s)
 {
     const uint32_t fpw = 64u / p.n_cand;
     dim3 grid((p.n_frames + fpw - 1u) / fpw);
     hipLaunchKernelGGL((k_lpc_analyze<T, LAGS>), grid, dim3(64), 0, s, p, pcm,
-                       frames, windows, coef_tab, shift_tab, est_tab);
+                       frames, windows, coef_tab, shift_tab, est_tab, probe);
     return hipGetLastError();
 }
 
@@ -377,27 +463,33 @@ template <typename T>
 static hipError_t launch_lags(const FlacParams &p, const T *pcm,
                               const FrameInfo *frames, const double *windows,
                               int16_t *coef_tab, int8_t *shift_tab,
-                              uint8_t *est_tab, hipStream_t s)
+                              uint8_t *est_tab, double *probe, hipStream_t s)
 {
-    const uint32_t M = p.max_lpc_order;
-    if (M <= 8)
-        return launch_t<T, 8>(p, pcm, frames, windows, coef_tab, shift_tab, est_tab, s);
-    if (M <= 12)
-        return launch_t<T, 12>(p, pcm, frames, windows, coef_tab, shift_tab, est_tab, s);
+    const uint32_t lags = lpc_probe_lags(p);
+    if (lags == 8)
+        return launch_t<T, 8>(p, pcm, frames, windows, coef_tab, shift_tab, est_tab, probe, s);
+    if (lags == 12)
+        return launch_t<T, 12>(p, pcm, frames, windows, coef_tab, shift_tab, est_tab, probe, s);
     return launch_t<T, ATG_MAX_LPC>(p, pcm, frames, windows, coef_tab, shift_tab,
-                                    est_tab, s);
+                                    est_tab, probe, s);
+}
+
+// LAGS of the instantiation that runs for these parameters
+uint32_t lpc_probe_lags(const FlacParams &p)
+{
+    return p.max_lpc_order <= 8 ? 8u : p.max_lpc_order <= 12 ? 12u : (uint32_t)ATG_MAX_LPC;
 }
 
 hipError_t launch_lpc_analyze(const FlacParams &p, const void *pcm, int fmt,
                               const FrameInfo *frames, const double *windows,
                               int16_t *coef_tab, int8_t *shift_tab,
-                              uint8_t *est_tab, hipStream_t s)
+                              uint8_t *est_tab, double *probe, hipStream_t s)
 {
     if (p.max_lpc_order == 0 || !p.try_lpc || p.n_frames == 0)
         return hipSuccess;
     if (fmt == 0)
         return launch_lags<int16_t>(p, (const int16_t *)pcm, frames, windows,
-                                    coef_tab, shift_tab, est_tab, s);
+                                    coef_tab, shift_tab, est_tab, probe, s);
     return launch_lags<int32_t>(p, (const int32_t *)pcm, frames, windows,
-                                coef_tab, shift_tab, est_tab, s);
+                                coef_tab, shift_tab, est_tab, probe, s);
 }

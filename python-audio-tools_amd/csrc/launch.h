@@ -5,11 +5,13 @@
 
 #include "flac_dev.h"
 
-// flac_lpc.hip
+// flac_lpc.hip.  probe (null in production): every lane's raw
+// autocorrelation sums, lpc_probe_lags(p) + 1 doubles per (frame, candidate)
 hipError_t launch_lpc_analyze(const FlacParams &p, const void *pcm, int fmt,
                               const FrameInfo *frames, const double *windows,
                               int16_t *coef_tab, int8_t *shift_tab,
-                              uint8_t *est_tab, hipStream_t s);
+                              uint8_t *est_tab, double *probe, hipStream_t s);
+uint32_t lpc_probe_lags(const FlacParams &p);
 // flac_search.hip
 hipError_t launch_subframe_search(const FlacParams &p, const void *pcm, int fmt,
                                   const FrameInfo *frames,
