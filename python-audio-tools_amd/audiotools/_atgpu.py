@@ -811,9 +811,21 @@ def load_library():
         return lib
 
 
-def _check(lib, status):
+def _check(lib, status, component=""):
+    """raise ATGError unless status is ATG_OK, with the text of the engine's
+    atg_last_error or of atg_<component>_last_error"""
     if status != ATG_OK:
-        raise ATGError(status, lib.atg_last_error().decode("utf-8", "replace"))
+        last = getattr(lib, "atg_%slast_error" % (component and component + "_"))
+        raise ATGError(status, last().decode("utf-8", "replace"))
+
+
+def _thread_times(fn, cap):
+    """{stage: ms} of this thread's last call, from a component's
+    atg_*_kernel_times `fn`"""
+    names = (ctypes.c_char_p * cap)()
+    ms = (ctypes.c_float * cap)()
+    k = fn(names, ms, cap)
+    return {names[i].decode(): float(ms[i]) for i in range(k)}
 
 
 def make_options(block_size, max_lpc_order, min_residual_partition_order,
@@ -2183,14 +2195,8 @@ def pcm_convert(kind, pcm, channels, in_bps, out_bps=None, channel_mask=0,
         channels, channel_mask, in_bps, in_bps if out_bps is None else out_bps,
         d.ctypes.data_as(ctypes.c_void_p) if d is not None else None,
         0 if d is None else len(d), dither_bit0)
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_pcm_convert_last_error().decode("utf-8", "replace"))
+    _check(lib, st, "pcm_convert")
     return out[:frames * oc]
-
-
-def _rg_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_replaygain_last_error().decode("utf-8", "replace"))
 
 
 def replaygain_device(d_pcm, tracks, n_albums=0, d_album_hist=None):
@@ -2201,9 +2207,9 @@ def replaygain_device(d_pcm, tracks, n_albums=0, d_album_hist=None):
     arr = (RgTrack * max(1, n))(*tracks)
     res = (RgResult * max(1, n))()
     peaks = (ctypes.c_double * max(1, n_albums))()
-    _rg_check(lib, lib.atg_replaygain_device(
+    _check(lib, lib.atg_replaygain_device(
         ctypes.c_void_p(d_pcm), arr, n, n_albums, res,
-        ctypes.c_void_p(d_album_hist) if d_album_hist else None, peaks, None))
+        ctypes.c_void_p(d_album_hist) if d_album_hist else None, peaks, None), "replaygain")
     return [res[i] for i in range(n)], [peaks[i] for i in range(n_albums)]
 
 
@@ -2211,7 +2217,7 @@ def replaygain_hist_gain(d_hist, n):
     """analyzeResult of n device histograms -> list of gains (NaN = none)"""
     lib = load_library()
     g = (ctypes.c_double * max(1, n))()
-    _rg_check(lib, lib.atg_replaygain_hist_gain(ctypes.c_void_p(d_hist), n, g, None))
+    _check(lib, lib.atg_replaygain_hist_gain(ctypes.c_void_p(d_hist), n, g, None), "replaygain")
     return [g[i] for i in range(n)]
 
 
@@ -2281,8 +2287,7 @@ def _ar_call(call, tracks, max_offset):
     res = (ArResult * max(1, n))()
     table = np.zeros((n, 2 * max_offset + 1), dtype=np.uint32)
     st = call(lib, arr, n, res, table.ctypes.data_as(ctypes.c_void_p))
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_accuraterip_last_error().decode("utf-8", "replace"))
+    _check(lib, st, "accuraterip")
     return [res[i] for i in range(n)], table
 
 
@@ -2322,29 +2327,24 @@ def pcm_runs(runs):
     return arr, len(runs)
 
 
-def _pb_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_pcm_bytes_last_error().decode("utf-8", "replace"))
-
-
 def pcm_unpack_device(d_bytes, bytes_cap, layout, runs, d_pcm, fmt, pcm_cap_samples):
     """packed bytes in device memory -> interleaved int16 (PCM_S16) or int32
     (PCM_S32) in device memory, one launch for all runs (atg_pcm_unpack_device);
     runs: [(byte_offset, samples, sample_offset)] or a pcm_runs() pair"""
     lib = load_library()
     arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
-    _pb_check(lib, lib.atg_pcm_unpack_device(
+    _check(lib, lib.atg_pcm_unpack_device(
         ctypes.c_void_p(d_bytes), bytes_cap, layout, arr, n, ctypes.c_void_p(d_pcm), fmt,
-        pcm_cap_samples, None))
+        pcm_cap_samples, None), "pcm_bytes")
 
 
 def pcm_pack_device(d_pcm, fmt, pcm_cap_samples, layout, runs, d_bytes, bytes_cap):
     """the inverse (atg_pcm_pack_device): only the runs' packed bytes are written"""
     lib = load_library()
     arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
-    _pb_check(lib, lib.atg_pcm_pack_device(
+    _check(lib, lib.atg_pcm_pack_device(
         ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, layout, arr, n, ctypes.c_void_p(d_bytes),
-        bytes_cap, None))
+        bytes_cap, None), "pcm_bytes")
 
 
 def pcm_unpack_host(data, layout, runs, out, device=None):
@@ -2354,9 +2354,9 @@ def pcm_unpack_host(data, layout, runs, out, device=None):
     a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
     arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
     fmt = PCM_S16 if out.dtype == np.int16 else PCM_S32
-    _pb_check(lib, lib.atg_pcm_unpack_host(
+    _check(lib, lib.atg_pcm_unpack_host(
         default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
-        a.nbytes, layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, len(out)))
+        a.nbytes, layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, len(out)), "pcm_bytes")
     return out
 
 
@@ -2367,9 +2367,9 @@ def pcm_pack_host(pcm, layout, runs, out, device=None):
     a = np.ascontiguousarray(pcm)
     arr, n = runs if isinstance(runs, tuple) else pcm_runs(runs)
     fmt = PCM_S16 if a.dtype == np.int16 else PCM_S32
-    _pb_check(lib, lib.atg_pcm_pack_host(
+    _check(lib, lib.atg_pcm_pack_host(
         default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p), fmt,
-        len(a), layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+        len(a), layout, arr, n, out.ctypes.data_as(ctypes.c_void_p), out.nbytes), "pcm_bytes")
     return out
 
 
@@ -2380,11 +2380,7 @@ def pcm_bytes_tile_samples():
 
 def pcm_bytes_kernel_times():
     """{"unpack" or "pack": ms} of this thread's last launch"""
-    lib = load_library()
-    names = (ctypes.c_char_p * 1)()
-    ms = (ctypes.c_float * 1)()
-    k = lib.atg_pcm_bytes_kernel_times(names, ms, 1)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    return _thread_times(load_library().atg_pcm_bytes_kernel_times, 1)
 
 
 # ------------------------------------------------- DVD-Audio AOB (aob_decode.hip)
@@ -2395,11 +2391,6 @@ def aob_titles(titles):
     for i, (off, n) in enumerate(titles):
         arr[i].byte_offset, arr[i].n_sectors = off, n
     return arr, len(titles)
-
-
-def _aob_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_aob_last_error().decode("utf-8", "replace"))
 
 
 def aob_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_sectors=False):
@@ -2413,8 +2404,8 @@ def aob_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_sectors=False)
     total = ctypes.c_uint64()
     n_sec = sum(arr[i].n_sectors for i in range(n))
     sec = (AobSector * max(1, n_sec))() if want_sectors else None
-    _aob_check(lib, lib.atg_aob_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
-                                            ctypes.byref(total), sec, n_sec, None))
+    _check(lib, lib.atg_aob_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                        ctypes.byref(total), sec, n_sec, None), "aob")
     out = (list(res[:n]), total.value)
     return out + (list(sec[:n_sec]),) if want_sectors else out
 
@@ -2425,9 +2416,9 @@ def aob_decode_device(d_bytes, bytes_cap, titles, d_pcm, fmt, pcm_cap_samples):
     lib = load_library()
     arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
     res = (AobResult * max(1, n))()
-    _aob_check(lib, lib.atg_aob_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
-                                              ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
-                                              None))
+    _check(lib, lib.atg_aob_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
+                                          ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
+                                          None), "aob")
     return list(res[:n])
 
 
@@ -2441,9 +2432,9 @@ def aob_decode_host(data, titles, fmt=PCM_S32, device=None):
     res = (AobResult * max(1, n))()
     cap = sum(arr[i].n_sectors for i in range(n)) * (AOB_SECTOR_BYTES // 2) + 8 * n
     out = np.zeros(cap, dtype=np.int16 if fmt == PCM_S16 else np.int32)
-    _aob_check(lib, lib.atg_aob_decode_host(
+    _check(lib, lib.atg_aob_decode_host(
         default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
-        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap, res))
+        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap, res), "aob")
     return list(res[:n]), out
 
 
@@ -2454,19 +2445,10 @@ def aob_tile_frames():
 
 def aob_kernel_times():
     """{"sectors", "layout", "pcm": ms} of this thread's last call"""
-    lib = load_library()
-    names = (ctypes.c_char_p * 3)()
-    ms = (ctypes.c_float * 3)()
-    k = lib.atg_aob_kernel_times(names, ms, 3)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    return _thread_times(load_library().atg_aob_kernel_times, 3)
 
 
 # ------------------------------------------------- MLP titles (mlp_decode.hip)
-def _mlp_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_mlp_last_error().decode("utf-8", "replace"))
-
-
 def mlp_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_units=False):
     """every pass that writes no PCM over AOB bytes in device memory
     (atg_mlp_scan_device): ([MlpResult], total_samples) with sample_offset
@@ -2476,14 +2458,14 @@ def mlp_scan_device(d_bytes, bytes_cap, titles, fmt=PCM_S32, want_units=False):
     arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
     res = (MlpResult * max(1, n))()
     total = ctypes.c_uint64()
-    _mlp_check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
-                                            ctypes.byref(total), None, 0, None))
+    _check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                        ctypes.byref(total), None, 0, None), "mlp")
     if not want_units:
         return list(res[:n]), total.value
     n_units = sum(res[i].access_units for i in range(n))
     units = (MlpUnit * max(1, n_units))()
-    _mlp_check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
-                                            ctypes.byref(total), units, n_units, None))
+    _check(lib, lib.atg_mlp_scan_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n, fmt, res,
+                                        ctypes.byref(total), units, n_units, None), "mlp")
     return list(res[:n]), total.value, list(units[:n_units])
 
 
@@ -2493,9 +2475,9 @@ def mlp_decode_device(d_bytes, bytes_cap, titles, d_pcm, fmt, pcm_cap_samples):
     lib = load_library()
     arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
     res = (MlpResult * max(1, n))()
-    _mlp_check(lib, lib.atg_mlp_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
-                                              ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
-                                              None))
+    _check(lib, lib.atg_mlp_decode_device(ctypes.c_void_p(d_bytes), bytes_cap, arr, n,
+                                          ctypes.c_void_p(d_pcm), fmt, pcm_cap_samples, res,
+                                          None), "mlp")
     return list(res[:n])
 
 
@@ -2507,19 +2489,15 @@ def mlp_decode_host(data, titles, cap_samples, fmt=PCM_S32, device=None):
     arr, n = titles if isinstance(titles, tuple) else aob_titles(titles)
     res = (MlpResult * max(1, n))()
     out = np.zeros(max(1, cap_samples), dtype=np.int16 if fmt == PCM_S16 else np.int32)
-    _mlp_check(lib, lib.atg_mlp_decode_host(
+    _check(lib, lib.atg_mlp_decode_host(
         default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
-        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap_samples, res))
+        a.nbytes, arr, n, out.ctypes.data_as(ctypes.c_void_p), fmt, cap_samples, res), "mlp")
     return list(res[:n]), out
 
 
 def mlp_kernel_times():
     """{pass name: ms} of this thread's last MLP call"""
-    lib = load_library()
-    names = (ctypes.c_char_p * 10)()
-    ms = (ctypes.c_float * 10)()
-    k = lib.atg_mlp_kernel_times(names, ms, 10)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    return _thread_times(load_library().atg_mlp_kernel_times, 10)
 
 
 # ------------------------------------------------- PCM comparison (pcm_compare.hip)
@@ -2540,8 +2518,7 @@ def _pc_call(call, pairs):
     arr = (PcmPair * max(1, n))(*pairs)
     res = (PcmCmpResult * max(1, n))()
     st = call(lib, arr, n, res)
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_pcm_compare_last_error().decode("utf-8", "replace"))
+    _check(lib, st, "pcm_compare")
     return [res[i] for i in range(n)]
 
 
@@ -2570,11 +2547,7 @@ def pcm_compare_tile_frames():
 
 def pcm_compare_kernel_times():
     """{"compare": ms, "probe": ms} of this thread's last compare or search"""
-    lib = load_library()
-    names = (ctypes.c_char_p * 2)()
-    ms = (ctypes.c_float * 2)()
-    k = lib.atg_pcm_compare_kernel_times(names, ms, 2)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    return _thread_times(load_library().atg_pcm_compare_kernel_times, 2)
 
 
 # ------------------------------------------------- converter chain (pcm_chain.hip)
@@ -2596,19 +2569,14 @@ def pcm_chain_row(src, in_channels, out_channels, in_bps, out_bps, out_offset,
     return r
 
 
-def _chain_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_pcm_chain_last_error().decode("utf-8", "replace"))
-
-
 def pcm_chain_device(rows, d_out, out_fmt, out_cap_samples, d_dither=None, dither_bytes=0):
     """every PcmChainRow converted in one launch, device memory in and out
     (atg_pcm_chain_device)"""
     lib = load_library()
     arr = (PcmChainRow * max(1, len(rows)))(*rows)
-    _chain_check(lib, lib.atg_pcm_chain_device(
+    _check(lib, lib.atg_pcm_chain_device(
         arr, len(rows), ctypes.c_void_p(d_out), out_fmt, out_cap_samples,
-        ctypes.c_void_p(d_dither) if d_dither else None, dither_bytes, None))
+        ctypes.c_void_p(d_dither) if d_dither else None, dither_bytes, None), "pcm_chain")
 
 
 def pcm_chain_host(rows, out, dither=b"", device=None):
@@ -2618,11 +2586,11 @@ def pcm_chain_host(rows, out, dither=b"", device=None):
     lib = load_library()
     arr = (PcmChainRow * max(1, len(rows)))(*rows)
     d = np.frombuffer(bytes(dither), dtype=np.uint8) if len(dither) else None
-    _chain_check(lib, lib.atg_pcm_chain_host(
+    _check(lib, lib.atg_pcm_chain_host(
         default_device() if device is None else device, arr, len(rows),
         out.ctypes.data_as(ctypes.c_void_p), PCM_S16 if out.dtype == np.int16 else PCM_S32,
         len(out), d.ctypes.data_as(ctypes.c_void_p) if d is not None else None,
-        0 if d is None else len(d)))
+        0 if d is None else len(d)), "pcm_chain")
     return out
 
 
@@ -2638,11 +2606,7 @@ def pcm_chain_tile_frames(in_channels, out_channels):
 
 def pcm_chain_kernel_times():
     """{"chain": ms} of this thread's last launch"""
-    lib = load_library()
-    names = (ctypes.c_char_p * 1)()
-    ms = (ctypes.c_float * 1)()
-    k = lib.atg_pcm_chain_kernel_times(names, ms, 1)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    return _thread_times(load_library().atg_pcm_chain_kernel_times, 1)
 
 
 def aiff_read_info(data):
@@ -2670,17 +2634,11 @@ def apply_gain(pcm, channels, bits_per_sample, multiplier, chunk_frames, dither,
         default_device() if device is None else device, a.ctypes.data_as(ctypes.c_void_p),
         out.ctypes.data_as(ctypes.c_void_p), len(a) // channels, channels, bits_per_sample,
         multiplier, chunk_frames, d.ctypes.data_as(ctypes.c_void_p), len(d), dither_bit0)
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_pcm_convert_last_error().decode("utf-8", "replace"))
+    _check(lib, st, "pcm_convert")
     return out[:len(a)]
 
 
 # ------------------------------------------------------------------ resampler
-def _rs_check(lib, st):
-    if st != ATG_OK:
-        raise ATGError(st, lib.atg_resample_last_error().decode("utf-8", "replace"))
-
-
 def resample_output_frames(in_frames, channels, in_rate, out_rate):
     return int(load_library().atg_resample_output_frames(in_frames, channels, in_rate, out_rate))
 
@@ -2714,10 +2672,10 @@ def resample_device(d_in, d_out, out_cap_samples, tracks, channels, bits_per_sam
     arr = resample_tracks(tracks, channels)
     offs = np.zeros(max(1, n), dtype=np.uint64)
     cnt = np.zeros(max(1, n), dtype=np.uint64)
-    _rs_check(lib, lib.atg_resample_device(
+    _check(lib, lib.atg_resample_device(
         arr, n, channels, bits_per_sample, ctypes.c_void_p(d_in), ctypes.c_void_p(d_out),
         out_cap_samples, offs.ctypes.data_as(ctypes.c_void_p),
-        cnt.ctypes.data_as(ctypes.c_void_p), stream))
+        cnt.ctypes.data_as(ctypes.c_void_p), stream), "resample")
     return offs[:n], cnt[:n]
 
 
@@ -2736,11 +2694,11 @@ def resample_host(pcm, tracks, channels, bits_per_sample, device=None):
     out = np.empty(max(1, total * channels), dtype=np.int32)
     offs = np.zeros(max(1, n), dtype=np.uint64)
     cnt = np.zeros(max(1, n), dtype=np.uint64)
-    _rs_check(lib, lib.atg_resample_host(
+    _check(lib, lib.atg_resample_host(
         default_device() if device is None else device, resample_tracks(tracks, channels), n,
         channels, bits_per_sample, a.ctypes.data_as(ctypes.c_void_p), len(a),
         out.ctypes.data_as(ctypes.c_void_p), total * channels,
-        offs.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        offs.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)), "resample")
     return out[:total * channels], offs[:n], cnt[:n]
 
 
@@ -2762,8 +2720,5 @@ def resample_read_sizes(in_frames, channels, in_rate, out_rate, reads):
 
 
 def resample_kernel_times():
-    lib = load_library()
-    names = (ctypes.c_char_p * 4)()
-    ms = (ctypes.c_float * 4)()
-    k = lib.atg_resample_kernel_times(names, ms, 4)
-    return {names[i].decode(): float(ms[i]) for i in range(k)}
+    """{"rs_positions", "rs_filter": ms} of this thread's last resample"""
+    return _thread_times(load_library().atg_resample_kernel_times, 4)

@@ -35,7 +35,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -67,11 +66,9 @@ struct ArTrack {
 };
 
 struct ArCtx {
-    std::mutex mu;
     DevBuf tracks, tiles, sums, sweep;
 };
-constexpr int kMaxDevices = 64;
-ArCtx g_ctxs[kMaxDevices];
+DeviceContexts<ArCtx> g_ctxs;
 
 template <int FMT> struct Pcm;
 template <> struct Pcm<ATG_PCM_S32> {
@@ -384,20 +381,10 @@ atg_status atg_accuraterip_device(const void *d_pcm, int format, const atg_ar_tr
     if (!n)
         return ATG_OK;
     hipStream_t s = (hipStream_t)stream;
-    // run where the PCM is: a sharded caller's thread may sit on another device
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_pcm) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-        dev = attr.device;
-        AHIP(hipSetDevice(dev));
-    } else {
-        (void)hipGetLastError();
-        AHIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_ar_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    ArCtx &c = g_ctxs[dev];
-    std::lock_guard<std::mutex> lock(c.mu);
+    DeviceContexts<ArCtx>::Held held; // where the PCM is
+    if ((st = g_ctxs.hold(d_pcm, g_ar_err, held)) != ATG_OK)
+        return st;
+    ArCtx &c = *held;
     std::vector<ArTrack> tr(n);
     uint64_t n_tiles = 0;
     for (uint32_t t = 0; t < n; ++t) {
@@ -449,23 +436,15 @@ atg_status atg_accuraterip_host(int device, const void *pcm, int format,
             return g_ar_err.fail(ATG_ERR_INVALID, "hi_frame beyond the PCM buffer");
     if (!n)
         return ATG_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return g_ar_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev)
-        return g_ar_err.fail(ATG_ERR_INVALID, "device index out of range");
-    AHIP(hipSetDevice(device));
+    if ((st = use_device(device, g_ar_err)) != ATG_OK)
+        return st;
     const size_t bytes = (size_t)pcm_frames_total * (format == ATG_PCM_S32 ? 8 : 4);
-    void *d = nullptr;
-    AHIP(hipMalloc(&d, std::max<size_t>(bytes, 16)));
-    hipError_t e = bytes ? hipMemcpy(d, pcm, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return g_ar_err.fail(ATG_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    st = atg_accuraterip_device(d, format, tracks, n, max_offset, results, offset_v1, nullptr);
-    (void)hipFree(d);
-    return st;
+    DevTemp d;
+    ATG_HIP_TRY(g_ar_err, d.alloc(std::max<size_t>(bytes, 16)),
+                "hipMalloc(&d, std::max<size_t>(bytes, 16))");
+    if (bytes)
+        ATG_HIP_TRY(g_ar_err, hipMemcpy(d.p, pcm, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    return atg_accuraterip_device(d.p, format, tracks, n, max_offset, results, offset_v1, nullptr);
 }
 
 uint32_t atg_accuraterip_tile_frames(void) { return kTile; }

@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -44,8 +43,7 @@ constexpr uint32_t kMaxBlocks = 4096;
 constexpr int kStages = 3;
 const char *const kStageNames[kStages] = {"sectors", "layout", "pcm"};
 
-thread_local float g_aob_ms[kStages] = {};
-thread_local int g_aob_n = 0;
+thread_local StageTimes<kStages> g_aob_times;
 
 // a title with PCM to write: its tiles are [tile0, next run's tile0)
 struct AobRun {
@@ -170,12 +168,10 @@ __global__ __launch_bounds__(kAobBlock) void k_aob_pcm(const uint8_t *__restrict
 
 // per device: the tables and the events that time the passes
 struct AobCtx {
-    std::mutex mu;
     DevBuf titles, sectors, prefix, results, runs;
     hipEvent_t ev[kStages + 1] = {};
 };
-constexpr int kMaxDevices = 64;
-AobCtx g_ctxs[kMaxDevices];
+DeviceContexts<AobCtx> g_ctxs;
 
 atg_status check_args(bool aligned, const void *bytes, uint64_t bytes_cap,
                       const atg_aob_title *titles, uint32_t n, int format,
@@ -183,24 +179,6 @@ atg_status check_args(bool aligned, const void *bytes, uint64_t bytes_cap,
 {
     return aob_check_args(g_aob_err, aligned, bytes, bytes_cap, titles, n, format, results,
                           n_sectors);
-}
-
-atg_status pick_device(const void *d_ptr, AobCtx **ctx)
-{
-    // run where the buffers are: a sharded caller's thread may sit elsewhere
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_ptr) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-        dev = attr.device;
-        AHIP(hipSetDevice(dev));
-    } else {
-        (void)hipGetLastError();
-        AHIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_aob_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    *ctx = &g_ctxs[dev];
-    return ATG_OK;
 }
 
 // sample offsets for `format`, each title on a 16-byte boundary
@@ -215,14 +193,12 @@ uint64_t lay_out(atg_aob_result *results, uint32_t n, int format)
     return pos;
 }
 
-// the sector and layout passes; the caller holds c.mu.  Records ev[0..2].
+// the sector and layout passes on a held context.  Records ev[0..2].
 atg_status scan_locked(AobCtx &c, const void *d_bytes, const atg_aob_title *titles, uint32_t n,
                        uint64_t n_sectors, int format, atg_aob_result *results,
                        uint64_t *total_samples, hipStream_t s)
 {
-    for (hipEvent_t &e : c.ev)
-        if (!e)
-            AHIP(hipEventCreate(&e));
+    ATG_HIP_TRY(g_aob_err, ensure_events(c.ev), "hipEventCreate(&e)");
     std::vector<AobTitle> tab(n);
     uint32_t sec0 = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -261,9 +237,9 @@ atg_status scan_locked(AobCtx &c, const void *d_bytes, const atg_aob_title *titl
 void take_times(AobCtx &c, int stages)
 {
     for (int k = 0; k < stages; ++k)
-        if (hipEventElapsedTime(&g_aob_ms[k], c.ev[k], c.ev[k + 1]) != hipSuccess)
-            g_aob_ms[k] = 0.f;
-    g_aob_n = stages;
+        if (hipEventElapsedTime(&g_aob_times.ms[k], c.ev[k], c.ev[k + 1]) != hipSuccess)
+            g_aob_times.ms[k] = 0.f;
+    g_aob_times.n = stages;
 }
 
 } // namespace
@@ -276,14 +252,7 @@ uint32_t atg_aob_tile_frames(void) { return 2 * kAobTileChunks; }
 
 int atg_aob_kernel_times(const char **names, float *ms, int cap)
 {
-    const int k = std::min(cap < 0 ? 0 : cap, g_aob_n);
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kStageNames[i];
-        if (ms)
-            ms[i] = g_aob_ms[i];
-    }
-    return k;
+    return copy_times(kStageNames, g_aob_times.ms, g_aob_times.n, names, ms, cap);
 }
 
 atg_status atg_aob_scan_device(const void *d_bytes, uint64_t bytes_cap,
@@ -303,10 +272,9 @@ atg_status atg_aob_scan_device(const void *d_bytes, uint64_t bytes_cap,
         *total_samples = 0;
     if (!n_titles)
         return ATG_OK;
-    AobCtx *c = nullptr;
-    if ((st = pick_device(d_bytes, &c)) != ATG_OK)
+    DeviceContexts<AobCtx>::Held c;
+    if ((st = g_ctxs.hold(d_bytes, g_aob_err, c)) != ATG_OK)
         return st;
-    std::lock_guard<std::mutex> lock(c->mu);
     hipStream_t s = (hipStream_t)stream;
     st = scan_locked(*c, d_bytes, titles, n_titles, n_sectors, (int)format, results,
                      total_samples, s);
@@ -335,10 +303,9 @@ atg_status atg_aob_decode_device(const void *d_bytes, uint64_t bytes_cap,
         return g_aob_err.fail(ATG_ERR_INVALID, "d_pcm must be 16-byte aligned");
     if (!n_titles)
         return ATG_OK;
-    AobCtx *c = nullptr;
-    if ((st = pick_device(d_bytes, &c)) != ATG_OK)
+    DeviceContexts<AobCtx>::Held c;
+    if ((st = g_ctxs.hold(d_bytes, g_aob_err, c)) != ATG_OK)
         return st;
-    std::lock_guard<std::mutex> lock(c->mu);
     hipStream_t s = (hipStream_t)stream;
     uint64_t total = 0;
     st = scan_locked(*c, d_bytes, titles, n_titles, n_sectors, (int)format, results, &total, s);
@@ -385,9 +352,9 @@ atg_status atg_aob_decode_device(const void *d_bytes, uint64_t bytes_cap,
     }
     AHIP(hipEventRecord(c->ev[3], s));
     AHIP(hipStreamSynchronize(s));
-    if (hipEventElapsedTime(&g_aob_ms[2], c->ev[2], c->ev[3]) != hipSuccess)
-        g_aob_ms[2] = 0.f;
-    g_aob_n = 3;
+    if (hipEventElapsedTime(&g_aob_times.ms[2], c->ev[2], c->ev[3]) != hipSuccess)
+        g_aob_times.ms[2] = 0.f;
+    g_aob_times.n = 3;
     return ATG_OK;
 }
 
@@ -405,34 +372,27 @@ atg_status atg_aob_decode_host(int device, const void *bytes, uint64_t n_bytes,
         return g_aob_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (!n_titles)
         return ATG_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return g_aob_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev)
-        return g_aob_err.fail(ATG_ERR_INVALID, "device index out of range");
-    AHIP(hipSetDevice(device));
+    if ((st = use_device(device, g_aob_err)) != ATG_OK)
+        return st;
     const uint64_t ssize = format == ATG_PCM_S16 ? 2 : 4;
-    void *d_bytes = nullptr, *d_pcm = nullptr;
-    AHIP(hipMalloc(&d_bytes, std::max<uint64_t>(n_bytes, 16)));
-    hipError_t e = hipMalloc(&d_pcm, std::max<uint64_t>(pcm_cap_samples * ssize, 16));
+    DevTemp d_bytes, d_pcm;
+    ATG_HIP_TRY(g_aob_err, d_bytes.alloc(std::max<uint64_t>(n_bytes, 16)),
+                "hipMalloc(&d_bytes, std::max<uint64_t>(n_bytes, 16))");
+    hipError_t e = d_pcm.alloc(std::max<uint64_t>(pcm_cap_samples * ssize, 16));
     if (e == hipSuccess)
-        e = hipMemcpy(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice);
+        e = hipMemcpy(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        st = atg_aob_decode_device(d_bytes, n_bytes, titles, n_titles, d_pcm, format,
+        st = atg_aob_decode_device(d_bytes.p, n_bytes, titles, n_titles, d_pcm.p, format,
                                    pcm_cap_samples, results, nullptr);
         // only the titles' own sample ranges are written
         for (uint32_t i = 0; st == ATG_OK && e == hipSuccess && i < n_titles; ++i) {
             const uint64_t n = results[i].good_frames * results[i].channels;
             if (n)
                 e = hipMemcpy((char *)pcm + results[i].sample_offset * ssize,
-                              (const char *)d_pcm + results[i].sample_offset * ssize, n * ssize,
-                              hipMemcpyDeviceToHost);
+                              (const char *)d_pcm.p + results[i].sample_offset * ssize,
+                              n * ssize, hipMemcpyDeviceToHost);
         }
     }
-    if (d_bytes)
-        (void)hipFree(d_bytes);
-    if (d_pcm)
-        (void)hipFree(d_pcm);
     if (e != hipSuccess)
         return g_aob_err.fail(ATG_ERR_DEVICE, std::string("staging: ") + hipGetErrorString(e));
     return st;

@@ -1,7 +1,9 @@
 // host_common.h — the host-side frame every component of libatgpu shares:
 // the growable device buffer, the per-component error slot with its
-// "try a HIP call" macro, and the base of the single-stream codec handles.
-// Host code only; nothing here is seen by a kernel.
+// "try a HIP call" macro, the stage times, the base of the single-stream
+// codec handles, and what a component without a handle is made of: its
+// per-device contexts, the device it runs on and the staging of its *_host
+// entries.  Host code only; nothing here is seen by a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +65,117 @@ struct ErrSlot {
                                std::string(text ": ") + hipGetErrorString(e_));          \
     } while (0)
 
+// The body of every *_kernel_times: the first min(cap, n) names and values.
+inline int copy_times(const char *const *stage, const float *times, int n, const char **names,
+                      float *ms, int cap)
+{
+    const int k = std::max(0, std::min(cap, n));
+    for (int i = 0; i < k; ++i) {
+        if (names)
+            names[i] = stage[i];
+        if (ms)
+            ms[i] = times[i];
+    }
+    return k;
+}
+
+// The stage times of a component without a handle: one thread_local per
+// component, so a thread reads its own last call.  n counts the valid
+// entries, 0 before the thread's first call.
+template <int N> struct StageTimes {
+    float ms[N] = {};
+    int n = 0;
+};
+
+// Create the events of an array that are still null.
+template <int N> hipError_t ensure_events(hipEvent_t (&ev)[N])
+{
+    hipError_t err = hipSuccess;
+    for (hipEvent_t &e : ev)
+        if (!e && err == hipSuccess)
+            err = hipEventCreate(&e);
+    return err;
+}
+
+// The head of every entry that takes a device index: the index checked, the
+// device made current.
+inline atg_status use_device(int device, ErrSlot &slot)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return slot.fail(ATG_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= n)
+        return slot.fail(ATG_ERR_INVALID, "device index out of range");
+    ATG_HIP_TRY(slot, hipSetDevice(device), "hipSetDevice(device)");
+    return ATG_OK;
+}
+
+// A device allocation of one call, freed at scope exit: the staging buffers
+// of the *_host entries.  Always a local, so DevBuf's reason to have no
+// destructor does not reach it.  alloc() hands back HIP's error and the
+// caller words it, each component in its own status and text.
+struct DevTemp {
+    void *p = nullptr;
+    DevTemp() = default;
+    DevTemp(const DevTemp &) = delete;
+    DevTemp &operator=(const DevTemp &) = delete;
+    ~DevTemp()
+    {
+        if (p)
+            (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+
+// The static per-device state of a component without a handle: one Ctx per
+// device, each behind a mutex, and the only way to one is hold(), which
+// returns it locked.  Ctx keeps DevBufs and events and has no destructor,
+// like DevBuf and for its reason.
+constexpr int kMaxDevices = 64;
+
+template <class Ctx> class DeviceContexts {
+    struct Slot {
+        std::mutex mu;
+        Ctx ctx;
+    };
+    Slot slots_[kMaxDevices];
+
+  public:
+    // a context for as long as this lives
+    class Held {
+        friend class DeviceContexts;
+        std::unique_lock<std::mutex> lock_;
+        Ctx *c_ = nullptr;
+
+      public:
+        Ctx &operator*() const { return *c_; }
+        Ctx *operator->() const { return c_; }
+    };
+
+    // Run where the buffers are: a sharded caller's thread may sit elsewhere.
+    // The device that holds d_ptr is made current; for NULL or a pointer HIP
+    // does not know, the current device stands.  Then that device's context,
+    // locked, into `out`.
+    atg_status hold(const void *d_ptr, ErrSlot &slot, Held &out)
+    {
+        int dev = 0;
+        hipPointerAttribute_t attr;
+        if (d_ptr && hipPointerGetAttributes(&attr, d_ptr) == hipSuccess &&
+            attr.type == hipMemoryTypeDevice) {
+            dev = attr.device;
+            ATG_HIP_TRY(slot, hipSetDevice(dev), "hipSetDevice(dev)");
+        } else {
+            (void)hipGetLastError();
+            ATG_HIP_TRY(slot, hipGetDevice(&dev), "hipGetDevice(&dev)");
+        }
+        if (dev < 0 || dev >= kMaxDevices)
+            return slot.fail(ATG_ERR_UNSUPPORTED, "device index too large");
+        out.lock_ = std::unique_lock<std::mutex>(slots_[dev].mu);
+        out.c_ = &slots_[dev].ctx;
+        return ATG_OK;
+    }
+};
+
 // Base of the codec handles that run one batch at a time on one non-blocking
 // stream and time its N-1 stages with N events: times[k] is ev[k] -> ev[k+1],
 // times[N-1] the whole run.  The codec's struct derives from this and adds
@@ -87,16 +200,7 @@ template <int N> struct StageHandle {
     // the body of *_kernel_times
     int report(const char *const (&stage)[N], const char **names, float *ms, int cap) const
     {
-        if (!have_times)
-            return 0;
-        const int k = cap < N ? cap : N;
-        for (int i = 0; i < k; ++i) {
-            if (names)
-                names[i] = stage[i];
-            if (ms)
-                ms[i] = times[i];
-        }
-        return k;
+        return have_times ? copy_times(stage, times, N, names, ms, cap) : 0;
     }
 
     // Drain the stream, free the codec's buffers, then the events and the
@@ -124,12 +228,9 @@ template <class H> atg_status open_handle(int device, H **out, ErrSlot &slot, co
     if (!out)
         return slot.fail(ATG_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return slot.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return slot.fail(ATG_ERR_INVALID, "device index out of range");
-    ATG_HIP_TRY(slot, hipSetDevice(device), "hipSetDevice(device)");
+    const atg_status st = use_device(device, slot);
+    if (st != ATG_OK)
+        return st;
     H *h = new H();
     h->device = device;
     hipError_t err = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);

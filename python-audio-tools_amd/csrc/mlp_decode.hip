@@ -34,7 +34,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -55,8 +54,7 @@ constexpr uint32_t kMaxBlocks = 4096;
 constexpr int kStages = 10;
 const char *const kStageNames[kStages] = {"sectors", "layout", "gather", "walk",   "check",
                                           "parse",   "resolve", "store", "filter", "output"};
-thread_local float g_mlp_ms[kStages] = {};
-thread_local int g_mlp_n = 0;
+thread_local StageTimes<kStages> g_mlp_times;
 
 constexpr uint32_t kMlpWindow = 4096; // bytes of stream per LDS window of the walk
 constexpr uint32_t kMlpTile = 256;    // frames per LDS tile of the filter pass
@@ -515,31 +513,11 @@ __global__ __launch_bounds__(kAobBlock) void k_mlp_output(
 
 // per device: the tables and the events that time the passes
 struct MlpCtx {
-    std::mutex mu;
     DevBuf at, mt, sectors, prefix, stream, units, chk, sizes, uframe0, ublk0, urec, res, byp,
         blocks;
     hipEvent_t ev[14] = {};
 };
-constexpr int kMaxDevices = 64;
-MlpCtx g_ctxs[kMaxDevices];
-
-atg_status pick_device(const void *d_ptr, MlpCtx **ctx)
-{
-    // run where the buffers are: a sharded caller's thread may sit elsewhere
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_ptr) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-        dev = attr.device;
-        MHIP(hipSetDevice(dev));
-    } else {
-        (void)hipGetLastError();
-        MHIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_mlp_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    *ctx = &g_ctxs[dev];
-    return ATG_OK;
-}
+DeviceContexts<MlpCtx> g_ctxs;
 
 uint32_t grid_for(uint64_t items, uint32_t block)
 {
@@ -547,16 +525,14 @@ uint32_t grid_for(uint64_t items, uint32_t block)
                                         0x7FFFFFFFull);
 }
 
-// Every pass; the caller holds c.mu.  d_pcm == NULL: stop after resolve (the
+// Every pass, on a held context.  d_pcm == NULL: stop after resolve (the
 // scan).  units (host, may be NULL) receives the unit table.
 atg_status run_locked(MlpCtx &c, const void *d_bytes, const atg_aob_title *titles, uint32_t n,
                       uint64_t n_sectors, int format, atg_mlp_result *results,
                       uint64_t *total_samples, atg_mlp_unit *units, uint64_t units_cap,
                       bool decode, void *d_pcm, uint64_t pcm_cap, hipStream_t s)
 {
-    for (hipEvent_t &e : c.ev)
-        if (!e)
-            MHIP(hipEventCreate(&e));
+    ATG_HIP_TRY(g_mlp_err, ensure_events(c.ev), "hipEventCreate(&e)");
     std::vector<AobTitle> at(n);
     std::vector<MlpTitle> mt(n);
     uint32_t sec0 = 0;
@@ -687,14 +663,14 @@ atg_status run_locked(MlpCtx &c, const void *d_bytes, const atg_aob_title *title
         const int pairs[kStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4},  {6, 7},
                                        {7, 8}, {8, 9}, {10, 11}, {11, 12}, {12, 13}};
         for (int k = 0; k < kStages; ++k) {
-            g_mlp_ms[k] = 0.f;
+            float &ms = g_mlp_times.ms[k] = 0.f;
             if (k < upto)
-                (void)hipEventElapsedTime(&g_mlp_ms[k], c.ev[pairs[k][0]], c.ev[pairs[k][1]]);
+                (void)hipEventElapsedTime(&ms, c.ev[pairs[k][0]], c.ev[pairs[k][1]]);
         }
         float again = 0.f; // the storing walk
         if (hipEventElapsedTime(&again, c.ev[5], c.ev[6]) == hipSuccess)
-            g_mlp_ms[3] += again;
-        g_mlp_n = upto;
+            g_mlp_times.ms[3] += again;
+        g_mlp_times.n = upto;
     };
     times(7);
     if (units) {
@@ -757,14 +733,7 @@ const char *atg_mlp_last_error(void) { return g_mlp_err.msg.c_str(); }
 
 int atg_mlp_kernel_times(const char **names, float *ms, int cap)
 {
-    const int k = std::min(cap < 0 ? 0 : cap, g_mlp_n);
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kStageNames[i];
-        if (ms)
-            ms[i] = g_mlp_ms[i];
-    }
-    return k;
+    return copy_times(kStageNames, g_mlp_times.ms, g_mlp_times.n, names, ms, cap);
 }
 
 atg_status atg_mlp_scan_device(const void *d_bytes, uint64_t bytes_cap,
@@ -782,10 +751,9 @@ atg_status atg_mlp_scan_device(const void *d_bytes, uint64_t bytes_cap,
         *total_samples = 0;
     if (!n_titles)
         return ATG_OK;
-    MlpCtx *c = nullptr;
-    if ((st = pick_device(d_bytes, &c)) != ATG_OK)
+    DeviceContexts<MlpCtx>::Held c;
+    if ((st = g_ctxs.hold(d_bytes, g_mlp_err, c)) != ATG_OK)
         return st;
-    std::lock_guard<std::mutex> lock(c->mu);
     return run_locked(*c, d_bytes, titles, n_titles, n_sectors, (int)format, results,
                       total_samples, units, units_cap, false, nullptr, 0, (hipStream_t)stream);
 }
@@ -806,10 +774,9 @@ atg_status atg_mlp_decode_device(const void *d_bytes, uint64_t bytes_cap,
         return g_mlp_err.fail(ATG_ERR_INVALID, "d_pcm must be 16-byte aligned");
     if (!n_titles)
         return ATG_OK;
-    MlpCtx *c = nullptr;
-    if ((st = pick_device(d_bytes, &c)) != ATG_OK)
+    DeviceContexts<MlpCtx>::Held c;
+    if ((st = g_ctxs.hold(d_bytes, g_mlp_err, c)) != ATG_OK)
         return st;
-    std::lock_guard<std::mutex> lock(c->mu);
     return run_locked(*c, d_bytes, titles, n_titles, n_sectors, (int)format, results, nullptr,
                       nullptr, 0, true, d_pcm, pcm_cap_samples, (hipStream_t)stream);
 }
@@ -828,34 +795,27 @@ atg_status atg_mlp_decode_host(int device, const void *bytes, uint64_t n_bytes,
         return g_mlp_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (!n_titles)
         return ATG_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return g_mlp_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev)
-        return g_mlp_err.fail(ATG_ERR_INVALID, "device index out of range");
-    MHIP(hipSetDevice(device));
+    if ((st = use_device(device, g_mlp_err)) != ATG_OK)
+        return st;
     const uint64_t ssize = format == ATG_PCM_S16 ? 2 : 4;
-    void *d_bytes = nullptr, *d_pcm = nullptr;
-    MHIP(hipMalloc(&d_bytes, std::max<uint64_t>(n_bytes, 16)));
-    hipError_t e = hipMalloc(&d_pcm, std::max<uint64_t>(pcm_cap_samples * ssize, 16));
+    DevTemp d_bytes, d_pcm;
+    ATG_HIP_TRY(g_mlp_err, d_bytes.alloc(std::max<uint64_t>(n_bytes, 16)),
+                "hipMalloc(&d_bytes, std::max<uint64_t>(n_bytes, 16))");
+    hipError_t e = d_pcm.alloc(std::max<uint64_t>(pcm_cap_samples * ssize, 16));
     if (e == hipSuccess)
-        e = hipMemcpy(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice);
+        e = hipMemcpy(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        st = atg_mlp_decode_device(d_bytes, n_bytes, titles, n_titles, d_pcm, format,
+        st = atg_mlp_decode_device(d_bytes.p, n_bytes, titles, n_titles, d_pcm.p, format,
                                    pcm_cap_samples, results, nullptr);
         // only the titles' own sample ranges are written
         for (uint32_t i = 0; st == ATG_OK && e == hipSuccess && i < n_titles; ++i) {
             const uint64_t n = results[i].good_frames * results[i].channels;
             if (n)
                 e = hipMemcpy((char *)pcm + results[i].sample_offset * ssize,
-                              (const char *)d_pcm + results[i].sample_offset * ssize, n * ssize,
-                              hipMemcpyDeviceToHost);
+                              (const char *)d_pcm.p + results[i].sample_offset * ssize,
+                              n * ssize, hipMemcpyDeviceToHost);
         }
     }
-    if (d_bytes)
-        (void)hipFree(d_bytes);
-    if (d_pcm)
-        (void)hipFree(d_pcm);
     if (e != hipSuccess)
         return g_mlp_err.fail(ATG_ERR_DEVICE, std::string("staging: ") + hipGetErrorString(e));
     return st;

@@ -27,7 +27,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -44,17 +43,15 @@ thread_local ErrSlot g_pb_err;
 
 constexpr uint32_t kMaxBlocks = 4096;
 
-thread_local float g_pb_ms = 0.f;
+thread_local StageTimes<1> g_pb_times; // one entry, named after the last call
 thread_local const char *g_pb_name = nullptr;
 
 // per device: the run table and the two events that time a launch
 struct PbCtx {
-    std::mutex mu;
     DevBuf runs;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
-constexpr int kMaxDevices = 64;
-PbCtx g_ctxs[kMaxDevices];
+DeviceContexts<PbCtx> g_ctxs;
 
 template <int B, bool BE, bool SGN, typename T>
 __global__ __launch_bounds__(kPbBlock) void k_pcm_unpack(const uint8_t *__restrict__ bytes,
@@ -192,23 +189,11 @@ atg_status run_device(bool pack, const void *d_bytes, uint64_t bytes_cap, atg_pc
     if (tab.empty())
         return ATG_OK;
     hipStream_t s = (hipStream_t)stream;
-    // run where the buffers are: a sharded caller's thread may sit elsewhere
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_pcm) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-        dev = attr.device;
-        PHIP(hipSetDevice(dev));
-    } else {
-        (void)hipGetLastError();
-        PHIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_pb_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    PbCtx &c = g_ctxs[dev];
-    std::lock_guard<std::mutex> lock(c.mu);
-    for (hipEvent_t &e : c.ev)
-        if (!e)
-            PHIP(hipEventCreate(&e));
+    DeviceContexts<PbCtx>::Held held;
+    if ((st = g_ctxs.hold(d_pcm, g_pb_err, held)) != ATG_OK)
+        return st;
+    PbCtx &c = *held;
+    ATG_HIP_TRY(g_pb_err, ensure_events(c.ev), "hipEventCreate(&e)");
     PHIP(c.runs.ensure(sizeof(PbRun) * tab.size()));
     PHIP(hipMemcpyAsync(c.runs.p, tab.data(), sizeof(PbRun) * tab.size(), hipMemcpyHostToDevice, s));
     const Launch l = {pack,
@@ -225,7 +210,7 @@ atg_status run_device(bool pack, const void *d_bytes, uint64_t bytes_cap, atg_pc
     PHIP(hipStreamSynchronize(s));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) {
-        g_pb_ms = ms;
+        g_pb_times = {{ms}, 1};
         g_pb_name = pack ? "pack" : "unpack";
     }
     return ATG_OK;
@@ -265,20 +250,17 @@ atg_status run_host(bool pack, int device, const void *bytes, uint64_t n_bytes, 
         any = any || runs[i].samples;
     if (!any)
         return ATG_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return g_pb_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev)
-        return g_pb_err.fail(ATG_ERR_INVALID, "device index out of range");
-    PHIP(hipSetDevice(device));
+    if ((st = use_device(device, g_pb_err)) != ATG_OK)
+        return st;
     const uint64_t ssize = format == ATG_PCM_S16 ? 2 : 4;
     const uint64_t cap16 = (n_bytes + 15) & ~(uint64_t)15;
-    void *d_bytes = nullptr, *d_pcm = nullptr;
-    PHIP(hipMalloc(&d_bytes, std::max<uint64_t>(cap16, 16)));
-    hipError_t e = hipMalloc(&d_pcm, std::max<uint64_t>(pcm_cap * ssize, 16));
+    DevTemp d_bytes, d_pcm;
+    ATG_HIP_TRY(g_pb_err, d_bytes.alloc(std::max<uint64_t>(cap16, 16)),
+                "hipMalloc(&d_bytes, std::max<uint64_t>(cap16, 16))");
+    hipError_t e = d_pcm.alloc(std::max<uint64_t>(pcm_cap * ssize, 16));
     // in: the runs' ranges of the source side; out: those of the other side
     const void *src = pack ? pcm : bytes;
-    void *d_src = pack ? d_pcm : d_bytes, *d_dst = pack ? d_bytes : d_pcm;
+    void *d_src = pack ? d_pcm.p : d_bytes.p, *d_dst = pack ? d_bytes.p : d_pcm.p;
     void *dst = const_cast<void *>(pack ? bytes : pcm);
     if (e == hipSuccess)
         for (const auto &r : covered(runs, n, !pack, pack ? ssize : lay.bytes_per_sample))
@@ -286,9 +268,9 @@ atg_status run_host(bool pack, int device, const void *bytes, uint64_t n_bytes, 
                 e = hipMemcpy((char *)d_src + r.first, (const char *)src + r.first,
                               r.second - r.first, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        st = pack ? atg_pcm_pack_device(d_pcm, (atg_pcm_format)format, pcm_cap, lay, runs, n,
-                                        d_bytes, cap16, nullptr)
-                  : atg_pcm_unpack_device(d_bytes, cap16, lay, runs, n, d_pcm,
+        st = pack ? atg_pcm_pack_device(d_pcm.p, (atg_pcm_format)format, pcm_cap, lay, runs, n,
+                                        d_bytes.p, cap16, nullptr)
+                  : atg_pcm_unpack_device(d_bytes.p, cap16, lay, runs, n, d_pcm.p,
                                           (atg_pcm_format)format, pcm_cap, nullptr);
         if (st == ATG_OK)
             for (const auto &r : covered(runs, n, pack, pack ? lay.bytes_per_sample : ssize))
@@ -296,10 +278,6 @@ atg_status run_host(bool pack, int device, const void *bytes, uint64_t n_bytes, 
                     e = hipMemcpy((char *)dst + r.first, (const char *)d_dst + r.first,
                                   r.second - r.first, hipMemcpyDeviceToHost);
     }
-    if (d_bytes)
-        (void)hipFree(d_bytes);
-    if (d_pcm)
-        (void)hipFree(d_pcm);
     if (e != hipSuccess)
         return g_pb_err.fail(ATG_ERR_DEVICE, std::string("staging: ") + hipGetErrorString(e));
     return st;
@@ -315,13 +293,7 @@ uint32_t atg_pcm_bytes_tile_samples(void) { return kPbTile; }
 
 int atg_pcm_bytes_kernel_times(const char **names, float *ms, int cap)
 {
-    if (!g_pb_name || cap < 1)
-        return 0;
-    if (names)
-        names[0] = g_pb_name;
-    if (ms)
-        ms[0] = g_pb_ms;
-    return 1;
+    return copy_times(&g_pb_name, g_pb_times.ms, g_pb_times.n, names, ms, cap);
 }
 
 atg_status atg_pcm_unpack_device(const void *d_bytes, uint64_t bytes_cap, atg_pcm_layout layout,

@@ -44,7 +44,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -66,8 +65,8 @@ constexpr uint32_t kSilent = 15; // a map nibble
 constexpr uint32_t kOpIdentity = 4; // in the device table: a MAP that changes nothing
 constexpr uint64_t kLimit = 1ull << 62;
 
-thread_local float g_ch_ms = 0.f;
-thread_local bool g_ch_have = false;
+const char *const kStageNames[1] = {"chain"};
+thread_local StageTimes<1> g_ch_times;
 
 struct ChainRow {
     const void *p;    // the source's pointer rounded down to 16 bytes
@@ -84,12 +83,10 @@ struct ChainRow {
 };
 
 struct ChainCtx {
-    std::mutex mu;
     DevBuf rows;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
-constexpr int kMaxDevices = 64;
-ChainCtx g_ctxs[kMaxDevices];
+DeviceContexts<ChainCtx> g_ctxs;
 
 typedef unsigned int Unit __attribute__((ext_vector_type(4))); // 16 bytes
 typedef const __attribute__((address_space(1))) Unit *Units;   // in global memory
@@ -498,23 +495,11 @@ atg_status atg_pcm_chain_device(const atg_pcm_chain_row *rows, uint32_t n_rows, 
         return ATG_OK;
     if (n_tiles > 0x7FFFFFFFull)
         return g_ch_err.fail(ATG_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles in one call");
-    // the device that holds the output, made current
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-        dev = attr.device;
-        CHIP(hipSetDevice(dev));
-    } else {
-        (void)hipGetLastError();
-        CHIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_ch_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    ChainCtx &c = g_ctxs[dev];
-    std::lock_guard<std::mutex> lock(c.mu);
-    for (hipEvent_t &e : c.ev)
-        if (!e)
-            CHIP(hipEventCreate(&e));
+    DeviceContexts<ChainCtx>::Held held; // the device that holds the output
+    if ((st = g_ctxs.hold(d_out, g_ch_err, held)) != ATG_OK)
+        return st;
+    ChainCtx &c = *held;
+    ATG_HIP_TRY(g_ch_err, ensure_events(c.ev), "hipEventCreate(&e)");
     hipStream_t s = (hipStream_t)stream;
     CHIP(c.rows.ensure(sizeof(ChainRow) * tab.size()));
     CHIP(hipMemcpyAsync(c.rows.p, tab.data(), sizeof(ChainRow) * tab.size(),
@@ -529,8 +514,8 @@ atg_status atg_pcm_chain_device(const atg_pcm_chain_row *rows, uint32_t n_rows, 
     CHIP(hipGetLastError());
     CHIP(hipEventRecord(c.ev[1], s));
     CHIP(hipStreamSynchronize(s));
-    g_ch_ms = 0.f;
-    g_ch_have = hipEventElapsedTime(&g_ch_ms, c.ev[0], c.ev[1]) == hipSuccess;
+    g_ch_times = {};
+    g_ch_times.n = hipEventElapsedTime(&g_ch_times.ms[0], c.ev[0], c.ev[1]) == hipSuccess;
     return ATG_OK;
 }
 
@@ -544,12 +529,8 @@ atg_status atg_pcm_chain_host(int device, const atg_pcm_chain_row *rows, uint32_
                                out_cap_samples, dither, dither_bytes);
     if (st != ATG_OK)
         return st;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return g_ch_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return g_ch_err.fail(ATG_ERR_INVALID, "device index out of range");
-    CHIP(hipSetDevice(device));
+    if ((st = use_device(device, g_ch_err)) != ATG_OK)
+        return st;
     // Every source goes up at its host address modulo 16, so the kernel meets
     // the phase the caller laid out.
     std::vector<atg_pcm_chain_row> drows(rows, rows + n_rows);
@@ -563,57 +544,44 @@ atg_status atg_pcm_chain_host(int device, const atg_pcm_chain_row *rows, uint32_
         in_bytes = (at[i] + v.src_frames * rows[i].in_channels * size + 15) / 16 * 16;
     }
     const uint64_t out_bytes = out_cap_samples * (out_format == ATG_PCM_S32 ? 4 : 2);
-    void *di = nullptr, *dout = nullptr, *dd = nullptr;
-    if (hipMalloc(&di, in_bytes ? in_bytes : 16) != hipSuccess ||
-        hipMalloc(&dout, out_bytes ? out_bytes : 16) != hipSuccess ||
-        hipMalloc(&dd, dither_bytes ? dither_bytes : 16) != hipSuccess) {
-        (void)hipFree(di);
-        (void)hipFree(dout);
-        (void)hipFree(dd);
+    DevTemp di, dout, dd;
+    if (di.alloc(in_bytes ? in_bytes : 16) != hipSuccess ||
+        dout.alloc(out_bytes ? out_bytes : 16) != hipSuccess ||
+        dd.alloc(dither_bytes ? dither_bytes : 16) != hipSuccess)
         return g_ch_err.fail(ATG_ERR_NOMEM, "device allocation failed");
-    }
     bool ok = true;
     for (uint32_t i = 0; i < n_rows && ok; ++i) {
         const atg_pcm_view &v = rows[i].src;
         const uint64_t size = v.format == ATG_PCM_S32 ? 4 : 2;
         const uint64_t bytes = v.src_frames * rows[i].in_channels * size;
-        drows[i].src.d_pcm = (const uint8_t *)di + at[i];
+        drows[i].src.d_pcm = (const uint8_t *)di.p + at[i];
         drows[i].src.sample_offset = 0;
         if (bytes)
-            ok = hipMemcpy((uint8_t *)di + at[i],
+            ok = hipMemcpy((uint8_t *)di.p + at[i],
                            (const uint8_t *)v.d_pcm + v.sample_offset * size, bytes,
                            hipMemcpyHostToDevice) == hipSuccess;
     }
     // the output goes up first and comes back whole: what the kernel leaves
     // alone the caller gets back as it was
     if (ok && out_bytes)
-        ok = hipMemcpy(dout, out, out_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        ok = hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (ok && dither_bytes)
-        ok = hipMemcpy(dd, dither, dither_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        ok = hipMemcpy(dd.p, dither, dither_bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok)
         st = g_ch_err.fail(ATG_ERR_DEVICE, "copy to device failed");
     if (st == ATG_OK)
-        st = atg_pcm_chain_device(drows.data(), n_rows, dout, out_format, out_cap_samples,
-                                  dither_bytes ? (const uint8_t *)dd : nullptr, dither_bytes,
+        st = atg_pcm_chain_device(drows.data(), n_rows, dout.p, out_format, out_cap_samples,
+                                  dither_bytes ? (const uint8_t *)dd.p : nullptr, dither_bytes,
                                   nullptr);
     if (st == ATG_OK && out_bytes &&
-        hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
         st = g_ch_err.fail(ATG_ERR_DEVICE, "copy from device failed");
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(dd);
     return st;
 }
 
 int atg_pcm_chain_kernel_times(const char **names, float *ms, int cap)
 {
-    if (!g_ch_have || cap < 1)
-        return 0;
-    if (names)
-        names[0] = "chain";
-    if (ms)
-        ms[0] = g_ch_ms;
-    return 1;
+    return copy_times(kStageNames, g_ch_times.ms, g_ch_times.n, names, ms, cap);
 }
 
 } // extern "C"

@@ -49,7 +49,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -74,8 +73,8 @@ constexpr uint32_t kVerifyChunk = 256;  // of them, at most this many per pair
 constexpr uint64_t kNone = ATG_PCM_NO_MISMATCH;
 constexpr uint64_t kLimit = 1ull << 62;
 
-thread_local float g_pc_ms[2] = {0.f, 0.f}; // compare launches, probe launch
-thread_local bool g_pc_have = false;
+const char *const kStageNames[2] = {"compare", "probe"};
+thread_local StageTimes<2> g_pc_times; // summed over a call's compare launches, its probe launch
 
 // a view as the kernels see it: sample indices count from `p`, the caller's
 // pointer rounded down to 16 bytes
@@ -105,12 +104,10 @@ struct ProbeJob {
 };
 
 struct CmpCtx {
-    std::mutex mu;
     DevBuf pairs, first, jobs, bits;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
-constexpr int kMaxDevices = 64;
-CmpCtx g_ctxs[kMaxDevices];
+DeviceContexts<CmpCtx> g_ctxs;
 
 typedef unsigned int Unit __attribute__((ext_vector_type(4)));  // 16 bytes
 typedef const __attribute__((address_space(1))) Unit *Units; // in global memory
@@ -443,28 +440,16 @@ CmpPair plan_pair(const atg_pcm_pair &p, long long shift_b, uint32_t slot)
     return c;
 }
 
-// the device that holds the batch's PCM, made current
-atg_status pick_device(const atg_pcm_pair *pairs, uint32_t n, int *dev)
+// the batch's first PCM pointer: its device is where the batch runs
+const void *first_pcm(const atg_pcm_pair *pairs, uint32_t n)
 {
-    const void *p = nullptr;
-    for (uint32_t i = 0; i < n && !p; ++i) {
+    for (uint32_t i = 0; i < n; ++i) {
         if (pairs[i].a.src_frames)
-            p = pairs[i].a.d_pcm;
-        else if (pairs[i].b.src_frames)
-            p = pairs[i].b.d_pcm;
+            return pairs[i].a.d_pcm;
+        if (pairs[i].b.src_frames)
+            return pairs[i].b.d_pcm;
     }
-    hipPointerAttribute_t attr;
-    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess &&
-        attr.type == hipMemoryTypeDevice) {
-        *dev = attr.device;
-        CHIP(hipSetDevice(*dev));
-    } else {
-        (void)hipGetLastError();
-        CHIP(hipGetDevice(dev));
-    }
-    if (*dev < 0 || *dev >= kMaxDevices)
-        return g_pc_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    return ATG_OK;
+    return nullptr;
 }
 
 // One compare launch: tab's pairs (each with frames > 0) into n_slots minima.
@@ -495,7 +480,7 @@ atg_status run_compare(CmpCtx &c, std::vector<CmpPair> &tab, uint32_t n_slots,
     CHIP(hipStreamSynchronize(s));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess)
-        g_pc_ms[0] += ms;
+        g_pc_times.ms[0] += ms;
     return ATG_OK;
 }
 
@@ -582,7 +567,7 @@ atg_status search(const atg_pcm_pair *pairs, uint32_t n, uint32_t K, atg_pcm_cmp
         CHIP(hipStreamSynchronize(s));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess)
-            g_pc_ms[1] += ms;
+            g_pc_times.ms[1] += ms;
         for (uint32_t o = 0; o < open.size(); ++o)
             if (job_of[o] != UINT32_MAX)
                 std::copy(got.begin() + (size_t)job_of[o] * words,
@@ -659,17 +644,12 @@ atg_status run(const atg_pcm_pair *pairs, uint32_t n, uint32_t max_offset, bool 
     if (!any)
         return ATG_OK;
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    st = pick_device(pairs, n, &dev);
-    if (st != ATG_OK)
+    DeviceContexts<CmpCtx>::Held held;
+    if ((st = g_ctxs.hold(first_pcm(pairs, n), g_pc_err, held)) != ATG_OK)
         return st;
-    CmpCtx &c = g_ctxs[dev];
-    std::lock_guard<std::mutex> lock(c.mu);
-    for (hipEvent_t &e : c.ev)
-        if (!e)
-            CHIP(hipEventCreate(&e));
-    g_pc_ms[0] = g_pc_ms[1] = 0.f;
-    g_pc_have = true;
+    CmpCtx &c = *held;
+    ATG_HIP_TRY(g_pc_err, ensure_events(c.ev), "hipEventCreate(&e)");
+    g_pc_times = {{0.f, 0.f}, 2};
     if (want_offset)
         return search(pairs, n, max_offset, results, c, s);
     std::vector<CmpPair> tab;
@@ -708,17 +688,7 @@ uint32_t atg_pcm_compare_tile_frames(void) { return kTile; }
 
 int atg_pcm_compare_kernel_times(const char **names, float *ms, int cap)
 {
-    static const char *const kNames[2] = {"compare", "probe"};
-    if (!g_pc_have)
-        return 0;
-    const int k = cap < 2 ? (cap < 0 ? 0 : cap) : 2;
-    for (int i = 0; i < k; ++i) {
-        if (names)
-            names[i] = kNames[i];
-        if (ms)
-            ms[i] = g_pc_ms[i];
-    }
-    return k;
+    return copy_times(kStageNames, g_pc_times.ms, g_pc_times.n, names, ms, cap);
 }
 
 } // extern "C"

@@ -246,43 +246,34 @@ atg_status atg_pcm_convert_host(int device, int kind, const int32_t *in, int32_t
                                 uint32_t in_bps, uint32_t out_bps, const uint8_t *dither,
                                 uint64_t dither_bytes, uint64_t dither_bit0)
 {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return g_conv_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return g_conv_err.fail(ATG_ERR_INVALID, "device index out of range");
-    CHIP(hipSetDevice(device));
+    atg_status st = use_device(device, g_conv_err);
+    if (st != ATG_OK)
+        return st;
     const uint32_t oc = atg_pcm_convert_out_channels(kind, channels);
     const uint64_t need_bits = frames * channels;
     if (kind == ATG_CONV_BPS && out_bps < in_bps && dither_bytes * 8 < need_bits + dither_bit0)
         return g_conv_err.fail(ATG_ERR_INVALID, "not enough dither bytes");
-    void *di = nullptr, *dout = nullptr, *dd = nullptr;
+    DevTemp di, dout, dd;
     const size_t ib = sizeof(int32_t) * (frames * channels ? frames * channels : 1);
     const size_t ob = sizeof(int32_t) * (frames * oc ? frames * oc : 1);
-    if (hipMalloc(&di, ib) != hipSuccess || hipMalloc(&dout, ob) != hipSuccess ||
-        hipMalloc(&dd, dither_bytes ? dither_bytes : 1) != hipSuccess) {
-        (void)hipFree(di);
-        (void)hipFree(dout);
-        (void)hipFree(dd);
+    if (di.alloc(ib) != hipSuccess || dout.alloc(ob) != hipSuccess ||
+        dd.alloc(dither_bytes ? dither_bytes : 1) != hipSuccess)
         return g_conv_err.fail(ATG_ERR_NOMEM, "device allocation failed");
-    }
-    atg_status st = ATG_OK;
-    if (hipMemcpy(di, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
+    if (hipMemcpy(di.p, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
             hipSuccess ||
-        (dither_bytes && hipMemcpy(dd, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
+        (dither_bytes &&
+         hipMemcpy(dd.p, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
         st = g_conv_err.fail(ATG_ERR_DEVICE, "copy to device failed");
     if (st == ATG_OK)
-        st = atg_pcm_convert_device(kind, (const int32_t *)di, (int32_t *)dout, frames, channels,
-                                    channel_mask, in_bps, out_bps,
-                                    dither_bytes ? (const uint8_t *)dd : nullptr, dither_bit0,
+        st = atg_pcm_convert_device(kind, (const int32_t *)di.p, (int32_t *)dout.p, frames,
+                                    channels, channel_mask, in_bps, out_bps,
+                                    dither_bytes ? (const uint8_t *)dd.p : nullptr, dither_bit0,
                                     nullptr);
     if (st == ATG_OK &&
         (hipDeviceSynchronize() != hipSuccess ||
-         hipMemcpy(out, dout, sizeof(int32_t) * frames * oc, hipMemcpyDeviceToHost) != hipSuccess))
+         hipMemcpy(out, dout.p, sizeof(int32_t) * frames * oc, hipMemcpyDeviceToHost) !=
+             hipSuccess))
         st = g_conv_err.fail(ATG_ERR_DEVICE, "conversion failed on the device");
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(dd);
     return st;
 }
 
@@ -319,40 +310,30 @@ atg_status atg_pcm_apply_gain_host(int device, const int32_t *in, int32_t *out, 
                                    uint32_t chunk_frames, const uint8_t *dither,
                                    uint64_t dither_bytes, uint64_t dither_bit0)
 {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return g_conv_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return g_conv_err.fail(ATG_ERR_INVALID, "device index out of range");
-    CHIP(hipSetDevice(device));
+    atg_status st = use_device(device, g_conv_err);
+    if (st != ATG_OK)
+        return st;
     if (dither_bytes * 8 < frames * channels + dither_bit0)
         return g_conv_err.fail(ATG_ERR_INVALID, "not enough dither bytes");
-    void *di = nullptr, *dout = nullptr, *dd = nullptr;
+    DevTemp di, dout, dd;
     const size_t nb = sizeof(int32_t) * (frames * channels ? frames * channels : 1);
-    if (hipMalloc(&di, nb) != hipSuccess || hipMalloc(&dout, nb) != hipSuccess ||
-        hipMalloc(&dd, dither_bytes ? dither_bytes : 1) != hipSuccess) {
-        (void)hipFree(di);
-        (void)hipFree(dout);
-        (void)hipFree(dd);
+    if (di.alloc(nb) != hipSuccess || dout.alloc(nb) != hipSuccess ||
+        dd.alloc(dither_bytes ? dither_bytes : 1) != hipSuccess)
         return g_conv_err.fail(ATG_ERR_NOMEM, "device allocation failed");
-    }
-    atg_status st = ATG_OK;
-    if (hipMemcpy(di, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
+    if (hipMemcpy(di.p, in, sizeof(int32_t) * frames * channels, hipMemcpyHostToDevice) !=
             hipSuccess ||
-        (dither_bytes && hipMemcpy(dd, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
+        (dither_bytes &&
+         hipMemcpy(dd.p, dither, dither_bytes, hipMemcpyHostToDevice) != hipSuccess))
         st = g_conv_err.fail(ATG_ERR_DEVICE, "copy to device failed");
     if (st == ATG_OK)
-        st = atg_pcm_apply_gain_device((const int32_t *)di, (int32_t *)dout, frames, channels,
-                                       bps, multiplier, chunk_frames, (const uint8_t *)dd,
-                                       dither_bit0, nullptr);
+        st = atg_pcm_apply_gain_device((const int32_t *)di.p, (int32_t *)dout.p, frames,
+                                       channels, bps, multiplier, chunk_frames,
+                                       (const uint8_t *)dd.p, dither_bit0, nullptr);
     if (st == ATG_OK &&
         (hipDeviceSynchronize() != hipSuccess ||
-         hipMemcpy(out, dout, sizeof(int32_t) * frames * channels, hipMemcpyDeviceToHost) !=
+         hipMemcpy(out, dout.p, sizeof(int32_t) * frames * channels, hipMemcpyDeviceToHost) !=
              hipSuccess))
         st = g_conv_err.fail(ATG_ERR_DEVICE, "gain application failed on the device");
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(dd);
     return st;
 }
 

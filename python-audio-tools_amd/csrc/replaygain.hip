@@ -515,13 +515,11 @@ __global__ __launch_bounds__(256) void k_rg_gain(const uint32_t *__restrict__ hi
 // device buffers of one device (kept across calls; a batch pipeline calls
 // this once per album batch)
 struct RgCtx {
-    std::mutex mu;
     bool coeffs = false;
     DevBuf tracks, hist, peaks, gains, alb, meta, wsum, wbase, chunks, segs, seam_in, seam_out,
         amax, dmax, warm, flag, tlist, amb, namb, mag;
 };
-constexpr int kMaxDevices = 64;
-RgCtx g_ctxs[kMaxDevices];
+DeviceContexts<RgCtx> g_ctxs;
 
 // test hook (atg_replaygain_set_warmup): warm-up frames of every warm
 // segment, -1 = the rate-scaled default; 0 starts each segment from zero
@@ -977,12 +975,11 @@ atg_status atg_replaygain_device(const int32_t *d_pcm, const atg_rg_track *track
     if ((!tracks || !results) && n)
         return g_rg_err.fail(ATG_ERR_INVALID, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    RHIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices)
-        return g_rg_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    RgCtx &g_ctx = g_ctxs[dev];
-    std::lock_guard<std::mutex> lock(g_ctx.mu);
+    DeviceContexts<RgCtx>::Held held; // where the PCM is
+    const atg_status hs = g_ctxs.hold(d_pcm, g_rg_err, held);
+    if (hs != ATG_OK)
+        return hs;
+    RgCtx &g_ctx = *held;
     if (!g_ctx.coeffs) {
         RHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_yule), RG_YULE, sizeof(RG_YULE)));
         RHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_butter), RG_BUTTER, sizeof(RG_BUTTER)));
@@ -1234,15 +1231,14 @@ atg_status atg_replaygain_hist_gain(const uint32_t *d_hist, uint32_t n, double *
     if (!n)
         return ATG_OK;
     hipStream_t s = (hipStream_t)stream;
-    double *d_g = nullptr;
-    RHIP(hipMalloc(&d_g, sizeof(double) * n));
-    hipLaunchKernelGGL(k_rg_gain, dim3(n), dim3(256), 0, s, d_hist, n, d_g);
+    DevTemp d_g;
+    ATG_HIP_TRY(g_rg_err, d_g.alloc(sizeof(double) * n), "hipMalloc(&d_g, sizeof(double) * n)");
+    hipLaunchKernelGGL(k_rg_gain, dim3(n), dim3(256), 0, s, d_hist, n, (double *)d_g.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
-        e = hipMemcpyAsync(gains, d_g, sizeof(double) * n, hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(gains, d_g.p, sizeof(double) * n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);
-    (void)hipFree(d_g);
     if (e != hipSuccess)
         return g_rg_err.fail(ATG_ERR_DEVICE, hipGetErrorString(e));
     return ATG_OK;

@@ -991,10 +991,11 @@ struct RsCtx {
     void *table = nullptr;
     bool table_up = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms[2] = {0.0f, 0.0f};
 };
-constexpr int kMaxDev = 64;
-RsCtx g_rs[kMaxDev];
+DeviceContexts<RsCtx> g_rs;
+
+const char *const kStageNames[2] = {"rs_positions", "rs_filter"};
+thread_local StageTimes<2> g_rs_times;
 
 } // namespace
 
@@ -1022,11 +1023,10 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
     if (bits_per_sample < 1 || bits_per_sample > 24)
         return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "bits per sample must be 1..24");
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    RSHIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDev)
-        return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "device index too large");
-    RsCtx &X = g_rs[dev];
+    DeviceContexts<RsCtx>::Held held; // where the input is
+    if (atg_status st = g_rs.hold(d_in, g_rs_err, held); st != ATG_OK)
+        return st;
+    RsCtx &X = *held;
     std::vector<RsTrack> tr(n);
     std::vector<uint32_t> chunk_track, serial;
     // outputs per block iteration: the LDS holds the table plus the input
@@ -1194,8 +1194,7 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
     if (!X.table_up) {
         RSHIP(hipMalloc(&X.table, sizeof(SRC_MEDIUM_BITS)));
         RSHIP(hipMemcpy(X.table, SRC_MEDIUM_BITS, sizeof(SRC_MEDIUM_BITS), hipMemcpyHostToDevice));
-        for (int k = 0; k < 3; ++k)
-            RSHIP(hipEventCreate(&X.ev[k]));
+        ATG_HIP_TRY(g_rs_err, ensure_events(X.ev), "hipEventCreate(&X.ev[k])");
         RSHIP(set_lds_attr<1>());
         RSHIP(set_lds_attr<2>());
         RSHIP(set_lds_attr<3>());
@@ -1285,25 +1284,15 @@ atg_status atg_resample_device(const atg_rs_track *tracks, uint32_t n, uint32_t 
     }
     RSHIP(hipEventRecord(X.ev[2], s));
     RSHIP(hipStreamSynchronize(s));
-    X.ms[0] = X.ms[1] = 0.0f;
-    (void)hipEventElapsedTime(&X.ms[0], X.ev[0], X.ev[1]);
-    (void)hipEventElapsedTime(&X.ms[1], X.ev[1], X.ev[2]);
+    g_rs_times = {{0.0f, 0.0f}, 2};
+    (void)hipEventElapsedTime(&g_rs_times.ms[0], X.ev[0], X.ev[1]);
+    (void)hipEventElapsedTime(&g_rs_times.ms[1], X.ev[1], X.ev[2]);
     return ATG_OK;
 }
 
 int atg_resample_kernel_times(const char **names, float *ms, int cap)
 {
-    static const char *kNames[2] = {"rs_positions", "rs_filter"};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev)
-        return 0;
-    for (int k = 0; k < 2 && k < cap; ++k) {
-        if (names)
-            names[k] = kNames[k];
-        if (ms)
-            ms[k] = g_rs[dev].ms[k];
-    }
-    return 2;
+    return copy_times(kStageNames, g_rs_times.ms, g_rs_times.n, names, ms, cap);
 }
 
 atg_status atg_resample_host(int device, const atg_rs_track *tracks, uint32_t n,
@@ -1311,7 +1300,8 @@ atg_status atg_resample_host(int device, const atg_rs_track *tracks, uint32_t n,
                              uint64_t in_samples, int32_t *out, uint64_t out_cap_samples,
                              uint64_t *out_offsets, uint64_t *out_frames)
 {
-    RSHIP(hipSetDevice(device));
+    if (atg_status st = use_device(device, g_rs_err); st != ATG_OK)
+        return st;
     if (channels < 1 || channels > 8)
         return g_rs_err.fail(ATG_ERR_UNSUPPORTED, "channels must be 1..8");
     uint64_t total = 0;
@@ -1324,24 +1314,22 @@ atg_status atg_resample_host(int device, const atg_rs_track *tracks, uint32_t n,
     if (total * channels > out_cap_samples)
         return g_rs_err.fail(ATG_ERR_CAPACITY,
                              "output buffer too small (atg_resample_output_frames)");
-    int32_t *d_in = nullptr, *d_out = nullptr;
-    RSHIP(hipMalloc(&d_in, std::max<uint64_t>(in_samples, 1) * 4));
-    hipError_t e = hipMalloc(&d_out, std::max<uint64_t>(total * channels, 1) * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(d_in);
+    DevTemp d_in, d_out;
+    ATG_HIP_TRY(g_rs_err, d_in.alloc(std::max<uint64_t>(in_samples, 1) * 4),
+                "hipMalloc(&d_in, std::max<uint64_t>(in_samples, 1) * 4)");
+    hipError_t e = d_out.alloc(std::max<uint64_t>(total * channels, 1) * 4);
+    if (e != hipSuccess)
         return g_rs_err.fail(ATG_ERR_NOMEM, hipGetErrorString(e));
-    }
     atg_status st = ATG_OK;
-    if (in_samples && hipMemcpy(d_in, in, in_samples * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (in_samples && hipMemcpy(d_in.p, in, in_samples * 4, hipMemcpyHostToDevice) != hipSuccess)
         st = g_rs_err.fail(ATG_ERR_DEVICE, "hipMemcpy input");
     if (st == ATG_OK)
-        st = atg_resample_device(tracks, n, channels, bits_per_sample, d_in, d_out,
-                                 total * channels, out_offsets, out_frames, nullptr);
+        st = atg_resample_device(tracks, n, channels, bits_per_sample, (const int32_t *)d_in.p,
+                                 (int32_t *)d_out.p, total * channels, out_offsets, out_frames,
+                                 nullptr);
     if (st == ATG_OK && total &&
-        hipMemcpy(out, d_out, total * channels * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(out, d_out.p, total * channels * 4, hipMemcpyDeviceToHost) != hipSuccess)
         st = g_rs_err.fail(ATG_ERR_DEVICE, "hipMemcpy output");
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return st;
 }
 

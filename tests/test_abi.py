@@ -5,10 +5,12 @@ import ctypes
 import os
 import re
 import subprocess
+import threading
 
 import numpy as np
 import pytest
 
+import bad_device
 from audiotools import _atgpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,6 +101,40 @@ def test_handle_null_arguments(prefix):
     assert getattr(lib, prefix + "_create")(0, None) == _atgpu.ATG_ERR_INVALID
     getattr(lib, prefix + "_destroy")(None)  # no-op
     assert getattr(lib, prefix + "_kernel_times")(None, None, None, 0) == 0
+
+
+def test_host_entries_refuse_device_minus_1():
+    """the handle-less *_host entries kept in this file's care: the resampler
+    and the two single conversions answer a bad index as the others do"""
+    lib = _atgpu.load_library()
+    pcm = np.zeros(64, dtype=np.int32)
+    out = np.zeros(256, dtype=np.int32)
+    offs, cnt = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    tracks = _atgpu.resample_tracks([(0, 32, 44100, 48000)], 2)
+    bad_device.check_refused(lib.atg_resample_host(-1, tracks, 1, 2, 16, P(pcm), 64, P(out), 256,
+                                                   P(offs), P(cnt)), "resample")
+    # the index comes before the other arguments, as it did
+    bad_device.check_refused(lib.atg_resample_host(-1, tracks, 1, 9, 16, P(pcm), 64, P(out), 256,
+                                                   P(offs), P(cnt)), "resample")
+    bad_device.check_refused(lib.atg_pcm_convert_host(
+        -1, _atgpu.CONV_AVERAGE, P(pcm), P(out), 32, 2, 0, 16, 16, None, 0, 0), "pcm_convert")
+    dither = np.zeros(8, dtype=np.uint8)
+    bad_device.check_refused(lib.atg_pcm_apply_gain_host(
+        -1, P(pcm), P(out), 32, 2, 16, 0.5, 4096, P(dither), 8, 0), "pcm_convert")
+
+
+def test_resample_times_are_per_thread_and_honour_cap():
+    """a thread that has not resampled has no times, whatever another did"""
+    lib = _atgpu.load_library()
+    got = []
+    t = threading.Thread(target=lambda: got.extend([
+        lib.atg_resample_kernel_times(None, None, 4), lib.atg_resample_kernel_times(None, None, 0),
+        _atgpu.resample_kernel_times()]))
+    t.start()
+    t.join()
+    assert got == [0, 0, {}]
+    assert lib.atg_resample_kernel_times(None, None, 0) == 0
 
 
 def test_shared_handle_is_one_per_class(monkeypatch):

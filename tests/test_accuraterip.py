@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import accuraterip_port as port
+import bad_device
 import oracle_port
 from audiotools import _accuraterip, _atgpu, accuraterip, pcm
 
@@ -169,14 +170,14 @@ def _device_call(tracks, max_offset=0, fmt=_atgpu.PCM_S32, null=(), n=None):
         None if "table" in null else table.ctypes.data_as(ctypes.c_void_p), None)
 
 
-def _host_call(tracks, max_offset=0, frames_total=32, null=()):
+def _host_call(tracks, max_offset=0, frames_total=32, null=(), device=0):
     lib = _atgpu.load_library()
     arr = (_atgpu.ArTrack * max(1, len(tracks)))(*tracks)
     res = (_atgpu.ArResult * max(1, len(tracks)))()
     table = np.zeros(max(1, len(tracks)) * (2 * min(max_offset, 65535) + 1), dtype=np.uint32)
     buf = np.zeros(64, dtype=np.int32)
     return lib.atg_accuraterip_host(
-        0, None if "pcm" in null else buf.ctypes.data_as(ctypes.c_void_p), _atgpu.PCM_S32,
+        device, None if "pcm" in null else buf.ctypes.data_as(ctypes.c_void_p), _atgpu.PCM_S32,
         frames_total, None if "tracks" in null else arr, len(tracks), max_offset,
         None if "results" in null else res,
         None if "table" in null else table.ctypes.data_as(ctypes.c_void_p))
@@ -236,6 +237,11 @@ def test_unknown_format_and_empty_batch():
 
 def test_host_region_must_lie_in_the_buffer():
     assert _host_call([_t(hi_frame=33)], frames_total=32) == _atgpu.ATG_ERR_INVALID
+
+
+def test_host_entry_refuses_device_minus_1():
+    bad_device.check_refused(_host_call([_t()], device=-1), "accuraterip")
+    bad_device.check_refused(_host_call([_t()], max_offset=3, device=-1), "accuraterip")
 
 
 def test_binding_raises_with_the_message():

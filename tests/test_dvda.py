@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import aob_port as port
+import bad_device
 import dvda_build as build
 import dvda_cases as cases
 from audiotools import _atgpu, dvda
@@ -336,3 +337,9 @@ def test_argument_checks_need_no_device():
              _atgpu.ATG_ERR_INVALID, "NULL")]:
         assert call() == status, words
         assert words in lib.atg_aob_last_error().decode(), words
+    # a sound call on device -1: one whole sector in, room for its samples out
+    sector = np.zeros(2048, dtype=np.uint8)
+    pcm = np.zeros(1024, dtype=np.int32)
+    bad_device.check_refused(lib.atg_aob_decode_host(
+        -1, sector.ctypes.data_as(ctypes.c_void_p), 2048, _atgpu.aob_titles([(0, 1)])[0], 1,
+        pcm.ctypes.data_as(ctypes.c_void_p), _atgpu.PCM_S32, 1024, res), "aob")

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import bad_device
 from audiotools import _atgpu, aiff, au
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +108,20 @@ def test_host_entries_check_before_staging():
                                    0) == _atgpu.ATG_OK
     assert _atgpu.pcm_bytes_tile_samples() % 8 == 0
     assert lib.atg_pcm_bytes_kernel_times(None, None, 0) == 0
+
+
+def test_host_entries_refuse_device_minus_1():
+    lib = _atgpu.load_library()
+    arr, n = _atgpu.pcm_runs([(0, 8, 0)])
+    b, p = _buf(16), _buf(64)
+    lay = _atgpu.pcm_layout(2, True, True)
+    bad_device.check_refused(lib.atg_pcm_unpack_host(
+        -1, b.ctypes.data, 16, lay, arr, n, p.ctypes.data, _atgpu.PCM_S32, 16), "pcm_bytes")
+    bad_device.check_refused(lib.atg_pcm_pack_host(
+        -1, p.ctypes.data, _atgpu.PCM_S16, 16, lay, arr, n, b.ctypes.data, 16), "pcm_bytes")
+    # nothing to do comes first: no device is asked for
+    assert lib.atg_pcm_unpack_host(-1, None, 0, lay, None, 0, None, _atgpu.PCM_S32,
+                                   0) == _atgpu.ATG_OK
 
 
 # ------------------------------------------------------------------ parsers

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import bad_device
 import oracle_port
 import pcm_chain_port as port
 import signals
@@ -121,6 +122,20 @@ def test_host_entry_refuses_the_same():
     with pytest.raises(_atgpu.ATGError) as e:
         _atgpu.pcm_chain_host([row(d_pcm=src.ctypes.data, in_bps=24, out_bps=16)], out)
     assert e.value.status == INVALID  # no dither bytes
+
+
+def test_host_entry_refuses_device_minus_1():
+    lib = _atgpu.load_library()
+    src = np.zeros(64, dtype=np.int32)
+    out = np.zeros(64, dtype=np.int32)
+    arr = (_atgpu.PcmChainRow * 1)(row(d_pcm=src.ctypes.data))
+    bad_device.check_refused(lib.atg_pcm_chain_host(-1, arr, 1, out.ctypes.data, _atgpu.PCM_S32,
+                                                    64, None, 0), "pcm_chain")
+    # the rows are judged first
+    arr[0].in_channels = 9
+    assert lib.atg_pcm_chain_host(-1, arr, 1, out.ctypes.data, _atgpu.PCM_S32, 64, None,
+                                  0) == INVALID
+    assert b"channel count" in lib.atg_pcm_chain_last_error()
 
 
 def test_struct_size_and_tile():

@@ -1,7 +1,7 @@
 // Host-code probe, CPU only, under AddressSanitizer (csrc/Makefile
 // `host-asan`: the library's objects with the host side instrumented).  No
-// HIP call is made; it exercises the host code that parses untrusted bytes
-// or writes caller memory:
+// kernel is launched and no device is needed; it exercises the host code
+// that parses untrusted bytes or writes caller memory:
 //   * atg_flac_read_metadata / atg_alac_read_info on real images, every
 //     truncation of them and byte-mutated copies (the metadata and atom
 //     walkers must stay inside `len`);
@@ -14,7 +14,10 @@
 //     socket: a good reply, a reply whose frame count or sizes disagree
 //     with the request, an oversized byte count or error text, and a
 //     service that never answers -- refused, nothing written past the
-//     caller's buffers (guard words).
+//     caller's buffers (guard words);
+//   * every *_host entry of the components without a handle, sound arguments
+//     on device -1: refused by the shared prelude (host_common.h), with the
+//     scoped staging allocations left empty.
 // Prints one JSON line; exit status 0 when every check passed.
 #include "../include/atgpu.h"
 #include "../python-audio-tools_amd/csrc/md5_cpu.h"
@@ -311,6 +314,70 @@ static int service_check()
     return n;
 }
 
+// one refusal: the prelude counts the devices before it looks at the index
+static int refused(atg_status st, const char *msg)
+{
+    const bool none = st == ATG_ERR_DEVICE && !std::strcmp(msg, "no HIP device available");
+    const bool range = st == ATG_ERR_INVALID && !std::strcmp(msg, "device index out of range");
+    CHECK(none || range);
+    return 1;
+}
+
+static int host_refusals_check()
+{
+    int n = 0;
+    std::vector<int32_t> pcm(4096, 0), out(4096, 0);
+    std::vector<uint8_t> bytes(2048, 0);
+
+    atg_ar_track ar = {0, 16, 0, 16, 0, 16, 44100, 0};
+    atg_ar_result ar_res = {};
+    n += refused(atg_accuraterip_host(-1, pcm.data(), ATG_PCM_S32, 32, &ar, 1, 0, &ar_res, nullptr),
+                 atg_accuraterip_last_error());
+
+    const atg_pcm_layout lay = {2, 1, 1, 0};
+    const atg_pcm_run run = {0, 8, 0};
+    n += refused(atg_pcm_unpack_host(-1, bytes.data(), 16, lay, &run, 1, pcm.data(), ATG_PCM_S32,
+                                     16),
+                 atg_pcm_bytes_last_error());
+    n += refused(atg_pcm_pack_host(-1, pcm.data(), ATG_PCM_S32, 16, lay, &run, 1, bytes.data(), 16),
+                 atg_pcm_bytes_last_error());
+
+    atg_pcm_chain_row row = {};
+    row.src = {pcm.data(), 0, 10, 0, ATG_PCM_S32, 0};
+    row.in_channels = row.out_channels = 2;
+    row.channel_op = ATG_CHAIN_MAP;
+    row.map[0] = 0;
+    row.map[1] = 1;
+    row.in_bps = row.out_bps = 16;
+    n += refused(atg_pcm_chain_host(-1, &row, 1, out.data(), ATG_PCM_S32, 64, nullptr, 0),
+                 atg_pcm_chain_last_error());
+
+    const atg_aob_title title = {0, 1, 0};
+    atg_aob_result aob_res = {};
+    n += refused(atg_aob_decode_host(-1, bytes.data(), bytes.size(), &title, 1, out.data(),
+                                     ATG_PCM_S32, 1024, &aob_res),
+                 atg_aob_last_error());
+    atg_mlp_result mlp_res = {};
+    n += refused(atg_mlp_decode_host(-1, bytes.data(), bytes.size(), &title, 1, out.data(),
+                                     ATG_PCM_S32, 1024, &mlp_res),
+                 atg_mlp_last_error());
+
+    const atg_rs_track rs = {0, 32, 44100, 48000, nullptr, 0};
+    uint64_t offs = 0, cnt = 0;
+    n += refused(atg_resample_host(-1, &rs, 1, 2, 16, pcm.data(), 64, out.data(), 256, &offs, &cnt),
+                 atg_resample_last_error());
+    CHECK(atg_resample_kernel_times(nullptr, nullptr, 4) == 0);
+
+    const uint8_t dither[8] = {};
+    n += refused(atg_pcm_convert_host(-1, ATG_CONV_AVERAGE, pcm.data(), out.data(), 32, 2, 0, 16,
+                                      16, nullptr, 0, 0),
+                 atg_pcm_convert_last_error());
+    n += refused(atg_pcm_apply_gain_host(-1, pcm.data(), out.data(), 32, 2, 16, 0.5, 4096, dither,
+                                         8, 0),
+                 atg_pcm_convert_last_error());
+    return n;
+}
+
 int main(int argc, char **argv)
 {
     const std::string root = argc > 1 ? argv[1] : ".";
@@ -328,10 +395,10 @@ int main(int argc, char **argv)
     if (!m4a.empty())
         alac_calls = metadata_fuzz(m4a, true, rng);
     const int md5 = md5_check(rng), gather = gather_check(rng), bounds = bounds_check(),
-              svc = service_check();
+              svc = service_check(), refusals = host_refusals_check();
     std::printf("{\"flac_metadata_calls\": %d, \"alac_info_calls\": %d, \"md5_cases\": %d, "
                 "\"gather_cases\": %d, \"bounds_cases\": %d, \"service_cases\": %d, "
-                "\"failures\": %d}\n",
-                flac_calls, alac_calls, md5, gather, bounds, svc, g_fail);
+                "\"host_refusals\": %d, \"failures\": %d}\n",
+                flac_calls, alac_calls, md5, gather, bounds, svc, refusals, g_fail);
     return g_fail ? 1 : 0;
 }
