@@ -1896,6 +1896,8 @@ int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float
 #include "atgpu_dvda.h"
 /* MLP titles of DVD-Audio discs, on the same title table */
 #include "atgpu_mlp.h"
+/* PCM rows to and from planar float tensors */
+#include "atgpu_tensor.h"
 /* test probes into the encoder's kernels */
 #include "atgpu_probe.h"
 #endif

@@ -17,6 +17,9 @@ find the same names with the same meaning:
   audiotools.convert_files_batch  track2track's per-file convert() for a batch
                                   of files, the PCM on the device throughout
   audiotools.convert_pcm_batch .. PCMConverter for a batch of numpy tracks
+  audiotools.load_batch / save_flac_batch / pcm_to_tensor / tensor_to_pcm
+                                  decoded batches as PyTorch tensors and back
+                                  (tensors.py; torch is imported on first use)
 
 track2track's per-file step is `AudioFile.convert(target, FlacAudio, "8")`
 and trackverify's is `AudioFile.verify()`; both run through these classes,
@@ -608,3 +611,14 @@ from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa:
                        find_offset_batch, compare_pcm_batch)
 from .pcmconverter import convert_pcm_batch  # noqa: E402,F401
 from .convert import convert_files_batch  # noqa: E402,F401
+
+# the tensor interface (tensors.py) imports torch: its names are looked up on
+# first use, so importing the package does not import torch
+_TENSOR_NAMES = ("pcm_to_tensor", "tensor_to_pcm", "load_batch", "save_flac_batch")
+
+
+def __getattr__(name):
+    if name in _TENSOR_NAMES:
+        from . import tensors
+        return getattr(tensors, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -781,6 +781,32 @@ MLP_SIGNATURES = {
     "atg_mlp_kernel_times": _THREAD_TIMES,
 }
 
+# ---- tensors (include/atgpu_tensor.h, included by atgpu.h after atgpu_mlp.h)
+class PcmToTensorRow(ctypes.Structure):
+    """atg_pcm_to_tensor_row: one row of a PCM -> tensor call"""
+    _fields_ = [("src", PcmView), ("channels", c_u32), ("bits_per_sample", c_u32),
+                ("pad_frames", c_u64), ("out_offset", c_u64), ("channel_stride", c_u64)]
+
+
+class PcmFromTensorRow(ctypes.Structure):
+    """atg_pcm_from_tensor_row: one row of a tensor -> PCM call"""
+    _fields_ = [("in_offset", c_u64), ("channel_stride", c_u64), ("frames", c_u64),
+                ("channels", c_u32), ("bits_per_sample", c_u32), ("out_offset", c_u64)]
+
+
+TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_I32 = range(4)
+TENSOR_ELEM_BYTES = {TENSOR_F16: 2, TENSOR_F32: 4, TENSOR_F64: 8, TENSOR_I32: 4}
+
+# the prototypes of include/atgpu_tensor.h, applied by load_library() as well
+TENSOR_SIGNATURES = {
+    "atg_pcm_tensor_last_error": _LAST_ERROR,
+    "atg_pcm_to_tensor_device": (c_int, (ptr(PcmToTensorRow), c_u32, P, c_int, c_u64, P)),
+    "atg_pcm_from_tensor_device": (c_int, (ptr(PcmFromTensorRow), c_u32, P, c_int, c_u64, P,
+                                           c_int, c_u64, P)),
+    "atg_pcm_tensor_tile_frames": _TILE,
+    "atg_pcm_tensor_kernel_times": _THREAD_TIMES,
+}
+
 # ---- test probes (include/atgpu_probe.h, included by atgpu.h last)
 PROBE_SIGNATURES = {
     # engine, options, pcm, format, tracks, n, channels, bits, sums, cap, window_n, window
@@ -804,6 +830,7 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()) +
                                           list(MLP_SIGNATURES.items()) +
+                                          list(TENSOR_SIGNATURES.items()) +
                                           list(PROBE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -2607,6 +2634,50 @@ def pcm_chain_tile_frames(in_channels, out_channels):
 def pcm_chain_kernel_times():
     """{"chain": ms} of this thread's last launch"""
     return _thread_times(load_library().atg_pcm_chain_kernel_times, 1)
+
+
+# ------------------------------------------------------ tensors (pcm_tensor.hip)
+def pcm_to_tensor_row(src, channels, bits_per_sample, pad_frames, out_offset, channel_stride):
+    """PcmToTensorRow over the PcmView `src` (its src_frames is the row's
+    length)"""
+    return PcmToTensorRow(src, channels, bits_per_sample, pad_frames, out_offset, channel_stride)
+
+
+def pcm_from_tensor_row(in_offset, channel_stride, frames, channels, bits_per_sample,
+                        out_offset):
+    return PcmFromTensorRow(in_offset, channel_stride, frames, channels, bits_per_sample,
+                            out_offset)
+
+
+def pcm_to_tensor_device(rows, d_out, dtype, out_cap_elems, stream=None):
+    """rows: [PcmToTensorRow] -> the planar runs in device memory
+    (atg_pcm_to_tensor_device); stream: a hipStream_t as an integer"""
+    lib = load_library()
+    arr = (PcmToTensorRow * max(len(rows), 1))(*rows)
+    _check(lib, lib.atg_pcm_to_tensor_device(
+        arr, len(rows), ctypes.c_void_p(d_out), dtype, out_cap_elems,
+        ctypes.c_void_p(stream) if stream else None), "pcm_tensor")
+
+
+def pcm_from_tensor_device(rows, d_in, dtype, in_cap_elems, d_out, out_fmt, out_cap_samples,
+                           stream=None):
+    """rows: [PcmFromTensorRow] -> interleaved PCM in device memory
+    (atg_pcm_from_tensor_device)"""
+    lib = load_library()
+    arr = (PcmFromTensorRow * max(len(rows), 1))(*rows)
+    _check(lib, lib.atg_pcm_from_tensor_device(
+        arr, len(rows), ctypes.c_void_p(d_in), dtype, in_cap_elems, ctypes.c_void_p(d_out),
+        out_fmt, out_cap_samples, ctypes.c_void_p(stream) if stream else None), "pcm_tensor")
+
+
+def pcm_tensor_tile_frames():
+    """frames per tile of both tensor kernels"""
+    return int(load_library().atg_pcm_tensor_tile_frames())
+
+
+def pcm_tensor_kernel_times():
+    """{"to_tensor" or "from_tensor": ms} of this thread's last tensor call"""
+    return _thread_times(load_library().atg_pcm_tensor_kernel_times, 2)
 
 
 def aiff_read_info(data):
