@@ -2,8 +2,8 @@
 // the growable device buffer, the per-component error slot with its
 // "try a HIP call" macro, the stage times, the base of the single-stream
 // codec handles, and what a component without a handle is made of: its
-// per-device contexts, the device it runs on and the staging of its *_host
-// entries.  Host code only; nothing here is seen by a kernel.
+// per-device contexts, its one timed launch, the device it runs on and the
+// staging of its *_host entries.  Host code only; nothing here is seen by a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/atgpu.h"
 
@@ -95,6 +96,38 @@ template <int N> hipError_t ensure_events(hipEvent_t (&ev)[N])
         if (!e && err == hipSuccess)
             err = hipEventCreate(&e);
     return err;
+}
+
+// The context of a component that keeps one table per device: the table and
+// the two events that time its launch.
+struct TableCtx {
+    DevBuf table;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+// One timed launch on a held context's table buffer and two events: the host
+// table goes up, launch(device table) enqueues the kernel(s) on s between the
+// events, before_sync() the device-to-host copies, then s is synchronised.
+// *ms is the time between the events, negative where HIP could not tell.
+template <class Row, class Launch, class Hook = hipError_t (*)()>
+atg_status timed_launch(DevBuf &table, hipEvent_t (&ev)[2], const std::vector<Row> &tab,
+                        hipStream_t s, ErrSlot &slot, float *ms, Launch launch,
+                        Hook before_sync = [] { return hipSuccess; })
+{
+    const size_t bytes = sizeof(Row) * tab.size();
+    ATG_HIP_TRY(slot, ensure_events(ev), "hipEventCreate(&e)");
+    ATG_HIP_TRY(slot, table.ensure(bytes), "table.ensure(bytes)");
+    ATG_HIP_TRY(slot, hipMemcpyAsync(table.p, tab.data(), bytes, hipMemcpyHostToDevice, s),
+                "hipMemcpyAsync(table.p, tab.data(), bytes, hipMemcpyHostToDevice, s)");
+    ATG_HIP_TRY(slot, hipEventRecord(ev[0], s), "hipEventRecord(ev[0], s)");
+    launch((const Row *)table.p);
+    ATG_HIP_TRY(slot, hipGetLastError(), "hipGetLastError()");
+    ATG_HIP_TRY(slot, hipEventRecord(ev[1], s), "hipEventRecord(ev[1], s)");
+    ATG_HIP_TRY(slot, before_sync(), "before_sync()");
+    ATG_HIP_TRY(slot, hipStreamSynchronize(s), "hipStreamSynchronize(s)");
+    if (hipEventElapsedTime(ms, ev[0], ev[1]) != hipSuccess)
+        *ms = -1.f;
+    return ATG_OK;
 }
 
 // The head of every entry that takes a device index: the index checked, the

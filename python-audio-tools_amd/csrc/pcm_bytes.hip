@@ -39,19 +39,13 @@
 namespace {
 
 thread_local ErrSlot g_pb_err;
-#define PHIP(expr) ATG_HIP_TRY(g_pb_err, expr, #expr)
 
 constexpr uint32_t kMaxBlocks = 4096;
 
 thread_local StageTimes<1> g_pb_times; // one entry, named after the last call
 thread_local const char *g_pb_name = nullptr;
 
-// per device: the run table and the two events that time a launch
-struct PbCtx {
-    DevBuf runs;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-};
-DeviceContexts<PbCtx> g_ctxs;
+DeviceContexts<TableCtx> g_ctxs; // per device: the run table
 
 template <int B, bool BE, bool SGN, typename T>
 __global__ __launch_bounds__(kPbBlock) void k_pcm_unpack(const uint8_t *__restrict__ bytes,
@@ -189,31 +183,25 @@ atg_status run_device(bool pack, const void *d_bytes, uint64_t bytes_cap, atg_pc
     if (tab.empty())
         return ATG_OK;
     hipStream_t s = (hipStream_t)stream;
-    DeviceContexts<PbCtx>::Held held;
+    DeviceContexts<TableCtx>::Held held;
     if ((st = g_ctxs.hold(d_pcm, g_pb_err, held)) != ATG_OK)
         return st;
-    PbCtx &c = *held;
-    ATG_HIP_TRY(g_pb_err, ensure_events(c.ev), "hipEventCreate(&e)");
-    PHIP(c.runs.ensure(sizeof(PbRun) * tab.size()));
-    PHIP(hipMemcpyAsync(c.runs.p, tab.data(), sizeof(PbRun) * tab.size(), hipMemcpyHostToDevice, s));
-    const Launch l = {pack,
-                      pack ? d_pcm : d_bytes,
-                      const_cast<void *>(pack ? d_bytes : d_pcm),
-                      (const PbRun *)c.runs.p,
-                      (uint32_t)tab.size(),
-                      n_tiles,
-                      s};
-    PHIP(hipEventRecord(c.ev[0], s));
-    launch(l, lay, (atg_pcm_format)format);
-    PHIP(hipGetLastError());
-    PHIP(hipEventRecord(c.ev[1], s));
-    PHIP(hipStreamSynchronize(s));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) {
+    st = timed_launch(held->table, held->ev, tab, s, g_pb_err, &ms, [&](const PbRun *d_runs) {
+        const Launch l = {pack,
+                          pack ? d_pcm : d_bytes,
+                          const_cast<void *>(pack ? d_bytes : d_pcm),
+                          d_runs,
+                          (uint32_t)tab.size(),
+                          n_tiles,
+                          s};
+        launch(l, lay, (atg_pcm_format)format);
+    });
+    if (st == ATG_OK && ms >= 0.f) {
         g_pb_times = {{ms}, 1};
         g_pb_name = pack ? "pack" : "unpack";
     }
-    return ATG_OK;
+    return st;
 }
 
 // the ranges [first, second) the runs cover on one side, merged where they

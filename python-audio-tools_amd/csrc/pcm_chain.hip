@@ -23,32 +23,31 @@
 // batch's tiles form one list, a workgroup takes one, and its row is a binary
 // search over the rows' first tiles (table_search.h).
 //
-// Loads.  The source is addressed in samples from its pointer rounded down to
-// 16 bytes.  The workgroup loads the aligned 16-byte units that cover the
-// tile's input samples -- each holds a sample of the row -- into the LDS as
-// they are, every lane's loads issued before its first LDS write.  A lane then
-// picks the samples of its output samples out of the LDS by address, so the
-// source's phase within a unit never indexes a register, and there is one
-// code path per (input format, output format).
+// Loads (pcm_rows.h, as the store).  The source is addressed in samples from
+// its pointer rounded down to 16 bytes.  The workgroup loads the aligned
+// 16-byte units that cover the tile's input samples -- each holds a sample of
+// the row -- into the LDS as they are, every lane's loads issued before its
+// first LDS write.  A lane then picks the samples of its output samples out
+// of the LDS by address, so the source's phase within a unit never indexes a
+// register, and there is one code path per (input format, output format).
 //
 // Stores.  A lane converts the 8 (int16) or 4 (int32) output samples of one
 // 16-byte non-temporal store, so a wave's store writes 1 KiB without a gap:
 // a row's output starts on a 16-byte boundary and a tile on a multiple of 8
-// samples.  The last group of a row, when short, is written sample by
-// sample, so nothing outside a row's range is written.  The rounds of a tile
-// (two for int16 output, four for int32) are unrolled: the dither byte loads
-// of all of them are in flight together, where a loop serialised them behind
-// the barrier (0.85 -> 0.97 of k_pcm_bps's bytes per second on its own shape,
-// profiles/pcm_chain_bench.json).
+// samples.  The last group of a row, when short, goes sample by sample.  The
+// rounds of a tile (two for int16 output, four for int32) are unrolled: the
+// dither byte loads of all of them are in flight together, where a loop
+// serialised them behind the barrier (0.85 -> 0.97 of k_pcm_bps's bytes per
+// second on its own shape, profiles/pcm_chain_bench.json).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 #include <vector>
 
 #include "../../include/atgpu.h"
 #include "host_common.h"
+#include "pcm_rows.h"
 #include "table_search.h"
 
 #pragma clang fp contract(off)
@@ -56,7 +55,6 @@
 namespace {
 
 thread_local ErrSlot g_ch_err;
-#define CHIP(expr) ATG_HIP_TRY(g_ch_err, expr, #expr)
 
 constexpr uint32_t kTile = 4096; // samples of a tile, on its wider side
 constexpr uint32_t kBlock = 256;
@@ -69,8 +67,7 @@ const char *const kStageNames[1] = {"chain"};
 thread_local StageTimes<1> g_ch_times;
 
 struct ChainRow {
-    const void *p;    // the source's pointer rounded down to 16 bytes
-    uint64_t lo;      // index from p of the source's first sample
+    PcmSplit src;     // the source: its aligned pointer and first sample
     uint64_t frames;
     uint64_t out0;    // index in the output of the row's first sample
     uint64_t tile0;   // the row's first tile in the batch's list
@@ -82,39 +79,9 @@ struct ChainRow {
     uint8_t in_bps, out_bps, pad[2];
 };
 
-struct ChainCtx {
-    DevBuf rows;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-};
-DeviceContexts<ChainCtx> g_ctxs;
-
-typedef unsigned int Unit __attribute__((ext_vector_type(4))); // 16 bytes
-typedef const __attribute__((address_space(1))) Unit *Units;   // in global memory
+DeviceContexts<TableCtx> g_ctxs;
 
 constexpr uint32_t kLdsUnits = kTile / 4 + 1; // int32 input at any phase
-
-// The aligned units [u0, u0 + nu) of the source into the LDS.  A lane has
-// all its loads in flight before the first LDS write; the one unit an odd
-// phase adds goes through lane 0.
-template <int FIN>
-__device__ __forceinline__ void stage(const void *p, uint64_t u0, uint32_t nu, Unit *lds)
-{
-    constexpr int kDeep = (FIN == ATG_PCM_S32 ? kTile / 4 : kTile / 8) / kBlock;
-    Unit v[kDeep];
-#pragma unroll
-    for (int d = 0; d < kDeep; ++d) {
-        const uint32_t j = threadIdx.x + d * kBlock;
-        v[d] = j < nu ? ((Units)p)[u0 + j] : Unit{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int d = 0; d < kDeep; ++d) {
-        const uint32_t j = threadIdx.x + d * kBlock;
-        if (j < nu)
-            lds[j] = v[d];
-    }
-    if (threadIdx.x == 0 && nu > kDeep * kBlock)
-        lds[kDeep * kBlock] = ((Units)p)[u0 + kDeep * kBlock];
-}
 
 // sample i of the staged units
 template <int FIN> __device__ __forceinline__ int32_t staged(const Unit *lds, uint32_t i)
@@ -173,9 +140,7 @@ __device__ __forceinline__ void convert_tile(const ChainRow &R, uint64_t fa, uin
                                              uint32_t skew, const Unit *lds, void *out,
                                              const uint8_t *__restrict__ dither)
 {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    // a lane takes the G output samples of one 16-byte store, so every store
-    // instruction of a wave writes 1 KiB without a gap
+    // a lane takes the G output samples of one 16-byte store (pcm_store_group)
     constexpr int G = FOUT == ATG_PCM_S16 ? 8 : 4;
     const uint32_t ic = R.ic, oc = R.oc, nf = (uint32_t)(fb - fa);
     const uint32_t n_out = nf * oc;
@@ -261,30 +226,7 @@ __device__ __forceinline__ void convert_tile(const ChainRow &R, uint64_t fa, uin
                 }
             }
         }
-        // ---- the store
-        if (q + G <= n_out) {
-            v4i w;
-            if constexpr (FOUT == ATG_PCM_S16) {
-                w.x = (x[0] & 0xFFFF) | (int)((uint32_t)x[1] << 16);
-                w.y = (x[2] & 0xFFFF) | (int)((uint32_t)x[3] << 16);
-                w.z = (x[4] & 0xFFFF) | (int)((uint32_t)x[5] << 16);
-                w.w = (x[6] & 0xFFFF) | (int)((uint32_t)x[7] << 16);
-                __builtin_nontemporal_store(w, (v4i *)((int16_t *)out + o0 + q));
-            } else {
-                w = v4i{x[0], x[1], x[2], x[3]};
-                __builtin_nontemporal_store(w, (v4i *)((int32_t *)out + o0 + q));
-            }
-        } else {
-            // the row's last, short group
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-                if (q + j < n_out) {
-                    if (FOUT == ATG_PCM_S16)
-                        ((int16_t *)out)[o0 + q + j] = (int16_t)x[j];
-                    else
-                        ((int32_t *)out)[o0 + q + j] = x[j];
-                }
-        }
+        pcm_store_group<FOUT>(x, out, o0, q, n_out);
     }
 }
 
@@ -293,12 +235,11 @@ __device__ __forceinline__ void run_tile(const ChainRow &R, uint64_t fa, uint64_
                                          void *out, const uint8_t *__restrict__ dither)
 {
     constexpr uint32_t kPer = FIN == ATG_PCM_S32 ? 4 : 8;
-    const uint64_t a = R.lo + fa * R.ic, b = R.lo + fb * R.ic; // b > a
-    const uint64_t u0 = a / kPer;
-    const uint32_t nu = (uint32_t)((b - 1) / kPer + 1 - u0);
-    stage<FIN>(R.p, u0, nu, lds);
+    const PcmUnits u = pcm_units(R.src.lo, fa, (uint32_t)(fb - fa), R.ic, kPer);
+    pcm_load_units<kTile / kPer / kBlock, kBlock>(R.src.p, u.u0, u.nu,
+                                                  [lds](Unit v, uint32_t j) { lds[j] = v; });
     __syncthreads();
-    convert_tile<FIN, FOUT>(R, fa, fb, (uint32_t)(a - u0 * kPer), lds, out, dither);
+    convert_tile<FIN, FOUT>(R, fa, fb, u.skew, lds, out, dither);
 }
 
 template <int FOUT>
@@ -332,8 +273,6 @@ uint32_t default_mask(uint32_t ch)
 uint32_t tile_frames_of(uint32_t ic, uint32_t oc) { return 8u * (kTile / (8u * std::max(ic, oc))); }
 
 bool reduces(const atg_pcm_chain_row &r) { return r.out_bps < r.in_bps; }
-
-std::string at_row(uint32_t i, const char *what) { return "row " + std::to_string(i) + ": " + what; }
 
 // every refusal, before any GPU call
 atg_status check_args(const atg_pcm_chain_row *rows, uint32_t n, const void *d_out,
@@ -387,15 +326,8 @@ atg_status check_args(const atg_pcm_chain_row *rows, uint32_t n, const void *d_o
             return g_ch_err.fail(ATG_ERR_INVALID,
                                  at_row(i, "S16 output with more than 16 bits per sample"));
         const atg_pcm_view &v = r.src;
-        if (v.format != ATG_PCM_S16 && v.format != ATG_PCM_S32)
-            return g_ch_err.fail(ATG_ERR_INVALID, at_row(i, "unknown source format"));
-        if (v.window_offset != 0)
-            return g_ch_err.fail(ATG_ERR_INVALID, at_row(i, "window_offset must be 0"));
-        if (v.src_frames && !v.d_pcm)
-            return g_ch_err.fail(ATG_ERR_INVALID, at_row(i, "d_pcm is NULL with src_frames > 0"));
-        if ((uintptr_t)v.d_pcm & (v.format == ATG_PCM_S32 ? 3u : 1u))
-            return g_ch_err.fail(ATG_ERR_INVALID,
-                                 at_row(i, "d_pcm is not aligned to its sample size"));
+        if (const atg_status st = pcm_check_view(g_ch_err, i, v))
+            return st;
         if (v.src_frames >= kLimit / kMaxChannels || v.sample_offset >= kLimit ||
             r.out_offset >= kLimit || r.dither_bit0 >= kLimit)
             return g_ch_err.fail(ATG_ERR_INVALID, at_row(i, "a size or offset is 2^59 or more"));
@@ -422,29 +354,22 @@ atg_status check_args(const atg_pcm_chain_row *rows, uint32_t n, const void *d_o
         return g_ch_err.fail(ATG_ERR_INVALID, "d_out is not 16-byte aligned");
     if (any_dither && !d_dither)
         return g_ch_err.fail(ATG_ERR_INVALID, "d_dither is NULL with a row that reduces bits");
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); ++k)
-        if (ranges[k].first < ranges[k - 1].second)
-            return g_ch_err.fail(ATG_ERR_INVALID, "output rows overlap");
+    if (pcm_ranges_overlap(ranges))
+        return g_ch_err.fail(ATG_ERR_INVALID, "output rows overlap");
     return ATG_OK;
 }
 
-// the device table of the rows that have output; *n_tiles its tiles
-void plan(const atg_pcm_chain_row *rows, uint32_t n, std::vector<ChainRow> &tab,
-          uint64_t *n_tiles)
+// the device table of the rows that have output
+void plan(const atg_pcm_chain_row *rows, uint32_t n, PcmRowTable<ChainRow> &tab)
 {
-    uint64_t tiles = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const atg_pcm_chain_row &r = rows[i];
         if (!r.src.src_frames)
             continue;
         ChainRow c = {};
-        const uintptr_t addr = (uintptr_t)r.src.d_pcm;
-        c.p = (const void *)(addr & ~(uintptr_t)15);
-        c.lo = (addr & 15u) / (r.src.format == ATG_PCM_S32 ? 4 : 2) + r.src.sample_offset;
+        c.src = pcm_split(r.src);
         c.frames = r.src.src_frames;
         c.out0 = r.out_offset;
-        c.tile0 = tiles;
         c.bit0 = r.dither_bit0;
         c.tile_frames = tile_frames_of(r.in_channels, r.out_channels);
         c.mask = (r.channel_mask ? r.channel_mask : default_mask(r.in_channels)) & 0x3Fu;
@@ -466,10 +391,8 @@ void plan(const atg_pcm_chain_row *rows, uint32_t n, std::vector<ChainRow> &tab,
         c.fmt = (uint8_t)r.src.format;
         c.in_bps = (uint8_t)r.in_bps;
         c.out_bps = (uint8_t)r.out_bps;
-        tiles += (c.frames + c.tile_frames - 1) / c.tile_frames;
-        tab.push_back(c);
+        tab.add(c, (c.frames + c.tile_frames - 1) / c.tile_frames);
     }
-    *n_tiles = tiles;
 }
 
 } // namespace
@@ -488,35 +411,27 @@ atg_status atg_pcm_chain_device(const atg_pcm_chain_row *rows, uint32_t n_rows, 
                                dither_bytes);
     if (st != ATG_OK)
         return st;
-    std::vector<ChainRow> tab;
-    uint64_t n_tiles = 0;
-    plan(rows, n_rows, tab, &n_tiles);
-    if (tab.empty())
+    PcmRowTable<ChainRow> tab;
+    plan(rows, n_rows, tab);
+    if (tab.rows.empty())
         return ATG_OK;
-    if (n_tiles > 0x7FFFFFFFull)
-        return g_ch_err.fail(ATG_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles in one call");
-    DeviceContexts<ChainCtx>::Held held; // the device that holds the output
+    if ((st = tab.check(g_ch_err)) != ATG_OK)
+        return st;
+    DeviceContexts<TableCtx>::Held held; // the device that holds the output
     if ((st = g_ctxs.hold(d_out, g_ch_err, held)) != ATG_OK)
         return st;
-    ChainCtx &c = *held;
-    ATG_HIP_TRY(g_ch_err, ensure_events(c.ev), "hipEventCreate(&e)");
     hipStream_t s = (hipStream_t)stream;
-    CHIP(c.rows.ensure(sizeof(ChainRow) * tab.size()));
-    CHIP(hipMemcpyAsync(c.rows.p, tab.data(), sizeof(ChainRow) * tab.size(),
-                        hipMemcpyHostToDevice, s));
-    CHIP(hipEventRecord(c.ev[0], s));
-    if (out_format == ATG_PCM_S16)
-        hipLaunchKernelGGL(k_pcm_chain<ATG_PCM_S16>, dim3((uint32_t)n_tiles), dim3(kBlock), 0, s,
-                           (const ChainRow *)c.rows.p, (uint32_t)tab.size(), d_out, d_dither);
-    else
-        hipLaunchKernelGGL(k_pcm_chain<ATG_PCM_S32>, dim3((uint32_t)n_tiles), dim3(kBlock), 0, s,
-                           (const ChainRow *)c.rows.p, (uint32_t)tab.size(), d_out, d_dither);
-    CHIP(hipGetLastError());
-    CHIP(hipEventRecord(c.ev[1], s));
-    CHIP(hipStreamSynchronize(s));
-    g_ch_times = {};
-    g_ch_times.n = hipEventElapsedTime(&g_ch_times.ms[0], c.ev[0], c.ev[1]) == hipSuccess;
-    return ATG_OK;
+    const auto kernel =
+        out_format == ATG_PCM_S16 ? k_pcm_chain<ATG_PCM_S16> : k_pcm_chain<ATG_PCM_S32>;
+    const auto launch = [&](const ChainRow *d_rows) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)tab.tiles), dim3(kBlock), 0, s, d_rows,
+                           (uint32_t)tab.rows.size(), d_out, d_dither);
+    };
+    float ms = 0.f;
+    st = timed_launch(held->table, held->ev, tab.rows, s, g_ch_err, &ms, launch);
+    if (st == ATG_OK)
+        g_ch_times = {{ms}, ms >= 0.f};
+    return st;
 }
 
 atg_status atg_pcm_chain_host(int device, const atg_pcm_chain_row *rows, uint32_t n_rows,

@@ -17,7 +17,7 @@
 // accuraterip.hip finds a tile's track).
 //
 // Alignment.  Both buffers are addressed in samples from their pointer
-// rounded down to 16 bytes.  A lane takes 8 consecutive samples whose A index
+// rounded down to 16 bytes (pcm_rows.h).  A lane takes 8 consecutive samples whose A index
 // is a multiple of 8, so A is one (int16) or two (int32) aligned 16-byte
 // loads.  The same 8 samples of B start at any index: the lane loads the two
 // (int16) or three (int32) aligned units that cover them.  B's phase within
@@ -54,6 +54,7 @@
 
 #include "../../include/atgpu.h"
 #include "host_common.h"
+#include "pcm_rows.h"
 #include "table_search.h"
 #include "wave.h"
 
@@ -108,9 +109,6 @@ struct CmpCtx {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 DeviceContexts<CmpCtx> g_ctxs;
-
-typedef unsigned int Unit __attribute__((ext_vector_type(4)));  // 16 bytes
-typedef const __attribute__((address_space(1))) Unit *Units; // in global memory
 
 // The 8 samples at indices idx .. idx + 7 of a view's buffer, as the aligned
 // 16-byte units that cover them.  PH is idx modulo the samples of a unit (4
@@ -361,15 +359,13 @@ __global__ __launch_bounds__(kBlock) void k_pcm_probe(const ProbeJob *__restrict
 
 // ---------------------------------------------------------------- host side
 
-bool known_format(uint32_t f) { return f == ATG_PCM_S16 || f == ATG_PCM_S32; }
-
 atg_status check_view(const atg_pcm_view &v, uint32_t channels)
 {
-    if (!known_format(v.format))
+    if (!pcm_known_format(v.format))
         return g_pc_err.fail(ATG_ERR_INVALID, "unknown PCM format");
     if (v.src_frames && !v.d_pcm)
         return g_pc_err.fail(ATG_ERR_INVALID, "d_pcm is NULL with src_frames > 0");
-    if ((uintptr_t)v.d_pcm & (v.format == ATG_PCM_S32 ? 3u : 1u))
+    if (pcm_misaligned(v))
         return g_pc_err.fail(ATG_ERR_INVALID, "d_pcm is not aligned to its sample size");
     if (v.src_frames > (kLimit - 1) / channels)
         return g_pc_err.fail(ATG_ERR_INVALID, "src_frames * channels is 2^62 or more");
@@ -413,10 +409,9 @@ CmpView plan_view(const atg_pcm_view &v, long long shift, uint64_t frames, uint3
     const long long wo = v.window_offset + shift;
     if (!v.src_frames || wo >= (long long)v.src_frames || wo + (long long)frames <= 0)
         return o;
-    const uintptr_t addr = (uintptr_t)v.d_pcm;
-    const long long skew = (long long)((addr & 15u) / (v.format == ATG_PCM_S32 ? 4 : 2));
-    o.p = (const void *)(addr & ~(uintptr_t)15);
-    o.lo = skew + (long long)v.sample_offset;
+    const PcmSplit src = pcm_split(v);
+    o.p = src.p;
+    o.lo = (long long)src.lo;
     o.hi = o.lo + (long long)(v.src_frames * channels);
     o.base = o.lo + wo * (long long)channels;
     return o;
@@ -464,24 +459,22 @@ atg_status run_compare(CmpCtx &c, std::vector<CmpPair> &tab, uint32_t n_slots,
         p.rest0 = n_tiles - tab.size();
         n_tiles += (p.n / p.channels + kTile - 1) / kTile - 1;
     }
-    CHIP(c.pairs.ensure(sizeof(CmpPair) * tab.size()));
     CHIP(c.first.ensure(sizeof(uint64_t) * n_slots));
-    CHIP(hipMemcpyAsync(c.pairs.p, tab.data(), sizeof(CmpPair) * tab.size(),
-                        hipMemcpyHostToDevice, s));
     CHIP(hipMemsetAsync(c.first.p, 0xFF, sizeof(uint64_t) * n_slots, s));
-    CHIP(hipEventRecord(c.ev[0], s));
-    hipLaunchKernelGGL(k_pcm_compare, dim3((uint32_t)std::min<uint64_t>(n_tiles, kMaxBlocks)),
-                       dim3(kBlock), 0, s, (const CmpPair *)c.pairs.p, (uint32_t)tab.size(),
-                       n_tiles, (unsigned long long *)c.first.p);
-    CHIP(hipGetLastError());
-    CHIP(hipEventRecord(c.ev[1], s));
-    CHIP(hipMemcpyAsync(out.data(), c.first.p, sizeof(uint64_t) * n_slots, hipMemcpyDeviceToHost,
-                        s));
-    CHIP(hipStreamSynchronize(s));
+    const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, kMaxBlocks));
+    const auto launch = [&](const CmpPair *d_pairs) {
+        hipLaunchKernelGGL(k_pcm_compare, grid, dim3(kBlock), 0, s, d_pairs, (uint32_t)tab.size(),
+                           n_tiles, (unsigned long long *)c.first.p);
+    };
+    const auto fetch = [&] {
+        return hipMemcpyAsync(out.data(), c.first.p, sizeof(uint64_t) * n_slots,
+                              hipMemcpyDeviceToHost, s);
+    };
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess)
+    const atg_status st = timed_launch(c.pairs, c.ev, tab, s, g_pc_err, &ms, launch, fetch);
+    if (st == ATG_OK && ms >= 0.f)
         g_pc_times.ms[0] += ms;
-    return ATG_OK;
+    return st;
 }
 
 // the r-th shift in order of |k|, +k before -k: 0, 1, -1, 2, -2, ...
@@ -549,24 +542,23 @@ atg_status search(const atg_pcm_pair *pairs, uint32_t n, uint32_t K, atg_pcm_cmp
     }
     if (!jobs.empty()) {
         std::vector<uint64_t> got((size_t)jobs.size() * words);
-        CHIP(c.jobs.ensure(sizeof(ProbeJob) * jobs.size()));
         CHIP(c.bits.ensure(sizeof(uint64_t) * got.size()));
-        CHIP(hipMemcpyAsync(c.jobs.p, jobs.data(), sizeof(ProbeJob) * jobs.size(),
-                            hipMemcpyHostToDevice, s));
-        CHIP(hipEventRecord(c.ev[0], s));
-        for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535) {
-            const uint32_t nj = (uint32_t)std::min<size_t>(65535, jobs.size() - j0);
-            hipLaunchKernelGGL(k_pcm_probe, dim3((width + kBlock - 1) / kBlock, nj), dim3(kBlock),
-                               0, s, (const ProbeJob *)c.jobs.p + j0, K, words,
-                               (unsigned long long *)c.bits.p + j0 * words);
-        }
-        CHIP(hipGetLastError());
-        CHIP(hipEventRecord(c.ev[1], s));
-        CHIP(hipMemcpyAsync(got.data(), c.bits.p, sizeof(uint64_t) * got.size(),
-                            hipMemcpyDeviceToHost, s));
-        CHIP(hipStreamSynchronize(s));
+        const auto launch = [&](const ProbeJob *d_jobs) {
+            for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535) {
+                const uint32_t nj = (uint32_t)std::min<size_t>(65535, jobs.size() - j0);
+                hipLaunchKernelGGL(k_pcm_probe, dim3((width + kBlock - 1) / kBlock, nj),
+                                   dim3(kBlock), 0, s, d_jobs + j0, K, words,
+                                   (unsigned long long *)c.bits.p + j0 * words);
+            }
+        };
+        const auto fetch = [&] {
+            return hipMemcpyAsync(got.data(), c.bits.p, sizeof(uint64_t) * got.size(),
+                                  hipMemcpyDeviceToHost, s);
+        };
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess)
+        if ((st = timed_launch(c.jobs, c.ev, jobs, s, g_pc_err, &ms, launch, fetch)) != ATG_OK)
+            return st;
+        if (ms >= 0.f)
             g_pc_times.ms[1] += ms;
         for (uint32_t o = 0; o < open.size(); ++o)
             if (job_of[o] != UINT32_MAX)
@@ -648,7 +640,6 @@ atg_status run(const atg_pcm_pair *pairs, uint32_t n, uint32_t max_offset, bool 
     if ((st = g_ctxs.hold(first_pcm(pairs, n), g_pc_err, held)) != ATG_OK)
         return st;
     CmpCtx &c = *held;
-    ATG_HIP_TRY(g_pc_err, ensure_events(c.ev), "hipEventCreate(&e)");
     g_pc_times = {{0.f, 0.f}, 2};
     if (want_offset)
         return search(pairs, n, max_offset, results, c, s);

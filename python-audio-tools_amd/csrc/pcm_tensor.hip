@@ -36,17 +36,17 @@
 // Ends.  A run may start at any element.  A group that lies whole inside the
 // tile's part of the run is one 16-byte access; the first and last group of a
 // tile, when they are not, go element by element, so nothing outside a run is
-// read or written.  The PCM side follows pcm_chain.hip: aligned 16-byte units
-// that hold a sample of the row, the last short group sample by sample.
+// read or written.  The PCM side is pcm_rows.h's: aligned 16-byte units that
+// hold a sample of the row, the last short group sample by sample.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
 
 #include "../../include/atgpu.h"
 #include "host_common.h"
+#include "pcm_rows.h"
 #include "table_search.h"
 
 #pragma clang fp contract(off)
@@ -54,7 +54,6 @@
 namespace {
 
 thread_local ErrSlot g_pt_err;
-#define THIP(expr) ATG_HIP_TRY(g_pt_err, expr, #expr)
 
 constexpr uint32_t kTileFrames = 1024;
 constexpr uint32_t kBlock = 256;
@@ -71,8 +70,7 @@ thread_local StageTimes<1> g_pt_times;
 thread_local int g_pt_which = 0;
 
 struct ToRow {
-    const void *p;    // the source's pointer rounded down to 16 bytes
-    uint64_t lo;      // index from p of the source's first sample
+    PcmSplit src;     // the source: its aligned pointer and first sample
     uint64_t frames, pad;
     uint64_t e0;      // element index, from the aligned output base, of channel 0's run
     uint64_t cstride;
@@ -88,14 +86,7 @@ struct FromRow {
     uint8_t ch, bps, reserved[6];
 };
 
-struct TensorCtx {
-    DevBuf rows;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-};
-DeviceContexts<TensorCtx> g_ctxs;
-
-typedef unsigned int Unit __attribute__((ext_vector_type(4))); // 16 bytes
-typedef const __attribute__((address_space(1))) Unit *Units;   // in global memory
+DeviceContexts<TableCtx> g_ctxs;
 
 template <int DT> struct Elem;
 template <> struct Elem<ATG_TENSOR_F16> { typedef _Float16 T; };
@@ -184,34 +175,18 @@ __device__ __forceinline__ void scatter(Unit v, uint32_t j, uint32_t skew, uint3
 }
 
 // The aligned units that cover source frames [fa, fa + n_src) of the row,
-// every lane's loads issued before its first LDS write (pcm_chain.hip's
-// stage); the one unit an odd phase adds goes through lane 0.
+// scattered into the planes.
 template <int FIN, uint32_t G>
 __device__ __forceinline__ void stage(const ToRow &R, uint64_t fa, uint32_t n_src, uint32_t e_lo,
                                       uint32_t cs_lo, int32_t *lds)
 {
     constexpr uint32_t kPer = FIN == ATG_PCM_S32 ? 4 : 8;
-    constexpr int kDeep = kTileFrames * kMaxChannels / kPer / kBlock;
     const uint32_t ch = R.ch;
-    const uint64_t a = R.lo + fa * ch, b = a + (uint64_t)n_src * ch; // b > a
-    const uint64_t u0 = a / kPer;
-    const uint32_t nu = (uint32_t)((b - 1) / kPer + 1 - u0);
-    const uint32_t skew = (uint32_t)(a - u0 * kPer);
-    Unit v[kDeep];
-#pragma unroll
-    for (int d = 0; d < kDeep; ++d) {
-        const uint32_t j = threadIdx.x + d * kBlock;
-        v[d] = j < nu ? ((Units)R.p)[u0 + j] : Unit{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int d = 0; d < kDeep; ++d) {
-        const uint32_t j = threadIdx.x + d * kBlock;
-        if (j < nu)
-            scatter<FIN, G>(v[d], j, skew, ch, n_src, e_lo, cs_lo, lds);
-    }
-    if (threadIdx.x == 0 && nu > kDeep * kBlock)
-        scatter<FIN, G>(((Units)R.p)[u0 + kDeep * kBlock], kDeep * kBlock, skew, ch, n_src, e_lo,
-                        cs_lo, lds);
+    const PcmUnits u = pcm_units(R.src.lo, fa, n_src, ch, kPer);
+    pcm_load_units<kTileFrames * kMaxChannels / kPer / kBlock, kBlock>(
+        R.src.p, u.u0, u.nu, [=](Unit v, uint32_t j) {
+            scatter<FIN, G>(v, j, u.skew, ch, n_src, e_lo, cs_lo, lds);
+        });
 }
 
 template <int DT>
@@ -278,7 +253,6 @@ __global__ __launch_bounds__(kBlock) void k_pcm_from_tensor(const FromRow *__res
     constexpr uint32_t kGroups = kTileFrames / G + 1;
     typedef T Vec __attribute__((ext_vector_type(G)));
     typedef int32_t IVec __attribute__((ext_vector_type(G)));
-    typedef int v4i __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) int32_t lds[];
 
     const uint64_t tile = blockIdx.x;
@@ -331,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_pcm_from_tensor(const FromRow *__res
         }
     }
     __syncthreads();
-    // a lane interleaves the samples of one 16-byte store (pcm_chain.hip)
+    // a lane interleaves the samples of one 16-byte store (pcm_store_group)
     constexpr uint32_t GO = FOUT == ATG_PCM_S16 ? 8 : 4;
     const uint32_t n_out = nf * ch;
     const uint64_t o0 = R.out0 + fa * ch; // a multiple of 8 past the row's start
@@ -346,35 +320,11 @@ __global__ __launch_bounds__(kBlock) void k_pcm_from_tensor(const FromRow *__res
                 ++f;
             }
         }
-        if (q + GO <= n_out) {
-            v4i w;
-            if constexpr (FOUT == ATG_PCM_S16) {
-                w.x = (x[0] & 0xFFFF) | (int)((uint32_t)x[1] << 16);
-                w.y = (x[2] & 0xFFFF) | (int)((uint32_t)x[3] << 16);
-                w.z = (x[4] & 0xFFFF) | (int)((uint32_t)x[5] << 16);
-                w.w = (x[6] & 0xFFFF) | (int)((uint32_t)x[7] << 16);
-                __builtin_nontemporal_store(w, (v4i *)((int16_t *)out + o0 + q));
-            } else {
-                w = v4i{x[0], x[1], x[2], x[3]};
-                __builtin_nontemporal_store(w, (v4i *)((int32_t *)out + o0 + q));
-            }
-        } else {
-            // the row's last, short group
-#pragma unroll
-            for (uint32_t j = 0; j < GO; ++j)
-                if (q + j < n_out) {
-                    if (FOUT == ATG_PCM_S16)
-                        ((int16_t *)out)[o0 + q + j] = (int16_t)x[j];
-                    else
-                        ((int32_t *)out)[o0 + q + j] = x[j];
-                }
-        }
+        pcm_store_group<FOUT>(x, out, o0, q, n_out);
     }
 }
 
 // ---------------------------------------------------------------- host side
-
-std::string at_row(uint32_t i, const char *what) { return "row " + std::to_string(i) + ": " + what; }
 
 uint32_t elem_size(int dtype)
 {
@@ -388,15 +338,6 @@ uint32_t elem_size(int dtype)
         return 8;
     }
     return 0;
-}
-
-bool overlap(std::vector<std::pair<uint64_t, uint64_t>> &ranges)
-{
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); ++k)
-        if (ranges[k].first < ranges[k - 1].second)
-            return true;
-    return false;
 }
 
 // every refusal of atg_pcm_to_tensor_device, before any GPU call
@@ -419,15 +360,8 @@ atg_status check_to(const atg_pcm_to_tensor_row *rows, uint32_t n, const void *d
             return g_pt_err.fail(ATG_ERR_INVALID, at_row(i, "channel count outside 1..8"));
         if (r.bits_per_sample < 1 || r.bits_per_sample > 24)
             return g_pt_err.fail(ATG_ERR_INVALID, at_row(i, "bits per sample outside 1..24"));
-        if (v.format != ATG_PCM_S16 && v.format != ATG_PCM_S32)
-            return g_pt_err.fail(ATG_ERR_INVALID, at_row(i, "unknown source format"));
-        if (v.window_offset != 0)
-            return g_pt_err.fail(ATG_ERR_INVALID, at_row(i, "window_offset must be 0"));
-        if (v.src_frames && !v.d_pcm)
-            return g_pt_err.fail(ATG_ERR_INVALID, at_row(i, "d_pcm is NULL with src_frames > 0"));
-        if ((uintptr_t)v.d_pcm & (v.format == ATG_PCM_S32 ? 3u : 1u))
-            return g_pt_err.fail(ATG_ERR_INVALID,
-                                 at_row(i, "d_pcm is not aligned to its sample size"));
+        if (const atg_status st = pcm_check_view(g_pt_err, i, v))
+            return st;
         if (v.src_frames >= kLimit / kMaxChannels || v.sample_offset >= kLimit ||
             r.pad_frames >= kLimit / kMaxChannels || r.out_offset >= kLimit ||
             r.channel_stride >= kLimit / kMaxChannels)
@@ -448,7 +382,7 @@ atg_status check_to(const atg_pcm_to_tensor_row *rows, uint32_t n, const void *d
     }
     if (any && !d_out)
         return g_pt_err.fail(ATG_ERR_INVALID, "d_out is NULL");
-    if (overlap(ranges))
+    if (pcm_ranges_overlap(ranges))
         return g_pt_err.fail(ATG_ERR_INVALID, "channel runs overlap");
     return ATG_OK;
 }
@@ -502,34 +436,29 @@ atg_status check_from(const atg_pcm_from_tensor_row *rows, uint32_t n, const voi
         return g_pt_err.fail(ATG_ERR_INVALID, "d_in is NULL");
     if (any && !d_out)
         return g_pt_err.fail(ATG_ERR_INVALID, "d_out is NULL");
-    if (overlap(ranges))
+    if (pcm_ranges_overlap(ranges))
         return g_pt_err.fail(ATG_ERR_INVALID, "output rows overlap");
     return ATG_OK;
 }
 
-// Upload the table, launch between the context's two events, synchronise,
-// keep the time.  `launch` enqueues the kernel on s over the device table.
+// the table's one timed launch, on the device that holds the tensor, d_where
 template <class Row, class Launch>
-atg_status run(const void *d_where, const std::vector<Row> &tab, hipStream_t s, int which,
+atg_status run(const void *d_where, const PcmRowTable<Row> &tab, hipStream_t s, int which,
                Launch launch)
 {
-    DeviceContexts<TensorCtx>::Held held; // the device that holds the tensor
-    atg_status st = g_ctxs.hold(d_where, g_pt_err, held);
-    if (st != ATG_OK)
+    if (tab.rows.empty())
+        return ATG_OK;
+    DeviceContexts<TableCtx>::Held held;
+    atg_status st = tab.check(g_pt_err);
+    if (st != ATG_OK || (st = g_ctxs.hold(d_where, g_pt_err, held)) != ATG_OK)
         return st;
-    TensorCtx &c = *held;
-    ATG_HIP_TRY(g_pt_err, ensure_events(c.ev), "hipEventCreate(&e)");
-    THIP(c.rows.ensure(sizeof(Row) * tab.size()));
-    THIP(hipMemcpyAsync(c.rows.p, tab.data(), sizeof(Row) * tab.size(), hipMemcpyHostToDevice, s));
-    THIP(hipEventRecord(c.ev[0], s));
-    launch((const Row *)c.rows.p);
-    THIP(hipGetLastError());
-    THIP(hipEventRecord(c.ev[1], s));
-    THIP(hipStreamSynchronize(s));
-    g_pt_times = {};
-    g_pt_times.n = hipEventElapsedTime(&g_pt_times.ms[0], c.ev[0], c.ev[1]) == hipSuccess;
-    g_pt_which = which;
-    return ATG_OK;
+    float ms = 0.f;
+    st = timed_launch(held->table, held->ev, tab.rows, s, g_pt_err, &ms, launch);
+    if (st == ATG_OK) {
+        g_pt_times = {{ms}, ms >= 0.f};
+        g_pt_which = which;
+    }
+    return st;
 }
 
 } // namespace
@@ -551,37 +480,28 @@ atg_status atg_pcm_to_tensor_device(const atg_pcm_to_tensor_row *rows, uint32_t 
     const uint32_t size = elem_size((int)dtype);
     const uintptr_t base = (uintptr_t)d_out & ~(uintptr_t)15;
     const uint64_t extra = ((uintptr_t)d_out & 15u) / size;
-    std::vector<ToRow> tab;
-    uint64_t tiles = 0;
+    PcmRowTable<ToRow> tab;
     uint32_t max_ch = 0;
     for (uint32_t i = 0; i < n_rows; ++i) {
         const atg_pcm_to_tensor_row &r = rows[i];
         if (!r.pad_frames)
             continue;
         ToRow t = {};
-        const uintptr_t addr = (uintptr_t)r.src.d_pcm;
-        t.p = (const void *)(addr & ~(uintptr_t)15);
-        t.lo = (addr & 15u) / (r.src.format == ATG_PCM_S32 ? 4 : 2) + r.src.sample_offset;
+        t.src = pcm_split(r.src);
         t.frames = r.src.src_frames;
         t.pad = r.pad_frames;
         t.e0 = extra + r.out_offset;
         t.cstride = r.channel_stride;
-        t.tile0 = tiles;
         t.ch = (uint8_t)r.channels;
         t.bps = (uint8_t)r.bits_per_sample;
         t.fmt = (uint8_t)r.src.format;
-        tiles += (t.pad + kTileFrames - 1) / kTileFrames;
         max_ch = std::max(max_ch, r.channels);
-        tab.push_back(t);
+        tab.add(t, (t.pad + kTileFrames - 1) / kTileFrames);
     }
-    if (tab.empty())
-        return ATG_OK;
-    if (tiles > 0x7FFFFFFFull)
-        return g_pt_err.fail(ATG_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles in one call");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((uint32_t)tiles), block(kBlock);
+    const dim3 grid((uint32_t)tab.tiles), block(kBlock);
     const size_t lds = sizeof(int32_t) * kPlane * max_ch;
-    const uint32_t n = (uint32_t)tab.size();
+    const uint32_t n = (uint32_t)tab.rows.size();
     void *out = (void *)base;
     return run(d_out, tab, s, 0, [&](const ToRow *d_rows) {
         switch ((int)dtype) {
@@ -613,8 +533,7 @@ atg_status atg_pcm_from_tensor_device(const atg_pcm_from_tensor_row *rows, uint3
     const uint32_t size = elem_size((int)dtype);
     const uintptr_t base = (uintptr_t)d_in & ~(uintptr_t)15;
     const uint64_t extra = ((uintptr_t)d_in & 15u) / size;
-    std::vector<FromRow> tab;
-    uint64_t tiles = 0;
+    PcmRowTable<FromRow> tab;
     uint32_t max_ch = 0;
     for (uint32_t i = 0; i < n_rows; ++i) {
         const atg_pcm_from_tensor_row &r = rows[i];
@@ -625,21 +544,15 @@ atg_status atg_pcm_from_tensor_device(const atg_pcm_from_tensor_row *rows, uint3
         t.cstride = r.channel_stride;
         t.frames = r.frames;
         t.out0 = r.out_offset;
-        t.tile0 = tiles;
         t.ch = (uint8_t)r.channels;
         t.bps = (uint8_t)r.bits_per_sample;
-        tiles += (t.frames + kTileFrames - 1) / kTileFrames;
         max_ch = std::max(max_ch, r.channels);
-        tab.push_back(t);
+        tab.add(t, (t.frames + kTileFrames - 1) / kTileFrames);
     }
-    if (tab.empty())
-        return ATG_OK;
-    if (tiles > 0x7FFFFFFFull)
-        return g_pt_err.fail(ATG_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles in one call");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((uint32_t)tiles), block(kBlock);
+    const dim3 grid((uint32_t)tab.tiles), block(kBlock);
     const size_t lds = sizeof(int32_t) * kPlane * max_ch;
-    const uint32_t n = (uint32_t)tab.size();
+    const uint32_t n = (uint32_t)tab.rows.size();
     const void *in = (const void *)base;
 #define ATG_FROM(DT)                                                                          \
     if (out_format == ATG_PCM_S16)                                                            \

@@ -193,6 +193,18 @@ def test_300_mixed_rows_in_one_call():
     assert set(_atgpu.pcm_tensor_kernel_times()) == {"to_tensor"}
 
 
+def test_full_8_channel_tile_off_a_unit_boundary():
+    """A full tile of 8 channels is as many 16-byte units as the lanes' loads
+    hold; a source that starts inside a unit adds one, which lane 0 loads
+    (pcm_rows.h).  One row per non-zero source phase of either format."""
+    rows = [Row(8, 16 if fmt == S16 else 24, tile() + 1, 0, 0, phase, phase % 4, fmt,
+                by_pointer=bool(phase % 2))
+            for fmt, per in ((S16, 8), (S32, 4)) for phase in range(1, per)]
+    assert len(rows) == 10
+    got, want = run_to_tensor(rows, F32, seed=8)
+    assert np.array_equal(got, want), explain(got, want)
+
+
 # ------------------------------------------------------------- tensor -> PCM
 def elements_of(rng, n, bps, dtype):
     """what the issue lists, then noise: exact k / 2^(b-1), +-(k + 0.5) /
