@@ -1898,6 +1898,8 @@ int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float
 #include "atgpu_mlp.h"
 /* PCM rows to and from planar float tensors */
 #include "atgpu_tensor.h"
+/* the dither bits of a batch conversion, made on the device */
+#include "atgpu_dither.h"
 /* test probes into the encoder's kernels */
 #include "atgpu_probe.h"
 #endif

@@ -17,7 +17,10 @@ find the same names with the same meaning:
   audiotools.convert_files_batch  track2track's per-file convert() for a batch
                                   of files, the PCM on the device throughout
   audiotools.convert_pcm_batch .. PCMConverter for a batch of numpy tracks
-  audiotools.load_batch / save_flac_batch / pcm_to_tensor / tensor_to_pcm
+  audiotools.DeviceDither ....... dither= of the batch paths: the bits made on
+                                  the device, a seeded stream per track
+  audiotools.load_batch / save_flac_batch / save_batch / pcm_to_tensor /
+  tensor_to_pcm
                                   decoded batches as PyTorch tensors and back
                                   (tensors.py; torch is imported on first use)
 
@@ -609,12 +612,12 @@ from .shn import ShortenAudio, InvalidShorten  # noqa: E402,F401
 from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa: E402,F401
                        frame_cmp_value, compare_files_batch, compare_image_batch,
                        find_offset_batch, compare_pcm_batch)
-from .pcmconverter import convert_pcm_batch  # noqa: E402,F401
+from .pcmconverter import DeviceDither, convert_pcm_batch  # noqa: E402,F401
 from .convert import convert_files_batch  # noqa: E402,F401
 
 # the tensor interface (tensors.py) imports torch: its names are looked up on
 # first use, so importing the package does not import torch
-_TENSOR_NAMES = ("pcm_to_tensor", "tensor_to_pcm", "load_batch", "save_flac_batch")
+_TENSOR_NAMES = ("pcm_to_tensor", "tensor_to_pcm", "load_batch", "save_flac_batch", "save_batch")
 
 
 def __getattr__(name):

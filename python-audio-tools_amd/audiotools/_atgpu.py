@@ -807,6 +807,21 @@ TENSOR_SIGNATURES = {
     "atg_pcm_tensor_kernel_times": _THREAD_TIMES,
 }
 
+# ---- device-side dither (include/atgpu_dither.h, included by atgpu.h after atgpu_tensor.h)
+class DitherRun(ctypes.Structure):
+    """atg_dither_run: blocks of one stream to one place of the output"""
+    _fields_ = [("stream", c_u64), ("first_block", c_u64), ("blocks", c_u64),
+                ("byte_offset", c_u64)]
+
+
+# the prototypes of include/atgpu_dither.h, applied by load_library() as well
+DITHER_SIGNATURES = {
+    "atg_dither_last_error": _LAST_ERROR,
+    "atg_dither_fill_device": (c_int, (ptr(DitherRun), c_u32, c_u64, P, c_u64, P)),
+    "atg_dither_tile_blocks": _TILE,
+    "atg_dither_kernel_times": _THREAD_TIMES,
+}
+
 # ---- test probes (include/atgpu_probe.h, included by atgpu.h last)
 PROBE_SIGNATURES = {
     # engine, options, pcm, format, tracks, n, channels, bits, sums, cap, window_n, window
@@ -831,6 +846,7 @@ def load_library():
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(DVDA_SIGNATURES.items()) +
                                           list(MLP_SIGNATURES.items()) +
                                           list(TENSOR_SIGNATURES.items()) +
+                                          list(DITHER_SIGNATURES.items()) +
                                           list(PROBE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -2634,6 +2650,28 @@ def pcm_chain_tile_frames(in_channels, out_channels):
 def pcm_chain_kernel_times():
     """{"chain": ms} of this thread's last launch"""
     return _thread_times(load_library().atg_pcm_chain_kernel_times, 1)
+
+
+# --------------------------------------------------- device-side dither (dither.hip)
+def dither_fill_device(runs, seed, d_out, out_cap, stream=None):
+    """runs: [(stream, first_block, blocks, byte_offset)]; the 16-byte blocks
+    of those streams under `seed` written to d_out in one launch
+    (atg_dither_fill_device)"""
+    lib = load_library()
+    arr = (DitherRun * max(1, len(runs)))(*[DitherRun(*[int(v) for v in r]) for r in runs])
+    _check(lib, lib.atg_dither_fill_device(
+        arr, len(runs), int(seed), ctypes.c_void_p(d_out) if d_out else None, out_cap,
+        ctypes.c_void_p(stream) if stream else None), "dither")
+
+
+def dither_tile_blocks():
+    """16-byte blocks one workgroup of the fill kernel writes"""
+    return int(load_library().atg_dither_tile_blocks())
+
+
+def dither_kernel_times():
+    """{"fill": ms} of this thread's last fill"""
+    return _thread_times(load_library().atg_dither_kernel_times, 1)
 
 
 # ------------------------------------------------------ tensors (pcm_tensor.hip)

@@ -258,6 +258,8 @@ class _Batch(object):
         return _atgpu.pcm_view(d_pcm, _atgpu.PCM_S32, p.frames, p.sample_offset, window_offset)
 
     def close(self):
+        if not self._free:
+            return
         eng = _atgpu.engine()
         for d in self._free:
             eng.device_free(d)

@@ -1,23 +1,24 @@
-"""audiotools.convert — a batch of files transcoded to FLAC on the device.
+"""audiotools.convert — a batch of files transcoded on the device, to FLAC or
+to any other format the engine writes.
 
 convert_files_batch is track2track's job for many files at once: every
 source is opened and told apart by magic (batchfiles), all sources of one
 format are decoded in one call of that format's decoder, the converter chain
 runs over the decoded PCM where it lies (pcmconverter.run_chain_device:
 csrc/pcm_chain.hip on either side of the resampler), the tracks that share
-output parameters are encoded in one encode_device call each, and every
-image is finished as FlacAudio.from_pcm finishes it.  The PCM never comes
-back to the host; the .flac images do.
+output parameters and target type are encoded in one encode_device call each
+(targets.write_tracks), and every image is finished as its class's from_pcm
+finishes it.  The PCM never comes back to the host; the encoded images do.
 """
-
-import numpy as np
 
 from . import DecodingError, EncodingError
 from . import _atgpu
 from .batchfiles import _Batch
-from .flac import (COMPRESSION_PRESETS, DEFAULT_COMPRESSION, FlacAudio, finish_image,
-                   padding_for, target_layout, _unlink)
+from .flac import FlacAudio, finish_image, _unlink
 from .pcmconverter import DevicePcm, plan_target, run_chain_device
+from .shn import ShortenAudio
+from .targets import Track, prepare, resolve_compression, resolve_types, write_tracks
+from .wav import WaveAudio
 
 
 def _frame_offsets(image, total_frames, interval, block_size):
@@ -41,28 +42,41 @@ def _frame_offsets(image, total_frames, interval, block_size):
 
 
 def convert_files_batch(sources, targets, sample_rate=None, channels=None, channel_mask=None,
-                        bits_per_sample=None, compression=None, dither=None):
+                        bits_per_sample=None, compression=None, dither=None, target_types=None):
     """sources[k] (a filename or a bytes image of any supported format) ->
-    the FLAC file targets[k], converted to the target parameters as
-    PCMConverter converts (None keeps each source's own value).  The file is
-    the one FlacAudio.from_pcm(targets[k], PCMConverter(BufferedPCMReader(
-    source.to_pcm()), ...), compression, total_pcm_frames=<converted frames>)
-    writes, except for where the dither bits fall behind a resampler (DESIGN
-    section 4o).  dither: n -> bytes (default os.urandom), drawn source by
-    source in argument order.
-    -> per source a FlacAudio, or the DecodingError / EncodingError instance
-    of a file that could not be read or written (no target is left for it and
-    the others go on).  ValueError, before any GPU work, for a target that
-    PCMConverter refuses."""
+    the file targets[k], converted to the target parameters as PCMConverter
+    converts (None keeps each source's own value).  target_types: None for
+    FLAC, else one value for all targets or one per target -- one of the
+    nine classes FlacAudio, OggFlacAudio, ALACAudio, TrueAudio, WavPackAudio,
+    ShortenAudio, WaveAudio, AiffAudio, AuAudio, one of their SUFFIX strings,
+    or "suffix" for the type each target's file name ends in.  compression:
+    one value or one per target, read against the target class's
+    COMPRESSION_MODES (None or an unknown value: that class's default).
+    The file is the one cls.from_pcm(targets[k], PCMConverter(
+    BufferedPCMReader(source.to_pcm()), ...), compression,
+    total_pcm_frames=<converted frames>) writes (encode_oggflac /
+    encode_wavpack being the encoding function of those two classes), except
+    for where the dither bits fall behind a resampler,
+    an Ogg FLAC stream's random serial number and an .m4a's creation time.
+    dither: n -> bytes (default os.urandom), drawn source by
+    source in argument order; or a DeviceDither, whose stream k makes the
+    bits of sources[k] on the device.
+    -> per source the target class's instance, or the DecodingError /
+    EncodingError instance of a file that could not be read or written (no
+    target is left for it and the others go on); a source whose converted
+    parameters its target type cannot hold gets the exception that type's
+    from_pcm raises, before any GPU work for it.  ValueError, before any GPU
+    work, for a target that PCMConverter refuses, an unknown target type and
+    lists of the wrong length."""
     sources, targets = list(sources), list(targets)
     if len(sources) != len(targets):
         raise ValueError("sources and targets differ in length")
-    if compression is None or compression not in FlacAudio.COMPRESSION_MODES:
-        compression = DEFAULT_COMPRESSION
-    preset = COMPRESSION_PRESETS[compression]
+    classes = ([FlacAudio] * len(targets) if target_types is None
+               else resolve_types(target_types, targets))
+    modes = resolve_compression(compression, classes)
     batch = _Batch()
     results = [None] * len(sources)
-    jobs = []  # (k, file index, ChainPlan, mask to write)
+    jobs = []  # (k, file index, ChainPlan, what prepare() returned)
     for k, (source, target) in enumerate(zip(sources, targets)):
         i = batch.add(source)
         h = batch.headers[i]
@@ -71,15 +85,22 @@ def convert_files_batch(sources, targets, sample_rate=None, channels=None, chann
             continue
         plan = plan_target((h.channels, h.channel_mask, h.bits_per_sample, h.sample_rate),
                            sample_rate, channels, channel_mask, bits_per_sample)
+        frames = h.total_frames
+        if plan.in_rate != plan.sample_rate and frames:
+            frames = _atgpu.resample_output_frames(frames, plan.channels, plan.in_rate,
+                                                   plan.sample_rate)
         try:
-            mask = target_layout(target, plan.channels, plan.channel_mask)
-        except EncodingError as err:
+            ready = prepare(classes[k], target, plan.channels, plan.channel_mask,
+                            plan.bits_per_sample, plan.sample_rate, frames)
+        except (EncodingError, ValueError) as err:
             results[k] = err
             continue
         batch.want(i)
-        jobs.append((k, i, plan, mask))
-    eng = _atgpu.engine()
+        jobs.append((k, i, plan, ready))
+    if not jobs:
+        return results
     free = []
+    eng = _atgpu.engine()
     try:
         batch.decode()
         good = []
@@ -92,30 +113,21 @@ def convert_files_batch(sources, targets, sample_rate=None, channels=None, chann
         views = [batch.views[i] for _, i, _, _ in good]
         done, free = run_chain_device(
             [DevicePcm(d, _atgpu.PCM_S32, p.sample_offset, p.frames) for d, p in views],
-            [plan for _, _, plan, _ in good], dither)
-        # one encode per (buffer, channels, bits, rate, PADDING size)
-        groups = {}
-        for (k, _, plan, mask), d in zip(good, done):
-            pad = padding_for(d.frames, plan.sample_rate * 10)
-            key = (d.d_pcm, d.fmt, plan.channels, plan.bits_per_sample, plan.sample_rate, pad)
-            groups.setdefault(key, []).append((k, plan, mask, d))
-        for (d_pcm, fmt, ch, bits, rate, pad), members in groups.items():
-            try:
-                opts = _atgpu.make_options(padding_size=pad, **preset)
-                tracks = [(d.sample_offset // ch, d.frames, None) for _, _, _, d in members]
-                _, nb = eng.bounds(opts, tracks, ch, bits)
-                d_out = eng.device_alloc(max(16, nb))
-                free.append(d_out)
-                encoded = eng.encode_device(opts, d_pcm, fmt, tracks, ch, bits, rate, d_out, nb)
-                out = eng.copy_to_host(np.empty(max(1, nb), dtype=np.uint8), d_out)
-            except _atgpu.ATGError as err:
-                for k, _, _, _ in members:
-                    results[k] = EncodingError(str(err))
-                continue
-            for (k, plan, mask, d), res in zip(members, encoded):
-                results[k] = _finish(targets[k], out[res.out_offset:res.out_offset + res.bytes]
-                                     .tobytes(), res.status, plan, mask, d.frames,
-                                     preset["block_size"])
+            [plan for _, _, plan, _ in good], dither, streams=[k for k, _, _, _ in good])
+        tracks = []
+        for (k, _, plan, ready), d in zip(good, done):
+            if classes[k] in (ShortenAudio, WaveAudio):
+                # their headers hold the length: made for the frames that came
+                try:
+                    ready = prepare(classes[k], targets[k], plan.channels, plan.channel_mask,
+                                    plan.bits_per_sample, plan.sample_rate, d.frames)
+                except (EncodingError, ValueError) as err:
+                    results[k] = err
+                    continue
+            tracks.append(Track(k, targets[k], classes[k], modes[k], d, plan.channels,
+                                plan.bits_per_sample, plan.sample_rate, plan.channel_mask, ready))
+        for k, r in write_tracks(tracks).items():
+            results[k] = r
         return results
     finally:
         for d in free:

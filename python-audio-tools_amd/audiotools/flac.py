@@ -229,6 +229,13 @@ def target_layout(filename, channels, channel_mask):
     return int(channel_mask)
 
 
+def oggflac_layout(filename, channels, channel_mask, bits_per_sample):
+    """OggFlacAudio.from_pcm's checks (flac.py:3280-3316) -> the mask its
+    encoder is given: the stream's for more than 2 channels or 16 bits, else 0"""
+    mask = target_layout(filename, channels, channel_mask)
+    return mask if channels > 2 or bits_per_sample > 16 else 0
+
+
 def padding_for(total_pcm_frames, interval):
     """from_pcm's PADDING: room for the SEEKTABLE the frame count implies"""
     if total_pcm_frames is None:
@@ -455,16 +462,8 @@ class OggFlacAudio(FlacAudio):
                                 "(the reference encodes it through the external flac program)")
         if compression is None or compression not in cls.COMPRESSION_MODES:
             compression = DEFAULT_COMPRESSION
-        if pcmreader.channels > 8:
-            raise UnsupportedChannelCount(filename, pcmreader.channels)
-        if int(pcmreader.channel_mask) == 0:
-            channel_mask = _DEFAULT_MASKS.get(pcmreader.channels, 0)
-        elif int(pcmreader.channel_mask) not in _VALID_MASKS:
-            raise UnsupportedChannelMask(filename, int(pcmreader.channel_mask))
-        else:
-            channel_mask = int(pcmreader.channel_mask)
-        if not (pcmreader.channels > 2 or pcmreader.bits_per_sample > 16):
-            channel_mask = 0
+        channel_mask = oggflac_layout(filename, pcmreader.channels, pcmreader.channel_mask,
+                                      pcmreader.bits_per_sample)
         try:
             encoding_function(filename, pcmreader=BufferedPCMReader(pcmreader),
                               channel_mask=channel_mask, **COMPRESSION_PRESETS[compression])

@@ -179,6 +179,14 @@ def m4a_file(channels, bps, rate, block_size, total, mdat, frame_sizes, create_d
     return ftyp + moov + free + bytes(mdat)
 
 
+def check_stream(filename, bits_per_sample, channel_mask):
+    """the streams ALACAudio.from_pcm refuses (m4a.py:953-972)"""
+    if bits_per_sample not in (16, 24):
+        raise UnsupportedBitsPerSample(filename, bits_per_sample)
+    if int(channel_mask) not in VALID_MASKS:
+        raise UnsupportedChannelMask(filename, int(channel_mask))
+
+
 class ALACAudio(AudioFile):
     """the reference's ALACAudio (m4a.py:750-1124), transcode slice"""
 
@@ -233,10 +241,7 @@ class ALACAudio(AudioFile):
         produced by encode_alac on the GPU, the atoms around it here"""
         import io
         from .encoders import encode_alac
-        if pcmreader.bits_per_sample not in (16, 24):
-            raise UnsupportedBitsPerSample(filename, pcmreader.bits_per_sample)
-        if int(pcmreader.channel_mask) not in VALID_MASKS:
-            raise UnsupportedChannelMask(filename, int(pcmreader.channel_mask))
+        check_stream(filename, pcmreader.bits_per_sample, pcmreader.channel_mask)
         mdat = io.BytesIO()
         try:
             (frame_sizes, frames) = (encode_alac if encoding_function is None else

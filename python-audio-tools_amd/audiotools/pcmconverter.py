@@ -270,15 +270,41 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
-def run_chain_device(sources, plans, dither=None, int16_out=True):
+class DeviceDither(object):
+    """The dither source of the batch paths that stays on the device: pass
+    one as `dither=` to run_chain_device, convert_pcm_batch,
+    convert_files_batch or load_batch and the bits are made in device memory
+    by csrc/dither.hip (atg_dither_fill_device) instead of being drawn and
+    uploaded by the host.  Track k of a call's sources reads stream k of a
+    counter-based generator (Philox4x32-10, include/atgpu_dither.h) under
+    the 64-bit `seed`, from the stream's bit 0 on, so a seed fixes a call's
+    result and tests/dither_port.py reproduces it.  seed=None takes 8 bytes
+    of os.urandom once, here, and keeps them in .seed."""
+
+    def __init__(self, seed=None):
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed must fit 64 bits")
+        self.seed = seed
+
+
+def run_chain_device(sources, plans, dither=None, int16_out=True, streams=None):
     """The chain over device memory.  sources: [DevicePcm]; plans:
     [ChainPlan].  -> ([DevicePcm] of the converted tracks, device pointers
     to free once they are used).  Tracks of at most 16 output bits land in
     an int16 buffer when int16_out is set, the others in an int32 one; every
     track starts on a 16-byte boundary, whole frames from its buffer's start.  The dither bytes are drawn from
     `dither` (n -> bytes, default os.urandom) track by track in order, one
-    draw of ceil(bits / 8) bytes per track that reduces."""
+    draw of ceil(bits / 8) bytes per track that reduces.  With a
+    DeviceDither nothing is drawn here: track i's bits are stream
+    streams[i] (default i) of its generator, written by one fill launch into
+    the dither buffer, every track's on a 16-byte boundary."""
+    on_device = isinstance(dither, DeviceDither)
     rand = os.urandom if dither is None else dither
+    if streams is None:
+        streams = range(len(sources))
     eng = _atgpu.engine()
     free = []
 
@@ -331,11 +357,16 @@ def run_chain_device(sources, plans, dither=None, int16_out=True):
             # on a 16-byte boundary and whole frames from the buffer's start
             starts.append(_round_up(sizes[f], 8 * p.channels))
             sizes[f] = starts[-1] + s.frames * p.channels
-        bits_at, parts, nbytes = [], [], 0
-        for s, p in zip(stage, plans):
+        bits_at, parts, runs, nbytes = [], [], [], 0
+        for s, p, stream in zip(stage, plans, streams):
             bits_at.append(8 * nbytes)
             if p.bits_per_sample < p.in_bits and s.frames:
                 want = (s.frames * p.channels + 7) // 8
+                if on_device:
+                    blocks = (want + 15) // 16
+                    runs.append((stream, 0, blocks, nbytes))
+                    nbytes += 16 * blocks
+                    continue
                 parts.append(bytes(rand(want)))
                 if len(parts[-1]) != want:
                     raise ValueError("dither callable returned the wrong number of bytes")
@@ -343,7 +374,10 @@ def run_chain_device(sources, plans, dither=None, int16_out=True):
         d_dither = None
         if nbytes:
             d_dither = alloc(nbytes)
-            eng.copy_to_device(d_dither, np.frombuffer(b"".join(parts), dtype=np.uint8))
+            if on_device:
+                _atgpu.dither_fill_device(runs, dither.seed, d_dither, nbytes)
+            else:
+                eng.copy_to_device(d_dither, np.frombuffer(b"".join(parts), dtype=np.uint8))
         out = [None] * n
         for fmt in (_atgpu.PCM_S16, _atgpu.PCM_S32):
             members = [i for i in range(n) if fmts[i] == fmt]

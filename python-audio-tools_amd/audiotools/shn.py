@@ -41,6 +41,16 @@ class InvalidShorten(InvalidFile):
     """reference audiotools/shn.py:26-27"""
 
 
+def wave_parts(sample_rate, channels, channel_mask, bits_per_sample, total_pcm_frames):
+    """the wave header from_pcm generates for a stream of known length and
+    the pad byte behind an odd amount of data: the bytes of the two VERBATIM
+    commands (shn.py:211-240)"""
+    from .wav import wave_header
+    data_bytes = (bits_per_sample // 8) * channels * total_pcm_frames
+    return (wave_header(sample_rate, channels, channel_mask, bits_per_sample, total_pcm_frames),
+            b"\x00" * (data_bytes % 2))
+
+
 class ShortenAudio(AudioFile):
     """the reference's ShortenAudio (shn.py:30-610), transcode slice"""
 
@@ -113,12 +123,10 @@ class ShortenAudio(AudioFile):
         if pcmreader.bits_per_sample not in (8, 16):
             raise UnsupportedBitsPerSample(filename, pcmreader.bits_per_sample)
         if total_pcm_frames is not None:
-            data_bytes = (pcmreader.bits_per_sample // 8) * pcmreader.channels * total_pcm_frames
-            return cls.from_wave(filename,
-                                 wave_header(pcmreader.sample_rate, pcmreader.channels,
-                                             pcmreader.channel_mask, pcmreader.bits_per_sample,
-                                             total_pcm_frames),
-                                 pcmreader, b"\x00" * (data_bytes % 2), compression, block_size,
+            header, footer = wave_parts(pcmreader.sample_rate, pcmreader.channels,
+                                        pcmreader.channel_mask, pcmreader.bits_per_sample,
+                                        total_pcm_frames)
+            return cls.from_wave(filename, header, pcmreader, footer, compression, block_size,
                                  encoding_function)
         import tempfile
         f = tempfile.NamedTemporaryFile(suffix=".wav")

@@ -11,6 +11,7 @@ such tensors out as FLAC files, without the PCM leaving device memory
   tensor_to_pcm    audio, lengths -> [DevicePcm]
   load_batch       files of any supported format -> AudioBatch
   save_flac_batch  audio, lengths -> .flac files
+  save_batch       audio, lengths -> files of any type the engine writes
 
 The arithmetic is FrameList.to_float() one way (sample / 2^(bits-1)) and
 FloatFrameList.to_int(bits) the other: truncation toward zero, clamped, NaN
@@ -36,7 +37,8 @@ from . import DecodingError, EncodingError  # noqa: E402
 from . import _atgpu  # noqa: E402
 from .pcmconverter import DevicePcm, plan_target, run_chain_device, _round_up  # noqa: E402
 
-__all__ = ["AudioBatch", "pcm_to_tensor", "tensor_to_pcm", "load_batch", "save_flac_batch"]
+__all__ = ["AudioBatch", "pcm_to_tensor", "tensor_to_pcm", "load_batch", "save_flac_batch",
+           "save_batch"]
 
 _DTYPES = {torch.float16: _atgpu.TENSOR_F16, torch.float32: _atgpu.TENSOR_F32,
            torch.float64: _atgpu.TENSOR_F64, torch.int32: _atgpu.TENSOR_I32}
@@ -177,7 +179,8 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
     sample_rates, bits_per_sample, channel_masks, errors).  Every format is
     decoded in one call of its decoder, the tracks are converted to the
     target parameters as PCMConverter converts them (None keeps each source's
-    own value; `dither`: n -> bytes for the tracks that lose bits) and
+    own value; `dither`: n -> bytes for the tracks that lose bits, or a
+    DeviceDither, whose stream k serves sources[k] on the device) and
     audio[k, :, :lengths[k]] is FrameList.to_float() of track k, channel by
     channel; the PCM is never on the host.  sample_rates, bits_per_sample and
     channel_masks are lists with one entry per source: without a target the
@@ -223,7 +226,7 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
         views = [batch.views[index[k]] for k in good]
         done, free = run_chain_device(
             [DevicePcm(d, _atgpu.PCM_S32, p.sample_offset, p.frames) for d, p in views],
-            [plans[k] for k in good], dither)
+            [plans[k] for k in good], dither, streams=good)
         if good:
             ch = counts[0]
             rows = [(DevicePcm(None, _atgpu.PCM_S32, 0, 0), ch, 16)] * n
@@ -245,6 +248,56 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
 
 
 _Target = namedtuple("_Target", "channels bits_per_sample sample_rate")
+
+
+def save_batch(audio, lengths, targets, sample_rate, bits_per_sample=16, channel_mask=None,
+               target_types="suffix", compression=None):
+    """audio[k, :, :lengths[k]] -> the file targets[k], of any type the
+    engine writes: target_types and compression as convert_files_batch takes
+    them, the type by default from each target's suffix.  The file is the one
+    cls.from_pcm(targets[k], <a reader of FloatFrameList(row).to_int(bits)
+    with channel mask `channel_mask or 0`>, compression,
+    total_pcm_frames=lengths[k]) writes (an Ogg FLAC serial number and an
+    .m4a's creation time apart).  sample_rate and bits_per_sample (8, 16 or
+    24): one value or one per row.  tensor_to_pcm, then one encode call per
+    group of rows that share what their encoder fixes per call
+    (targets.write_tracks); the PCM is never on the host.
+    -> per row the class's instance, or the exception its from_pcm raises
+    for a row its type cannot hold / the EncodingError of a row that could
+    not be written, with no file left for it.  ValueError, before any GPU
+    work, for arguments that do not fit the tensor or the targets."""
+    from .targets import Track, prepare, resolve_compression, resolve_types, write_tracks
+    lengths = _check_batch(audio, lengths)
+    targets = list(targets)
+    n, ch, _ = audio.shape
+    if len(targets) != n:
+        raise ValueError("targets has %d entries for %d rows" % (len(targets), n))
+    rates = _per_row(sample_rate, n, "sample_rate")
+    bits = _per_row(bits_per_sample, n, "bits_per_sample")
+    for r, b in zip(rates, bits):
+        if r <= 0:
+            raise ValueError("invalid sample rate")
+        if b not in (8, 16, 24):
+            raise ValueError("invalid bits-per-sample")
+    classes = resolve_types(target_types, targets)
+    modes = resolve_compression(compression, classes)
+    mask = int(channel_mask or 0)
+    results, ready = [None] * n, [None] * n
+    for k, target in enumerate(targets):
+        try:
+            ready[k] = prepare(classes[k], target, ch, mask, bits[k], rates[k], lengths[k])
+        except (EncodingError, ValueError) as err:
+            results[k] = err
+    rows, owner = tensor_to_pcm(audio, lengths, bits)
+    try:
+        written = write_tracks([Track(k, targets[k], classes[k], modes[k], rows[k], ch, bits[k],
+                                      rates[k], mask, ready[k])
+                                for k in range(n) if results[k] is None])
+    finally:
+        del owner
+    for k, r in written.items():
+        results[k] = r
+    return results
 
 
 def save_flac_batch(audio, lengths, targets, sample_rate, bits_per_sample=16,

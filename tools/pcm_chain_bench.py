@@ -19,6 +19,11 @@ conversion built on it.
    (FlacAudio.from_pcm over PCMConverter, one file after another),
    alternating, under an all-zero dither; the files must be identical.
 
+4. With --dither, instead of the three legs above: the headline shape's dither
+   bits made on the device (csrc/dither.hip) against os.urandom + upload, and
+   the fill kernel against a hipMemsetAsync of the same buffer (dither_leg;
+   default --out profiles/dither_bench.json).
+
 Writes one JSON document (--out, default profiles/pcm_chain_bench.json) and
 prints it.
 """
@@ -58,8 +63,15 @@ def main():
     ap.add_argument("--files", type=int, default=128)
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--file-steps", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pcm_chain_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--dither", action="store_true",
+                    help="the device-side dither leg alone (profiles/dither_bench.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles",
+                                "dither_bench.json" if args.dither else "pcm_chain_bench.json")
+    if args.dither:
+        return dither_leg(args)
 
     import torch
     import oracle_port
@@ -247,6 +259,133 @@ def main():
                                        files_doc["convert_files_batch"]["mean_ms"])
 
     return finish(args, torch, bits_doc, head_doc, files_doc, bad)
+
+
+def dither_leg(args):
+    """--dither: the headline shape's dither bits made on the device
+    (csrc/dither.hip) against drawing them with os.urandom and uploading them.
+
+    a. the fill kernel alone over the batch's dither buffer, and a
+       hipMemsetAsync of the same buffer as a store-only yardstick;
+    b. the chain of a batch conversion (pcmconverter.run_chain_device, what
+       convert_pcm_batch runs between its upload and its download) over the
+       same device-resident sources with dither=DeviceDither and with the
+       default os.urandom, alternating in one process."""
+    import torch
+    import dither_port
+    from audiotools import _atgpu, pcmconverter
+
+    torch.cuda.init()
+    dev = torch.device("cuda:0")
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemsetAsync.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t,
+                                   ctypes.c_void_p]
+    P, nf = args.tracks, int(args.seconds * args.rate)
+    blocks = ((nf * 2 + 7) // 8 + 15) // 16
+    size = 16 * blocks * P
+    buf = torch.zeros(size, dtype=torch.uint8, device=dev)
+    runs = [(t, 0, blocks, 16 * blocks * t) for t in range(P)]
+    seed = 0x0123456789ABCDEF
+    bad = 0
+
+    def event_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def memset():
+        if hip.hipMemsetAsync(buf.data_ptr(), 0x5A, size, None) != 0:
+            raise RuntimeError("hipMemsetAsync failed")
+
+    fill_call, fill_kernel, memset_ms = [], [], []
+    for step in range(args.warmup + args.steps):
+        m = event_ms(memset)
+        t0 = time.perf_counter()
+        _atgpu.dither_fill_device(runs, seed, buf.data_ptr(), size)
+        dt = (time.perf_counter() - t0) * 1e3
+        if step >= args.warmup:
+            memset_ms.append(m)
+            fill_call.append(dt)
+            fill_kernel.append(_atgpu.dither_kernel_times()["fill"])
+    host = buf.cpu().numpy()
+    for t in sorted(set(int(v) for v in np.linspace(0, P - 1, args.check))):
+        want = dither_port.blocks(seed, t, 0, blocks)
+        bad += not np.array_equal(host[16 * blocks * t:16 * blocks * (t + 1)], want)
+
+    def rate(ms):
+        return size / (np.mean(ms) * 1e-3)
+
+    fill_doc = {
+        "bytes": size, "runs": P, "blocks_per_run": blocks,
+        "tile_blocks": _atgpu.dither_tile_blocks(),
+        "fill_kernel": dict(stats(fill_kernel), bytes_per_s=rate(fill_kernel),
+                            fraction_of_8TBps=rate(fill_kernel) / HBM_BYTES_PER_S),
+        "fill_call": stats(fill_call),
+        "hipMemsetAsync": dict(stats(memset_ms), bytes_per_s=rate(memset_ms),
+                               fraction_of_8TBps=rate(memset_ms) / HBM_BYTES_PER_S),
+        "fill_over_memset_bytes_per_s": rate(fill_kernel) / rate(memset_ms),
+        "note": "fill_kernel: the call's own event pair round the launch; fill_call: host clock "
+                "round atg_dither_fill_device (checks, table upload, launch, synchronise); "
+                "hipMemsetAsync: torch events on the default stream round the call, alternating "
+                "with the fill",
+    }
+    del buf
+    torch.cuda.empty_cache()
+
+    # ---- b. the chain with the bits made on the device against drawn and uploaded
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    stride = (nf * 6 + 3) // 4 * 4
+    src = torch.randint(-(1 << 23), 1 << 23, (P * stride,), dtype=torch.int32, device=dev,
+                        generator=g)
+    sources = [pcmconverter.DevicePcm(src.data_ptr(), _atgpu.PCM_S32, t * stride, nf)
+               for t in range(P)]
+    plan = pcmconverter.plan_target((6, 0x3F, 24, args.rate), channels=2, channel_mask=0x3,
+                                    bits_per_sample=16)
+    plans = [plan] * P
+    eng = _atgpu.engine()
+
+    def chain(dither):
+        t0 = time.perf_counter()
+        done, free = pcmconverter.run_chain_device(sources, plans, dither)
+        dt = (time.perf_counter() - t0) * 1e3
+        kernel = _atgpu.pcm_chain_kernel_times()["chain"]
+        for d in free:
+            eng.device_free(d)
+        return dt, kernel
+
+    ms = {"DeviceDither": [], "os.urandom": [], "chain_kernel": []}
+    for step in range(args.warmup + args.steps):
+        a, k = chain(pcmconverter.DeviceDither(seed))
+        b, _ = chain(None)
+        if step >= args.warmup:
+            ms["DeviceDither"].append(a)
+            ms["os.urandom"].append(b)
+            ms["chain_kernel"].append(k)
+    chain_doc = {
+        "shape": {"tracks": P, "seconds": args.seconds, "rate": args.rate, "frames": nf,
+                  "in": "24-bit 5.1, int32, device resident", "out": "16-bit stereo, int16"},
+        "run_chain_device_DeviceDither": stats(ms["DeviceDither"]),
+        "run_chain_device_os_urandom": stats(ms["os.urandom"]),
+        "chain_kernel": stats(ms["chain_kernel"]),
+        "urandom_over_device": float(np.mean(ms["os.urandom"]) / np.mean(ms["DeviceDither"])),
+        "note": "host clock round pcmconverter.run_chain_device, the part of convert_pcm_batch "
+                "between its upload and its download (identical in both paths and left out: "
+                "the 10.8 GB of sources stay in device memory); the two paths alternate on the "
+                "same sources; each call allocates its output and dither buffers",
+    }
+    doc = {"device": torch.cuda.get_device_name(0), "warmup": args.warmup, "steps": args.steps,
+           "fill": fill_doc, "chain": chain_doc,
+           "verify": {"streams_checked": args.check, "mismatches": int(bad)}}
+    text = json.dumps(doc, indent=1, sort_keys=True)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    return 1 if bad else 0
 
 
 def finish(args, torch, bits_doc, head_doc, files_doc, bad):
