@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -2000,8 +2001,7 @@ struct DecSlot {
     hipEvent_t ev[kDecTimed + 1] = {}; // phase events (emit end = ev[5])
     hipEvent_t ev_chain = nullptr;     // the chain's second pass is done (decoder stream)
     hipEvent_t ev_done = nullptr;
-    uint8_t *md5_h = nullptr;          // pinned
-    size_t md5_cap = 0;
+    PinBuf<uint8_t> md5_h;             // the digests, then the hypothesis check word
     std::vector<DecTrack> tr;
     std::vector<DecCount> cnt;
     std::vector<uint64_t> md5_meta;    // offsets then lengths (upload source)
@@ -2018,6 +2018,51 @@ struct DecSlot {
     const uint8_t *data = nullptr;
     uint64_t len = 0;
     bool spec = false; // k_dec_spec ran for this batch
+
+    std::array<hipEvent_t *, 2> fences() { return {&ev_chain, &ev_done}; }
+    // the workspaces back (a slot past the rotation's depth), the slot's
+    // stream drained first
+    void release_device()
+    {
+        if (s_md5)
+            (void)hipStreamSynchronize(s_md5);
+        release_all(pcm, bytes, md5, md5meta, tracks, frames, jobs, warm, rows, meta);
+    }
+    // everything the slot holds; any of it may still be null after a failed
+    // create
+    void release()
+    {
+        release_device();
+        md5_h.release();
+        for (hipEvent_t &e : ev)
+            destroy_event(e);
+        for (hipEvent_t *e : fences())
+            destroy_event(*e);
+        if (s_md5)
+            (void)hipStreamDestroy(s_md5);
+    }
+};
+
+// Ogg FLAC (atg_oggflac_decode_*): the container pass's tables, the
+// compacted streams, its phase events and host copies
+struct DecOgg {
+    DevBuf streams, walk, pages, acc, sum, pos, len, trk, hdr, out;
+    hipEvent_t ev[kOggTimed + 1] = {};
+    float times[kOggTimed] = {};
+    bool ready = false; // tables uploaded, events created
+    bool last = false;  // the last waited batch came through the Ogg entries
+    uint32_t npk = 0;   // packets of the batch (upload source)
+    std::vector<OggStream> st;
+    std::vector<OggWalk> wk;
+    std::vector<OggSum> sm;
+    std::vector<OggHdr> hd;
+
+    void release()
+    {
+        release_all(streams, walk, pages, acc, sum, pos, len, trk, hdr, out);
+        for (hipEvent_t &e : ev)
+            destroy_event(e);
+    }
 };
 
 struct atg_decoder {
@@ -2040,19 +2085,18 @@ struct atg_decoder {
     std::vector<DecSlot *> roll_q;  // rolled batches with slices to run, oldest first
     uint64_t next_ticket = 1;
     int last = -1; // slot of the last waited batch (decode_fetch)
-    // Ogg FLAC (atg_oggflac_decode_*): the container pass's tables, the
-    // compacted streams, its phase events and host copies
-    DevBuf og_streams, og_walk, og_pages, og_acc, og_sum, og_pos, og_len, og_trk, og_hdr, og_out;
-    hipEvent_t og_ev[kOggTimed + 1] = {};
-    float og_times[kOggTimed] = {};
-    bool og_ready = false; // tables uploaded, events created
-    bool last_ogg = false; // the last waited batch came through the Ogg entries
-    uint32_t og_npk = 0;   // packets of the batch (upload source)
-    std::vector<OggStream> og_st;
-    std::vector<OggWalk> og_wk;
-    std::vector<OggSum> og_sm;
-    std::vector<OggHdr> og_hd;
+    DecOgg og;
 };
+
+// no batch in flight: what the staging buffer, a new depth and the Ogg
+// entries ask for
+static bool decoder_busy(const atg_decoder *d)
+{
+    for (const DecSlot &sl : d->slot)
+        if (sl.busy)
+            return true;
+    return false;
+}
 
 static const uint32_t kMasks[9] = {0, 0x4, 0x3, 0x7, 0x33, 0x37, 0x3F, 0x70F, 0x63F};
 
@@ -2190,12 +2234,9 @@ atg_status atg_decoder_create(int device, atg_decoder **out)
     if (!out)
         return g_dec_err.fail(ATG_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return g_dec_err.fail(ATG_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n)
-        return g_dec_err.fail(ATG_ERR_INVALID, "device index out of range");
-    DHIP(hipSetDevice(device));
+    const atg_status st = use_device(device, g_dec_err);
+    if (st != ATG_OK)
+        return st;
     static uint8_t t8[256];
     static uint16_t t16[4][256];
     crc_build_tables<8>(0x07u, t8, 1);
@@ -2205,7 +2246,10 @@ atg_status atg_decoder_create(int device, atg_decoder **out)
     static uint16_t adv[24][16];
     crc_build_advance<16>(t16[0], &adv[0][0], 24);
     DHIP(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_adv), adv, sizeof(adv)));
-    atg_decoder *d = new atg_decoder();
+    // destroyed with whatever it holds so far on any failure below
+    std::unique_ptr<atg_decoder, void (*)(atg_decoder *)> own(new atg_decoder(),
+                                                              atg_decoder_destroy);
+    atg_decoder *d = own.get();
     d->device = device;
     DHIP(hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking));
     for (DecSlot &sl : d->slot) {
@@ -2213,49 +2257,32 @@ atg_status atg_decoder_create(int device, atg_decoder **out)
         // every slot on these in turn and the chains on s_roll
         if (&sl - d->slot < kDecSlots)
             DHIP(hipStreamCreateWithFlags(&sl.s_md5, hipStreamNonBlocking));
-        for (auto &e : sl.ev)
-            DHIP(hipEventCreate(&e));
-        DHIP(hipEventCreateWithFlags(&sl.ev_chain, hipEventDisableTiming));
-        DHIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
+        ATG_HIP_TRY(g_dec_err, ensure_events(sl.ev), "hipEventCreate(&e)");
+        DHIP(create_fences(sl.fences()));
     }
-    *out = d;
+    *out = own.release();
     return ATG_OK;
 }
 
+// Streams drained in this order, then every owner gives back what it holds;
+// any stream or event may still be null after a failed create.
 void atg_decoder_destroy(atg_decoder *d)
 {
     if (!d)
         return;
     (void)hipSetDevice(d->device);
-    (void)hipStreamSynchronize(d->s);
-    for (DevBuf *b : {&d->data, &d->tracks, &d->counts, &d->ncand, &d->cand_pos, &d->cand_idx,
-                    &d->recs, &d->hits, &d->segs, &d->cbits, &d->spec, &d->cand_trk,
-                    &d->og_streams, &d->og_walk, &d->og_pages, &d->og_acc, &d->og_sum,
-                    &d->og_pos, &d->og_len, &d->og_trk, &d->og_hdr, &d->og_out})
-        b->release();
-    for (auto &e : d->og_ev)
-        if (e)
-            (void)hipEventDestroy(e);
+    if (d->s)
+        (void)hipStreamSynchronize(d->s);
+    release_all(d->data, d->tracks, d->counts, d->ncand, d->cand_pos, d->cand_idx, d->recs,
+                d->hits, d->segs, d->cbits, d->spec, d->cand_trk);
+    d->og.release();
     if (d->s_roll)
         (void)hipStreamSynchronize(d->s_roll);
-    for (DecSlot &sl : d->slot) {
-        if (sl.s_md5)
-            (void)hipStreamSynchronize(sl.s_md5);
-        for (DevBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames,
-                          &sl.jobs, &sl.warm, &sl.rows, &sl.meta})
-            b->release();
-        for (auto &e : sl.ev)
-            (void)hipEventDestroy(e);
-        (void)hipEventDestroy(sl.ev_chain);
-        (void)hipEventDestroy(sl.ev_done);
-        if (sl.md5_h)
-            (void)hipHostFree(sl.md5_h);
-        if (sl.s_md5)
-            (void)hipStreamDestroy(sl.s_md5);
-    }
-    if (d->s_roll)
-        (void)hipStreamDestroy(d->s_roll);
-    (void)hipStreamDestroy(d->s);
+    for (DecSlot &sl : d->slot)
+        sl.release();
+    for (hipStream_t q : {d->s_roll, d->s})
+        if (q)
+            (void)hipStreamDestroy(q);
     delete d;
 }
 
@@ -2269,9 +2296,9 @@ static hipError_t dec_results_d2h(DecSlot &sl, uint32_t n, hipStream_t q)
 {
     if (!n)
         return hipSuccess;
-    hipError_t e = hipMemcpyAsync(sl.md5_h, sl.md5.p, 16 * (size_t)n, hipMemcpyDeviceToHost, q);
+    hipError_t e = hipMemcpyAsync(sl.md5_h.p, sl.md5.p, 16 * (size_t)n, hipMemcpyDeviceToHost, q);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(sl.md5_h + 16 * (size_t)n, (uint8_t *)sl.md5.p + 16 * (size_t)n, 16,
+        e = hipMemcpyAsync(sl.md5_h.p + 16 * (size_t)n, (uint8_t *)sl.md5.p + 16 * (size_t)n, 16,
                            hipMemcpyDeviceToHost, q);
     return e;
 }
@@ -2607,14 +2634,7 @@ static atg_status enqueue_restore(atg_decoder *d, DecSlot &sl, const uint32_t *w
         sl.md5_meta[n + t] = vis * tr[t].channels * ((tr[t].bps + 7) / 8);
     }
     DHIP(sl.md5meta.ensure(sizeof(uint64_t) * 2 * std::max<uint32_t>(n, 1)));
-    if (sl.md5_cap < 16 * (size_t)n + 16) {
-        if (sl.md5_h)
-            (void)hipHostFree(sl.md5_h);
-        sl.md5_h = nullptr;
-        sl.md5_cap = 0;
-        DHIP(hipHostMalloc((void **)&sl.md5_h, 16 * (size_t)n + 16, hipHostMallocDefault));
-        sl.md5_cap = 16 * (size_t)n + 16;
-    }
+    DHIP(sl.md5_h.ensure(16 * (size_t)n + 16));
     if (n)
         DHIP(hipMemcpyAsync(sl.md5meta.p, sl.md5_meta.data(), sizeof(uint64_t) * 2 * n,
                             hipMemcpyHostToDevice, ss));
@@ -2623,11 +2643,9 @@ static atg_status enqueue_restore(atg_decoder *d, DecSlot &sl, const uint32_t *w
         // the chain in depth - 2 slices, one per enqueue, all batches' in one
         // launch on s_roll once this batch's bytes are written
         DHIP(hipEventRecord(ev[5], ss));
-        if (!d->s_roll) {
-            int prio_lo = 0, prio_hi = 0;
-            DHIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-            DHIP(hipStreamCreateWithPriority(&d->s_roll, hipStreamNonBlocking, prio_hi));
-        }
+        if (!d->s_roll)
+            ATG_HIP_TRY(g_dec_err, high_priority_stream(&d->s_roll),
+                        "hipStreamCreateWithPriority(&d->s_roll, hipStreamNonBlocking, prio_hi)");
         sl.roll_parts = (uint32_t)d->depth - 2u;
         sl.roll_done = 0;
         d->roll_q.push_back(&sl);
@@ -2653,7 +2671,7 @@ static atg_status finish_decode(atg_decoder *d, DecSlot &sl, atg_flac_dec_result
     }
     DHIP(hipEventSynchronize(sl.ev_done));
     const size_t nt = sl.tr.size();
-    if (sl.spec && nt && (*(const uint32_t *)(sl.md5_h + 16 * nt) || d->spec_mode == 2)) {
+    if (sl.spec && nt && (*(const uint32_t *)(sl.md5_h.p + 16 * nt) || d->spec_mode == 2)) {
         // a frame-end hypothesis failed the restore's check (or the
         // self-check mode): the batch again with every subframe walked
         const std::vector<atg_flac_dec_track> want = sl.want;
@@ -2698,7 +2716,7 @@ static atg_status finish_decode(atg_decoder *d, DecSlot &sl, atg_flac_dec_result
         r.walk_frames = c.n_frames;
         r.walk_status = c.status;
         fbase += c.n_frames;
-        std::memcpy(r.md5, &sl.md5_h[16 * (size_t)t], 16);
+        std::memcpy(r.md5, &sl.md5_h.p[16 * (size_t)t], 16);
         if (c.crc_frame != 0xFFFFFFFFu) { // read() stops at the bad frame
             r.pcm_frames = c.crc_pcm;
             r.n_frames = c.crc_frame;
@@ -2743,6 +2761,21 @@ static DecSlot *find_dec_ticket(atg_decoder *d, uint64_t ticket)
     return nullptr;
 }
 
+// The head of the *_host entries: the caller's bytes into d->data on the
+// decoder stream, 64 zero bytes behind them for the word readers.  The
+// decoder stream reads that buffer, so no batch may be in flight.
+static atg_status stage_input(atg_decoder *d, const uint8_t *data, uint64_t len)
+{
+    DHIP(hipSetDevice(d->device));
+    if (decoder_busy(d))
+        return g_dec_err.fail(ATG_ERR_INVALID, "a device decode is in flight: wait for it first");
+    DHIP(d->data.ensure(len + 64));
+    DHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
+    if (len)
+        DHIP(hipMemcpyAsync(d->data.p, data, len, hipMemcpyHostToDevice, d->s));
+    return ATG_OK;
+}
+
 extern "C" {
 
 atg_status atg_flac_decode_device_async(atg_decoder *d, const void *d_data, uint64_t len,
@@ -2784,7 +2817,7 @@ atg_status atg_flac_decode_wait(atg_decoder *d, uint64_t ticket, atg_flac_dec_re
     atg_status st = finish_decode(d, *sl, results);
     if (st != ATG_OK)
         return st;
-    d->last_ogg = false;
+    d->og.last = false;
     if (d_pcm)
         *d_pcm = (const int32_t *)sl->pcm.p;
     if (total_samples)
@@ -2815,18 +2848,11 @@ atg_status atg_flac_decode_host(atg_decoder *d, const uint8_t *data, uint64_t le
     ATG_HANDLE_LOCK(d);
     if (!d || (!tracks && n) || (!results && n) || (!data && len))
         return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
-    DHIP(hipSetDevice(d->device));
-    // the staging buffer is read by the decoder stream: no batch in flight
-    for (DecSlot &sl : d->slot)
-        if (sl.busy)
-            return g_dec_err.fail(ATG_ERR_INVALID,
-                                  "a device decode is in flight: wait for it first");
-    DHIP(d->data.ensure(len + 64));
-    DHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
-    if (len)
-        DHIP(hipMemcpyAsync(d->data.p, data, len, hipMemcpyHostToDevice, d->s));
+    atg_status st = stage_input(d, data, len);
+    if (st != ATG_OK)
+        return st;
     uint64_t ticket = 0;
-    atg_status st = atg_flac_decode_device_async(d, d->data.p, len, tracks, n, &ticket);
+    st = atg_flac_decode_device_async(d, d->data.p, len, tracks, n, &ticket);
     if (st != ATG_OK)
         return st;
     uint64_t ts = 0;
@@ -2885,20 +2911,12 @@ atg_status atg_decoder_set_inflight(atg_decoder *d, uint32_t n)
     ATG_HANDLE_LOCK(d);
     if (!d || n < (uint32_t)kDecSlots || n > (uint32_t)kDecMaxSlots)
         return g_dec_err.fail(ATG_ERR_INVALID, "decode batches in flight must be 3..16");
-    for (DecSlot &sl : d->slot)
-        if (sl.busy)
-            return g_dec_err.fail(ATG_ERR_INVALID,
-                                  "a decode batch is in flight: wait for it first");
+    if (decoder_busy(d))
+        return g_dec_err.fail(ATG_ERR_INVALID, "a decode batch is in flight: wait for it first");
     // a lower depth gives the workspaces of the slots past it back (a
     // config-2 slot holds ~5 GB: PCM, rows, byte image)
-    for (int k = (int)n; k < kDecMaxSlots; ++k) {
-        DecSlot &sl = d->slot[k];
-        if (sl.s_md5)
-            (void)hipStreamSynchronize(sl.s_md5);
-        for (DevBuf *b : {&sl.pcm, &sl.bytes, &sl.md5, &sl.md5meta, &sl.tracks, &sl.frames,
-                          &sl.jobs, &sl.warm, &sl.rows, &sl.meta})
-            b->release();
-    }
+    for (int k = (int)n; k < kDecMaxSlots; ++k)
+        d->slot[k].release_device();
     d->depth = (int)n;
     d->last = -1; // the oldest-slot rotation starts over
     return ATG_OK;
@@ -2925,21 +2943,9 @@ int atg_decoder_kernel_times(atg_decoder *d, const char **names, float *ms, int 
     ATG_HANDLE_LOCK(d);
     if (!d || !d->have_times)
         return 0;
-    int n = cap < kDecTimed ? cap : kDecTimed;
-    for (int k = 0; k < n; ++k) {
-        if (names)
-            names[k] = kDecNames[k];
-        if (ms)
-            ms[k] = d->times[k];
-    }
+    const int n = copy_times(kDecNames, d->times, kDecTimed, names, ms, cap);
     // an Ogg FLAC batch: the container pass's phases follow
-    for (int k = 0; d->last_ogg && k < kOggTimed && n < cap; ++k, ++n) {
-        if (names)
-            names[n] = kOggNames[k];
-        if (ms)
-            ms[n] = d->og_times[k];
-    }
-    return n;
+    return d->og.last ? copy_times(kOggNames, d->og.times, kOggTimed, names, ms, cap, n) : n;
 }
 
 } // extern "C"
@@ -3069,7 +3075,7 @@ static atg_status enqueue_ogg_decode(atg_decoder *d, DecSlot &sl, const uint8_t 
 {
     hipStream_t s = d->s;
     OGG_LIMIT(len > ATG_OGG_MAX_BATCH_BYTES, "Ogg FLAC batch larger than ATG_OGG_MAX_BATCH_BYTES");
-    std::vector<OggStream> &st = d->og_st;
+    std::vector<OggStream> &st = d->og.st;
     st.assign(n, OggStream());
     for (uint32_t t = 0; t < n; ++t) {
         const atg_oggflac_dec_track &a = tracks[t];
@@ -3080,57 +3086,55 @@ static atg_status enqueue_ogg_decode(atg_decoder *d, DecSlot &sl, const uint8_t 
         st[t].start = a.data_offset;
         st[t].end = a.data_offset + a.data_bytes;
     }
-    if (!d->og_ready) {
+    if (!d->og.ready) {
         DHIP(ogg_upload_tables());
-        for (auto &e : d->og_ev)
-            if (!e)
-                DHIP(hipEventCreate(&e));
-        d->og_ready = true;
+        ATG_HIP_TRY(g_dec_err, ensure_events(d->og.ev), "hipEventCreate(&e)");
+        d->og.ready = true;
     }
     const uint32_t n1 = std::max<uint32_t>(n, 1);
     const uint64_t nw = std::max<uint64_t>(1, (len + 3) / 4);
     const uint32_t *w = (const uint32_t *)d_data;
-    DHIP(d->og_streams.ensure(sizeof(OggStream) * n1));
-    DHIP(d->og_walk.ensure(sizeof(OggWalk) * n1));
-    DHIP(d->og_sum.ensure(sizeof(OggSum) * n1));
-    DHIP(d->og_hdr.ensure(sizeof(OggHdr) * n1));
-    OggStream *dst = (OggStream *)d->og_streams.p;
+    DHIP(d->og.streams.ensure(sizeof(OggStream) * n1));
+    DHIP(d->og.walk.ensure(sizeof(OggWalk) * n1));
+    DHIP(d->og.sum.ensure(sizeof(OggSum) * n1));
+    DHIP(d->og.hdr.ensure(sizeof(OggHdr) * n1));
+    OggStream *dst = (OggStream *)d->og.streams.p;
     // 1: the page walk counts
     DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
-    DHIP(hipEventRecord(d->og_ev[0], s));
-    DHIP(launch_ogg_walk(d_data, dst, n, 1, (OggWalk *)d->og_walk.p, nullptr, s));
-    d->og_wk.assign(n, OggWalk());
-    DHIP(hipMemcpyAsync(d->og_wk.data(), d->og_walk.p, sizeof(OggWalk) * n, hipMemcpyDeviceToHost,
+    DHIP(hipEventRecord(d->og.ev[0], s));
+    DHIP(launch_ogg_walk(d_data, dst, n, 1, (OggWalk *)d->og.walk.p, nullptr, s));
+    d->og.wk.assign(n, OggWalk());
+    DHIP(hipMemcpyAsync(d->og.wk.data(), d->og.walk.p, sizeof(OggWalk) * n, hipMemcpyDeviceToHost,
                         s));
     DHIP(hipStreamSynchronize(s));
     uint64_t npages = 0, nchunks = 0;
     for (uint32_t t = 0; t < n; ++t) {
         st[t].page_base = npages;
         st[t].chunk_base = nchunks;
-        npages += d->og_wk[t].pages;
-        nchunks += d->og_wk[t].chunks;
+        npages += d->og.wk[t].pages;
+        nchunks += d->og.wk[t].chunks;
     }
     // 2: the page records, their checksums, what is delivered
-    DHIP(d->og_pages.ensure(sizeof(OggPage) * std::max<uint64_t>(npages, 1)));
-    DHIP(d->og_acc.ensure(sizeof(uint32_t) * std::max<uint64_t>(npages, 1)));
-    DHIP(hipMemsetAsync(d->og_acc.p, 0, sizeof(uint32_t) * std::max<uint64_t>(npages, 1), s));
+    DHIP(d->og.pages.ensure(sizeof(OggPage) * std::max<uint64_t>(npages, 1)));
+    DHIP(d->og.acc.ensure(sizeof(uint32_t) * std::max<uint64_t>(npages, 1)));
+    DHIP(hipMemsetAsync(d->og.acc.p, 0, sizeof(uint32_t) * std::max<uint64_t>(npages, 1), s));
     DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
-    const OggPage *pages = (const OggPage *)d->og_pages.p;
-    DHIP(launch_ogg_walk(d_data, dst, n, 2, (OggWalk *)d->og_walk.p, (OggPage *)d->og_pages.p, s));
-    DHIP(hipEventRecord(d->og_ev[1], s));
-    DHIP(launch_ogg_crc(w, nw, pages, npages, nchunks, (uint32_t *)d->og_acc.p, s));
-    DHIP(launch_ogg_summary(dst, n, (const OggWalk *)d->og_walk.p, pages,
-                            (const uint32_t *)d->og_acc.p, (OggSum *)d->og_sum.p, s));
-    d->og_sm.assign(n, OggSum());
-    DHIP(hipMemcpyAsync(d->og_sm.data(), d->og_sum.p, sizeof(OggSum) * n, hipMemcpyDeviceToHost,
+    const OggPage *pages = (const OggPage *)d->og.pages.p;
+    DHIP(launch_ogg_walk(d_data, dst, n, 2, (OggWalk *)d->og.walk.p, (OggPage *)d->og.pages.p, s));
+    DHIP(hipEventRecord(d->og.ev[1], s));
+    DHIP(launch_ogg_crc(w, nw, pages, npages, nchunks, (uint32_t *)d->og.acc.p, s));
+    DHIP(launch_ogg_summary(dst, n, (const OggWalk *)d->og.walk.p, pages,
+                            (const uint32_t *)d->og.acc.p, (OggSum *)d->og.sum.p, s));
+    d->og.sm.assign(n, OggSum());
+    DHIP(hipMemcpyAsync(d->og.sm.data(), d->og.sum.p, sizeof(OggSum) * n, hipMemcpyDeviceToHost,
                         s));
     DHIP(hipStreamSynchronize(s));
     uint64_t npk = 0, out_bytes = 0, max_out = 0;
     for (uint32_t t = 0; t < n; ++t) {
         st[t].pkt_base = npk;
         st[t].out_base = out_bytes;
-        npk += d->og_sm[t].packets;
-        const uint64_t slot = (d->og_sm[t].bytes + 15u) & ~15ull;
+        npk += d->og.sm[t].packets;
+        const uint64_t slot = (d->og.sm[t].bytes + 15u) & ~15ull;
         out_bytes += slot;
         max_out = std::max(max_out, slot);
     }
@@ -3138,45 +3142,45 @@ static atg_status enqueue_ogg_decode(atg_decoder *d, DecSlot &sl, const uint8_t 
     // 3: the packet table and the compacted streams (zero slack after the
     // last: the bit reader's window loads are clamped to the buffer)
     const uint64_t out_cap = out_bytes + 256;
-    DHIP(d->og_pos.ensure(sizeof(uint64_t) * std::max<uint64_t>(npk, 1)));
-    DHIP(d->og_len.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
-    DHIP(d->og_trk.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
-    DHIP(d->og_out.ensure(out_cap));
-    DHIP(hipMemsetAsync((uint8_t *)d->og_out.p + out_bytes, 0, 256, s));
+    DHIP(d->og.pos.ensure(sizeof(uint64_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og.len.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og.trk.ensure(sizeof(uint32_t) * std::max<uint64_t>(npk, 1)));
+    DHIP(d->og.out.ensure(out_cap));
+    DHIP(hipMemsetAsync((uint8_t *)d->og.out.p + out_bytes, 0, 256, s));
     DHIP(hipMemcpyAsync(dst, st.data(), sizeof(OggStream) * n, hipMemcpyHostToDevice, s));
-    DHIP(hipEventRecord(d->og_ev[2], s));
-    DHIP(launch_ogg_packets(d_data, dst, (const OggSum *)d->og_sum.p, pages, npages,
-                            (uint64_t *)d->og_pos.p, (uint32_t *)d->og_len.p,
-                            (uint32_t *)d->og_trk.p, s));
-    DHIP(launch_ogg_gather(w, nw, dst, (const OggSum *)d->og_sum.p, pages, n, max_out,
-                           (uint32_t *)d->og_out.p, s));
-    DHIP(hipEventRecord(d->og_ev[3], s));
+    DHIP(hipEventRecord(d->og.ev[2], s));
+    DHIP(launch_ogg_packets(d_data, dst, (const OggSum *)d->og.sum.p, pages, npages,
+                            (uint64_t *)d->og.pos.p, (uint32_t *)d->og.len.p,
+                            (uint32_t *)d->og.trk.p, s));
+    DHIP(launch_ogg_gather(w, nw, dst, (const OggSum *)d->og.sum.p, pages, n, max_out,
+                           (uint32_t *)d->og.out.p, s));
+    DHIP(hipEventRecord(d->og.ev[3], s));
     // the frame decode over the compacted streams
-    const uint32_t *cw = (const uint32_t *)d->og_out.p;
+    const uint32_t *cw = (const uint32_t *)d->og.out.p;
     const uint64_t cnw = out_cap / 4;
     DHIP(d->tracks.ensure(sizeof(DecTrack) * n1));
     DHIP(d->counts.ensure(sizeof(DecCount) * n1));
     DHIP(d->ncand.ensure(2 * sizeof(uint32_t)));
     DHIP(d->recs.ensure(sizeof(ParseRec) * std::max<uint64_t>(npk, 1)));
-    d->og_npk = (uint32_t)npk;
-    DHIP(hipMemcpyAsync(d->ncand.p, &d->og_npk, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    d->og.npk = (uint32_t)npk;
+    DHIP(hipMemcpyAsync(d->ncand.p, &d->og.npk, sizeof(uint32_t), hipMemcpyHostToDevice, s));
     DecTrack *dtr = (DecTrack *)d->tracks.p;
-    const OggHdr *dh = (const OggHdr *)d->og_hdr.p;
-    const uint64_t *pos = (const uint64_t *)d->og_pos.p;
+    const OggHdr *dh = (const OggHdr *)d->og.hdr.p;
+    const uint64_t *pos = (const uint64_t *)d->og.pos.p;
     hipEvent_t *ev = sl.ev;
     const dim3 tg((n + 63) / 64);
     DHIP(hipEventRecord(ev[0], s));
     if (n)
         hipLaunchKernelGGL(k_ogg_tracks, tg, dim3(64), 0, s, cw, (const OggStream *)dst,
-                           (const OggSum *)d->og_sum.p, n, pos, (const uint32_t *)d->og_len.p,
-                           dtr, (OggHdr *)d->og_hdr.p);
+                           (const OggSum *)d->og.sum.p, n, pos, (const uint32_t *)d->og.len.p,
+                           dtr, (OggHdr *)d->og.hdr.p);
     DHIP(hipGetLastError());
     DHIP(hipEventRecord(ev[1], s));
     if (npk) {
         hipLaunchKernelGGL(k_ogg_parse, dim3((unsigned)std::min<uint64_t>((npk + 63) / 64, 4096)),
                            dim3(64), 0, s, cw, cnw, (const DecTrack *)dtr, (const OggStream *)dst,
-                           dh, (uint32_t)npk, pos, (const uint32_t *)d->og_len.p,
-                           (const uint32_t *)d->og_trk.p, (ParseRec *)d->recs.p);
+                           dh, (uint32_t)npk, pos, (const uint32_t *)d->og.len.p,
+                           (const uint32_t *)d->og.trk.p, (ParseRec *)d->recs.p);
         DHIP(hipGetLastError());
         hipLaunchKernelGGL(k_dec_crc, dim3((unsigned)std::min<uint64_t>((npk + 3) / 4, 8192)),
                            dim3(256), 0, s, cw, cnw, (const uint32_t *)d->ncand.p, pos,
@@ -3191,16 +3195,16 @@ static atg_status enqueue_ogg_decode(atg_decoder *d, DecSlot &sl, const uint8_t 
     DHIP(hipGetLastError());
     sl.cnt.assign(n, DecCount());
     sl.tr.assign(n, DecTrack());
-    d->og_hd.assign(n, OggHdr());
+    d->og.hd.assign(n, OggHdr());
     DHIP(hipMemcpyAsync(sl.cnt.data(), d->counts.p, sizeof(DecCount) * n, hipMemcpyDeviceToHost,
                         s));
     DHIP(hipMemcpyAsync(sl.tr.data(), dtr, sizeof(DecTrack) * n, hipMemcpyDeviceToHost, s));
-    DHIP(hipMemcpyAsync(d->og_hd.data(), d->og_hdr.p, sizeof(OggHdr) * n, hipMemcpyDeviceToHost,
+    DHIP(hipMemcpyAsync(d->og.hd.data(), d->og.hdr.p, sizeof(OggHdr) * n, hipMemcpyDeviceToHost,
                         s));
     DHIP(hipStreamSynchronize(s));
     sl.want.assign(n, atg_flac_dec_track());
     for (uint32_t t = 0; t < n; ++t)
-        std::memcpy(sl.want[t].md5, d->og_hd[t].md5, 16);
+        std::memcpy(sl.want[t].md5, d->og.hd[t].md5, 16);
     sl.data = d_data;
     sl.len = len;
     sl.spec = false;
@@ -3293,10 +3297,8 @@ atg_status atg_oggflac_decode_device(atg_decoder *d, const void *d_data, uint64_
         return g_dec_err.fail(ATG_ERR_INVALID, "NULL argument");
     if (((uintptr_t)d_data) & 3)
         return g_dec_err.fail(ATG_ERR_INVALID, "d_data must be 4-byte aligned");
-    for (DecSlot &sl : d->slot)
-        if (sl.busy)
-            return g_dec_err.fail(ATG_ERR_INVALID,
-                                  "a device decode is in flight: wait for it first");
+    if (decoder_busy(d))
+        return g_dec_err.fail(ATG_ERR_INVALID, "a device decode is in flight: wait for it first");
     DHIP(hipSetDevice(d->device));
     DecSlot *sl = nullptr;
     atg_status st = take_dec_slot(d, &sl);
@@ -3315,13 +3317,13 @@ atg_status atg_oggflac_decode_device(atg_decoder *d, const void *d_data, uint64_
         return st;
     }
     for (int k = 0; k < kOggTimed; ++k)
-        if (hipEventElapsedTime(&d->og_times[k], d->og_ev[k], d->og_ev[k + 1]) != hipSuccess)
-            d->og_times[k] = 0.f;
-    d->last_ogg = true;
+        if (hipEventElapsedTime(&d->og.times[k], d->og.ev[k], d->og.ev[k + 1]) != hipSuccess)
+            d->og.times[k] = 0.f;
+    d->og.last = true;
     for (uint32_t t = 0; t < n; ++t) {
         atg_oggflac_dec_result &r = results[t];
-        const OggSum &sm = d->og_sm[t];
-        const OggHdr &h = d->og_hd[t];
+        const OggSum &sm = d->og.sm[t];
+        const OggHdr &h = d->og.hd[t];
         std::memset(&r, 0, sizeof(r));
         r.pcm_offset = fr[t].pcm_offset;
         r.sample_offset = sl->tr[t].pcm_base;
@@ -3371,17 +3373,11 @@ atg_status atg_oggflac_decode_host(atg_decoder *d, const uint8_t *data, uint64_t
     if (len > ATG_OGG_MAX_BATCH_BYTES)
         return g_dec_err.fail(ATG_ERR_UNSUPPORTED,
                               "Ogg FLAC batch larger than ATG_OGG_MAX_BATCH_BYTES");
-    DHIP(hipSetDevice(d->device));
-    for (DecSlot &sl : d->slot)
-        if (sl.busy)
-            return g_dec_err.fail(ATG_ERR_INVALID,
-                                  "a device decode is in flight: wait for it first");
-    DHIP(d->data.ensure(len + 64));
-    DHIP(hipMemsetAsync((uint8_t *)d->data.p + (len & ~3ull), 0, 64, d->s));
-    if (len)
-        DHIP(hipMemcpyAsync(d->data.p, data, len, hipMemcpyHostToDevice, d->s));
+    atg_status st = stage_input(d, data, len);
+    if (st != ATG_OK)
+        return st;
     uint64_t ts = 0;
-    const atg_status st = atg_oggflac_decode_device(d, d->data.p, len, tracks, n, results, nullptr,
+    st = atg_oggflac_decode_device(d, d->data.p, len, tracks, n, results, nullptr,
                                                     &ts);
     if (st != ATG_OK)
         return st;

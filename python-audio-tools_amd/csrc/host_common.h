@@ -1,5 +1,5 @@
 // host_common.h — the host-side frame every component of libatgpu shares:
-// the growable device buffer, the per-component error slot with its
+// the growable device and pinned buffers, the per-component error slot with its
 // "try a HIP call" macro, the stage times, the base of the single-stream
 // codec handles, and what a component without a handle is made of: its
 // per-device contexts, its one timed launch, the device it runs on and the
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -42,6 +43,45 @@ struct DevBuf {
     }
 };
 
+// The pinned-host counterpart: n elements of T, at least 16, growing only.
+// No destructor either, for DevBuf's reason (teardown);
+// the owner calls release().
+template <class T> struct PinBuf {
+    T *p = nullptr;
+    size_t cap = 0; // elements
+    hipError_t ensure(size_t n)
+    {
+        if (p && n <= cap)
+            return hipSuccess;
+        release();
+        const size_t want = std::max<size_t>(n, 16);
+        hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess)
+            cap = want;
+        return e;
+    }
+    void release()
+    {
+        if (p)
+            (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// release() on every buffer named, DevBufs and PinBufs alike
+template <class... B> void release_all(B &...b) { (b.release(), ...); }
+
+// A non-blocking stream at the device's highest stream priority.
+inline hipError_t high_priority_stream(hipStream_t *s)
+{
+    int prio_lo = 0, prio_hi = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    if (e == hipSuccess)
+        e = hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio_hi);
+    return e;
+}
+
 // One component's last error message.  Every translation unit keeps its own
 // thread_local slot, so atg_*_last_error() reports that component alone.
 struct ErrSlot {
@@ -67,17 +107,19 @@ struct ErrSlot {
     } while (0)
 
 // The body of every *_kernel_times: the first min(cap, n) names and values.
+// A second call with at = what the first returned appends its stages as far
+// as cap still allows.  Returns the entries written so far.
 inline int copy_times(const char *const *stage, const float *times, int n, const char **names,
-                      float *ms, int cap)
+                      float *ms, int cap, int at = 0)
 {
-    const int k = std::max(0, std::min(cap, n));
+    const int k = std::max(0, std::min(cap - at, n));
     for (int i = 0; i < k; ++i) {
         if (names)
-            names[i] = stage[i];
+            names[at + i] = stage[i];
         if (ms)
-            ms[i] = times[i];
+            ms[at + i] = times[i];
     }
-    return k;
+    return at + k;
 }
 
 // The stage times of a component without a handle: one thread_local per
@@ -96,6 +138,24 @@ template <int N> hipError_t ensure_events(hipEvent_t (&ev)[N])
         if (!e && err == hipSuccess)
             err = hipEventCreate(&e);
     return err;
+}
+
+// The events of a handle that only order streams: no timestamps taken.
+template <size_t N> hipError_t create_fences(std::array<hipEvent_t *, N> evs)
+{
+    hipError_t err = hipSuccess;
+    for (hipEvent_t *e : evs)
+        if (err == hipSuccess)
+            err = hipEventCreateWithFlags(e, hipEventDisableTiming);
+    return err;
+}
+
+// Destroy an event that may still be null (a create that failed part-way).
+inline void destroy_event(hipEvent_t &e)
+{
+    if (e)
+        (void)hipEventDestroy(e);
+    e = nullptr;
 }
 
 // The context of a component that keeps one table per device: the table and
@@ -246,8 +306,7 @@ template <int N> struct StageHandle {
         for (DevBuf *b : bufs)
             b->release();
         for (hipEvent_t &e : ev)
-            if (e)
-                (void)hipEventDestroy(e);
+            destroy_event(e);
         if (s)
             (void)hipStreamDestroy(s);
     }

@@ -8,7 +8,9 @@ the stream header on edge geometries; md5_cpu.h against the byte-wise MD5;
 atg_host_gather against memcpy; the encoder service client against fake
 services (mismatched frame counts and sizes, oversized byte counts and error
 text, a mute service), guard words past the caller's buffers; the *_host
-entries of the handle-less components refused on device -1.  Any ASan
+entries of the handle-less components refused on device -1; the creates of
+the two FLAC handles refused on device -1, on device 0 without a GPU and with
+out == NULL, *out left null.  Any ASan
 report or failed check fails the test; skipped when the probe is not built.
 The GPU-side replay of the bench sequence is tools/teardown_probe.cpp.
 """
@@ -32,4 +34,4 @@ def test_host_code_clean_under_asan():
     assert line["failures"] == 0
     assert line["flac_metadata_calls"] > 10000 and line["alac_info_calls"] > 1000
     assert line["service_cases"] == 6
-    assert line["host_refusals"] == 9
+    assert line["host_refusals"] == 15

@@ -17,7 +17,9 @@
 //     caller's buffers (guard words);
 //   * every *_host entry of the components without a handle, sound arguments
 //     on device -1: refused by the shared prelude (host_common.h), with the
-//     scoped staging allocations left empty.
+//     scoped staging allocations left empty;
+//   * atg_engine_create_ex / atg_decoder_create on device -1, on device 0
+//     and with out == NULL: refused with *out null.
 // Prints one JSON line; exit status 0 when every check passed.
 #include "../include/atgpu.h"
 #include "../python-audio-tools_amd/csrc/md5_cpu.h"
@@ -375,7 +377,30 @@ static int host_refusals_check()
     n += refused(atg_pcm_apply_gain_host(-1, pcm.data(), out.data(), 32, 2, 16, 0.5, 4096, dither,
                                          8, 0),
                  atg_pcm_convert_last_error());
-    return n;
+
+    // the two FLAC handles: a create that is refused leaves *out null and
+    // nothing behind; device 0 is refused where there is no GPU and opens
+    // (and is closed again) where there is one
+    for (int device : {-1, 0}) {
+        atg_engine *e = (atg_engine *)&n;
+        const atg_status se = atg_engine_create_ex(device, 0, &e);
+        if (se == ATG_OK && device == 0)
+            atg_engine_destroy(e);
+        else
+            CHECK(e == nullptr && refused(se, atg_last_error()));
+        atg_decoder *d = (atg_decoder *)&n;
+        const atg_status sd = atg_decoder_create(device, &d);
+        if (sd == ATG_OK && device == 0)
+            atg_decoder_destroy(d);
+        else
+            CHECK(d == nullptr && refused(sd, atg_decoder_last_error()));
+        n += 2;
+    }
+    CHECK(atg_engine_create_ex(0, 0, nullptr) == ATG_ERR_INVALID &&
+          !std::strcmp(atg_last_error(), "out is NULL"));
+    CHECK(atg_decoder_create(0, nullptr) == ATG_ERR_INVALID &&
+          !std::strcmp(atg_decoder_last_error(), "out is NULL"));
+    return n + 2;
 }
 
 int main(int argc, char **argv)
