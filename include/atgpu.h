@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ATG_ABI_VERSION 10
+#define ATG_ABI_VERSION 11
 
 typedef enum {
     ATG_OK = 0,
@@ -1900,6 +1900,8 @@ int atg_shn_decoder_kernel_times(atg_shn_decoder *dec, const char **names, float
 #include "atgpu_tensor.h"
 /* the dither bits of a batch conversion, made on the device */
 #include "atgpu_dither.h"
+/* the frame starts inside ranges of FLAC frame data */
+#include "atgpu_flac_index.h"
 /* test probes into the encoder's kernels */
 #include "atgpu_probe.h"
 #endif

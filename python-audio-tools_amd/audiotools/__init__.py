@@ -19,6 +19,9 @@ find the same names with the same meaning:
   audiotools.convert_pcm_batch .. PCMConverter for a batch of numpy tracks
   audiotools.DeviceDither ....... dither= of the batch paths: the bits made on
                                   the device, a seeded stream per track
+  audiotools.decode_windows_batch any span of each file of a batch without
+                                  the rest: only the covering bytes uploaded,
+                                  only its units decoded (windows.py)
   audiotools.load_batch / save_flac_batch / save_batch / pcm_to_tensor /
   tensor_to_pcm
                                   decoded batches as PyTorch tensors and back
@@ -614,6 +617,7 @@ from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa:
                        find_offset_batch, compare_pcm_batch)
 from .pcmconverter import DeviceDither, convert_pcm_batch  # noqa: E402,F401
 from .convert import convert_files_batch  # noqa: E402,F401
+from .windows import decode_windows_batch  # noqa: E402,F401
 
 # the tensor interface (tensors.py) imports torch: its names are looked up on
 # first use, so importing the package does not import torch

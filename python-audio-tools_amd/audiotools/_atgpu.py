@@ -822,6 +822,29 @@ DITHER_SIGNATURES = {
     "atg_dither_kernel_times": _THREAD_TIMES,
 }
 
+# ---- FLAC frame index (include/atgpu_flac_index.h, included by atgpu.h after atgpu_dither.h)
+class FlacIndexRange(ctypes.Structure):
+    """atg_flac_index_range: a byte range of frame data and its STREAMINFO"""
+    _fields_ = [("data_offset", c_u64), ("data_bytes", c_u64), ("sample_rate", c_u32),
+                ("channels", c_u32), ("bits_per_sample", c_u32), ("max_block_size", c_u32),
+                ("min_block_size", c_u32), ("reserved", c_u32)]
+
+
+class FlacIndexEntry(ctypes.Structure):
+    """atg_flac_index_entry: one listed frame start"""
+    _fields_ = [("byte_offset", c_u64), ("first_sample", c_u64), ("block_size", c_u32),
+                ("range", c_u32)]
+
+
+_FLAC_INDEX = (ptr(FlacIndexRange), c_u32, ptr(FlacIndexEntry), c_u64, P64)
+# the prototypes of include/atgpu_flac_index.h, applied by load_library() as well
+FLAC_INDEX_SIGNATURES = {
+    "atg_flac_index_last_error": _LAST_ERROR,
+    "atg_flac_index_device": (c_int, (P, c_u64) + _FLAC_INDEX + (P,)),
+    "atg_flac_index_host": (c_int, (c_int, P, c_u64) + _FLAC_INDEX),
+    "atg_flac_index_kernel_times": _THREAD_TIMES,
+}
+
 # ---- test probes (include/atgpu_probe.h, included by atgpu.h last)
 PROBE_SIGNATURES = {
     # engine, options, pcm, format, tracks, n, channels, bits, sums, cap, window_n, window
@@ -847,6 +870,7 @@ def load_library():
                                           list(MLP_SIGNATURES.items()) +
                                           list(TENSOR_SIGNATURES.items()) +
                                           list(DITHER_SIGNATURES.items()) +
+                                          list(FLAC_INDEX_SIGNATURES.items()) +
                                           list(PROBE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -2662,6 +2686,59 @@ def dither_fill_device(runs, seed, d_out, out_cap, stream=None):
     _check(lib, lib.atg_dither_fill_device(
         arr, len(runs), int(seed), ctypes.c_void_p(d_out) if d_out else None, out_cap,
         ctypes.c_void_p(stream) if stream else None), "dither")
+
+
+def flac_index_range(offset, nbytes, si):
+    """FlacIndexRange over `nbytes` of frame data at `offset` of the buffer,
+    for a stream with the StreamInfo `si`"""
+    return FlacIndexRange(offset, nbytes, si.sample_rate, si.channels, si.bits_per_sample,
+                          si.max_block_size, si.min_block_size, 0)
+
+
+def _flac_index_call(call, ranges, cap):
+    """atg_flac_index_device / _host through `call(lib, ranges, n, entries,
+    cap, count)` -> [(range, byte_offset, first_sample, block_size)] sorted;
+    a capacity that proves too small is answered by one call with the
+    count the first reported"""
+    lib = load_library()
+    n = len(ranges)
+    arr = (FlacIndexRange * max(1, n))(*ranges)
+    count = c_u64()
+    while True:
+        ents = (FlacIndexEntry * max(1, cap))()
+        st = call(lib, arr, n, ents, cap, ctypes.byref(count))
+        if st != ATG_ERR_CAPACITY:
+            break
+        cap = count.value
+    _check(lib, st, "flac_index")
+    rows = np.frombuffer(ents, dtype=FLAC_INDEX_ENTRY_DTYPE, count=count.value)
+    return [(int(r), int(o), int(s), int(b)) for o, s, b, r in rows.tolist()]
+
+
+FLAC_INDEX_ENTRY_DTYPE = np.dtype([("byte_offset", "<u8"), ("first_sample", "<u8"),
+                                   ("block_size", "<u4"), ("range", "<u4")])
+
+
+def flac_index_device(d_data, nbytes, ranges, cap=None):
+    """the frame starts inside `ranges` (FlacIndexRange) of a device buffer
+    -> [(range, byte_offset from the range's start, first_sample, block_size)]"""
+    cap = sum(r.data_bytes for r in ranges) // 1024 + 64 if cap is None else cap
+    return _flac_index_call(lambda lib, arr, n, ents, cap, count: lib.atg_flac_index_device(
+        ctypes.c_void_p(d_data), nbytes, arr, n, ents, cap, count, None), ranges, cap)
+
+
+def flac_index_host(data, ranges, cap=None, device=None):
+    """flac_index_device over bytes in host memory, staged for the call"""
+    data = bytes(data)
+    cap = sum(r.data_bytes for r in ranges) // 1024 + 64 if cap is None else cap
+    dev = default_device() if device is None else device
+    return _flac_index_call(lambda lib, arr, n, ents, cap, count: lib.atg_flac_index_host(
+        dev, data, len(data), arr, n, ents, cap, count), ranges, cap)
+
+
+def flac_index_kernel_times():
+    """{stage: ms} of this thread's last frame index call"""
+    return _thread_times(load_library().atg_flac_index_kernel_times, 3)
 
 
 def dither_tile_blocks():

@@ -116,6 +116,30 @@ def decode_flac_batch(images):
     return out
 
 
+def flac_frame_index_batch(images):
+    """the frame starts of a list of .flac images (bytes), found on the GPU
+    in one call (flac_index.hip): a FLAC stream carries no per-frame table.
+    -> per image [(byte offset from the first frame, first_sample,
+    block_size)], ascending.  A start is listed when its header is sound,
+    agrees with STREAMINFO, and the bytes up to a later header whose number
+    follows (or up to the stream's end) pass CRC-16: starts are promised,
+    lengths are not, and the samples themselves are not decoded."""
+    infos, bodies = [], []
+    for img in images:
+        rc, si, _ = _atgpu.read_metadata(img)
+        if rc:
+            raise _metadata_error(rc)
+        infos.append(si)
+        bodies.append(bytes(img[si.frames_offset:]))
+    data, spans = _atgpu.pack_images(bodies)
+    ranges = [_atgpu.flac_index_range(offset, nbytes, si)
+              for (offset, nbytes), si in zip(spans, infos)]
+    out = [[] for _ in images]
+    for r, offset, first_sample, block_size in _atgpu.flac_index_host(data, ranges):
+        out[r].append((offset, first_sample, block_size))
+    return out
+
+
 def pcm_md5(samples, bits_per_sample):
     """MD5 of FrameList.to_bytes(False, True) for int32 samples (test aid)"""
     a = np.asarray(samples, dtype=np.int32)

@@ -173,7 +173,8 @@ def _name(source):
 
 
 def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
-               bits_per_sample=None, dtype=torch.float32, dither=None, frames=None):
+               bits_per_sample=None, dtype=torch.float32, dither=None, frames=None,
+               start=None, length=None):
     """sources (filenames or byte images of FLAC, Ogg FLAC, ALAC, True Audio,
     WavPack, Shorten, WAV, AIFF or Sun AU) -> AudioBatch(audio, lengths,
     sample_rates, bits_per_sample, channel_masks, errors).  Every format is
@@ -185,6 +186,12 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
     channel; the PCM is never on the host.  sample_rates, bits_per_sample and
     channel_masks are lists with one entry per source: without a target the
     sources may differ in them.
+    start, length (an int or one per row, in PCM frames at the source's rate,
+    before any conversion): when either is given, row k is the window [start,
+    start + length) of its source, decoded by decode_windows_batch -- only
+    the bytes that cover it uploaded, only its units decoded, the stream's
+    MD5 unchecked; a window that starts at or past the end is a row of zeros
+    with length 0 and no error.
     A source that cannot be opened or decoded stops nothing: its row is all
     zeros, its length and its list entries are 0 and errors[k] is the
     DecodingError (None for a good row).
@@ -194,6 +201,9 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
     sources = list(sources)
     n = len(sources)
     _dtype_code(dtype)
+    if start is not None or length is not None:
+        return _load_windows(sources, 0 if start is None else start, length, sample_rate,
+                             channels, channel_mask, bits_per_sample, dtype, dither, frames)
     batch = _Batch()
     errors, plans, index = [None] * n, [None] * n, [None] * n
     for k, source in enumerate(sources):
@@ -241,6 +251,52 @@ def load_batch(sources, sample_rate=None, channels=None, channel_mask=None,
         for d in free:
             eng.device_free(d)
         batch.close()
+    return AudioBatch(audio, lengths,
+                      [p.sample_rate if p else 0 for p in plans],
+                      [p.bits_per_sample if p else 0 for p in plans],
+                      [p.channel_mask if p else 0 for p in plans], errors)
+
+
+def _load_windows(sources, start, length, sample_rate, channels, channel_mask, bits_per_sample,
+                  dtype, dither, frames):
+    """load_batch over one window per source: the rows of decode_windows_batch
+    through the same chain and the same tensor kernel"""
+    from .windows import decode_windows_batch
+    n = len(sources)
+    wins = decode_windows_batch(sources, start, length)
+    eng = _atgpu.engine()
+    free = []
+    try:
+        errors = list(wins.errors)
+        plans = [None if errors[k] is not None else
+                 plan_target((wins.channels[k], wins.channel_mask[k], wins.bits_per_sample[k],
+                              wins.sample_rate[k]),
+                             sample_rate, channels, channel_mask, bits_per_sample)
+                 for k in range(n)]
+        counts = sorted(set(p.channels for p in plans if p is not None))
+        if len(counts) > 1:
+            raise ValueError("the sources have %s channels after conversion: pass channels= "
+                             "to give every row one count" % ", ".join(map(str, counts)))
+        device = _device()
+        good = [k for k in range(n) if plans[k] is not None]
+        # an empty window has nothing to convert: it stays a row of length 0
+        full = [k for k in good if wins.rows[k].frames]
+        done, free = run_chain_device([wins.rows[k] for k in full], [plans[k] for k in full],
+                                      dither, streams=full)
+        if good:
+            ch = counts[0]
+            rows = [(DevicePcm(None, _atgpu.PCM_S32, 0, 0), ch, 16)] * n
+            for k, d in zip(full, done):
+                rows[k] = (d, ch, plans[k].bits_per_sample)
+            audio, lengths = pcm_to_tensor(rows, dtype, frames)
+        else:
+            audio = torch.zeros((n, counts[0] if counts else 0, frames or 0), dtype=dtype,
+                                device=device)
+            lengths = torch.zeros(n, dtype=torch.int64)
+    finally:
+        for d in free:
+            eng.device_free(d)
+        wins.close()
     return AudioBatch(audio, lengths,
                       [p.sample_rate if p else 0 for p in plans],
                       [p.bits_per_sample if p else 0 for p in plans],
