@@ -22,6 +22,14 @@ find the same names with the same meaning:
   audiotools.decode_windows_batch any span of each file of a batch without
                                   the rest: only the covering bytes uploaded,
                                   only its units decoded (windows.py)
+  audiotools.Sheet / SheetTrack / SheetIndex / read_sheet, audiotools.cue,
+  audiotools.toc ................ reference audiotools/__init__.py:4265-4479,
+                                  cue.py, toc.py (sheets.py, cue.py, toc.py)
+  audiotools.PCMCat / LimitedPCMReader / pcm_split
+                                  reference audiotools/__init__.py:2487-2726
+  audiotools.split_image_batch .. tracksplit for a batch of CD images: each
+                                  decoded once, its tracks cut on the device
+  audiotools.join_tracks_batch .. trackcat for a batch of albums (cdimage.py)
   audiotools.load_batch / save_flac_batch / save_batch / pcm_to_tensor /
   tensor_to_pcm
                                   decoded batches as PyTorch tensors and back
@@ -152,6 +160,98 @@ class BufferedPCMReader(object):
 
     def read_closed(self, pcm_frames):
         raise ValueError()
+
+
+class PCMCat(object):
+    """several PCMReaders of one sample rate, channel count and sample size
+    read as one stream, each to its end (reference
+    audiotools/__init__.py:2487-2558); the channel mask is the first one's"""
+
+    def __init__(self, pcmreaders):
+        self.pcmreaders = list(pcmreaders)
+        if len(self.pcmreaders) == 0:
+            raise ValueError("you must have at least 1 PCMReader")
+        if len(set(r.sample_rate for r in self.pcmreaders)) != 1:
+            raise ValueError("all audio files must have the same sample rate")
+        if len(set(r.channels for r in self.pcmreaders)) != 1:
+            raise ValueError("all audio files must have the same channel count")
+        if len(set(r.bits_per_sample for r in self.pcmreaders)) != 1:
+            raise ValueError("all audio files must have the same bits per sample")
+        first = self.pcmreaders[0]
+        self.sample_rate = first.sample_rate
+        self.channels = first.channels
+        self.channel_mask = first.channel_mask
+        self.bits_per_sample = first.bits_per_sample
+        self._at = 0
+
+    def read(self, pcm_frames):
+        # an empty FrameList ends a reader: on to the next, and past the last
+        # one every read gives an empty FrameList
+        while self._at < len(self.pcmreaders):
+            framelist = self.pcmreaders[self._at].read(pcm_frames)
+            if len(framelist) > 0:
+                return framelist
+            self._at += 1
+        return pcm.empty_framelist(self.channels, self.bits_per_sample)
+
+    def read_closed(self, pcm_frames):
+        raise ValueError()
+
+    def close(self):
+        self.read = self.read_closed
+        for reader in self.pcmreaders:
+            reader.close()
+
+
+class LimitedPCMReader(object):
+    """the next total_pcm_frames frames of a BufferedPCMReader, which stays
+    open for whoever reads on behind them (reference
+    audiotools/__init__.py:2656-2686)"""
+
+    def __init__(self, buffered_pcmreader, total_pcm_frames):
+        self.pcmreader = buffered_pcmreader
+        self.total_pcm_frames = total_pcm_frames
+        self.sample_rate = self.pcmreader.sample_rate
+        self.channels = self.pcmreader.channels
+        self.channel_mask = self.pcmreader.channel_mask
+        self.bits_per_sample = self.pcmreader.bits_per_sample
+
+    def read(self, pcm_frames):
+        if self.total_pcm_frames > 0:
+            frame = self.pcmreader.read(min(pcm_frames, self.total_pcm_frames))
+            self.total_pcm_frames -= frame.frames
+            return frame
+        return pcm.empty_framelist(self.channels, self.bits_per_sample)
+
+    def read_closed(self, pcm_frames):
+        raise ValueError()
+
+    def close(self):
+        self.read = self.read_closed
+
+
+def pcm_split(reader, pcm_lengths):
+    """yields one PCMReader per length of pcm_lengths (PCM frames), each
+    over the next that many frames of `reader` and with its parameters;
+    `reader` is closed once the last has been handed out (reference
+    audiotools/__init__.py:2689-2726).  A long piece is kept in a temporary
+    file, a short one in memory."""
+    import io
+    import tempfile
+    full = BufferedPCMReader(reader)
+    for pcm_length in pcm_lengths:
+        if pcm_length > FRAMELIST_SIZE * 10:
+            sub_file = tempfile.TemporaryFile()
+            left = pcm_length
+            while left > 0:
+                sub_file.write(full.read(min(left, FRAMELIST_SIZE)).to_bytes(False, True))
+                left -= min(left, FRAMELIST_SIZE)
+            sub_file.seek(0, 0)
+        else:
+            sub_file = io.BytesIO(full.read(pcm_length).to_bytes(False, True))
+        yield PCMReader(sub_file, reader.sample_rate, reader.channels, reader.channel_mask,
+                        reader.bits_per_sample)
+    full.close()
 
 
 class FrameListReader(object):
@@ -618,6 +718,10 @@ from .trackcmp import (PCMReaderHead, PCMReaderDeHead, PCMReaderWindow,  # noqa:
 from .pcmconverter import DeviceDither, convert_pcm_batch  # noqa: E402,F401
 from .convert import convert_files_batch  # noqa: E402,F401
 from .windows import decode_windows_batch  # noqa: E402,F401
+from .sheets import (SheetException, Sheet, SheetTrack, SheetIndex, read_sheet,  # noqa: E402,F401
+                     parse_timestamp, build_timestamp)
+from . import cue, toc  # noqa: E402,F401
+from .cdimage import SplitResult, split_image_batch, join_tracks_batch  # noqa: E402,F401
 
 # the tensor interface (tensors.py) imports torch: its names are looked up on
 # first use, so importing the package does not import torch

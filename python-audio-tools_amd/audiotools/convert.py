@@ -42,7 +42,8 @@ def _frame_offsets(image, total_frames, interval, block_size):
 
 
 def convert_files_batch(sources, targets, sample_rate=None, channels=None, channel_mask=None,
-                        bits_per_sample=None, compression=None, dither=None, target_types=None):
+                        bits_per_sample=None, compression=None, dither=None, target_types=None,
+                        starts=None, lengths=None):
     """sources[k] (a filename or a bytes image of any supported format) ->
     the file targets[k], converted to the target parameters as PCMConverter
     converts (None keeps each source's own value).  target_types: None for
@@ -67,13 +68,30 @@ def convert_files_batch(sources, targets, sample_rate=None, channels=None, chann
     parameters its target type cannot hold gets the exception that type's
     from_pcm raises, before any GPU work for it.  ValueError, before any GPU
     work, for a target that PCMConverter refuses, an unknown target type and
-    lists of the wrong length."""
+    lists of the wrong length.
+
+    starts, lengths: with either given, row k converts only the window
+    [starts[k], starts[k] + lengths[k]) of sources[k] -- each one value or
+    one per source, in PCM frames at the source's rate, before conversion; a
+    start of None is 0 and a length of None runs to the end.  The rows come
+    from decode_windows_batch's planner and decoder (only the covering bytes
+    of a source go up, once for all the rows that name it, and the stream's
+    MD5 is not checked) and go into the chain as they are.  A window is cut
+    to the stream as decode_windows_batch cuts it -- it is not padded with
+    silence as PCMReaderWindow pads one, so the file is the one from_pcm
+    writes over PCMReaderWindow of the cut window -- and a negative value
+    raises ValueError before any GPU work.  With both None the whole files
+    are converted as before, their MD5 checked."""
     sources, targets = list(sources), list(targets)
     if len(sources) != len(targets):
         raise ValueError("sources and targets differ in length")
     classes = ([FlacAudio] * len(targets) if target_types is None
                else resolve_types(target_types, targets))
     modes = resolve_compression(compression, classes)
+    if starts is not None or lengths is not None:
+        return _convert_windows(sources, targets, classes, modes, 0 if starts is None else starts,
+                                lengths, (sample_rate, channels, channel_mask, bits_per_sample),
+                                dither)
     batch = _Batch()
     results = [None] * len(sources)
     jobs = []  # (k, file index, ChainPlan, what prepare() returned)
@@ -116,6 +134,67 @@ def convert_files_batch(sources, targets, sample_rate=None, channels=None, chann
             [plan for _, _, plan, _ in good], dither, streams=[k for k, _, _, _ in good])
         tracks = []
         for (k, _, plan, ready), d in zip(good, done):
+            if classes[k] in (ShortenAudio, WaveAudio):
+                # their headers hold the length: made for the frames that came
+                try:
+                    ready = prepare(classes[k], targets[k], plan.channels, plan.channel_mask,
+                                    plan.bits_per_sample, plan.sample_rate, d.frames)
+                except (EncodingError, ValueError) as err:
+                    results[k] = err
+                    continue
+            tracks.append(Track(k, targets[k], classes[k], modes[k], d, plan.channels,
+                                plan.bits_per_sample, plan.sample_rate, plan.channel_mask, ready))
+        for k, r in write_tracks(tracks).items():
+            results[k] = r
+        return results
+    finally:
+        for d in free:
+            eng.device_free(d)
+        batch.close()
+
+
+def _convert_windows(sources, targets, classes, modes, starts, lengths, want, dither):
+    """convert_files_batch over one window of each source"""
+    from .windows import decode_rows, plan_rows
+    batch, rows, headers = plan_rows(sources, starts, lengths)
+    results = list(batch.errors)
+    keep = dict((r.k, r.plan.keep) for r in rows)
+    jobs = []  # (k, ChainPlan, what prepare() returned)
+    for k, h in enumerate(headers):
+        if h is None:
+            continue
+        plan = plan_target((h.channels, h.channel_mask, h.bits_per_sample, h.sample_rate), *want)
+        frames = keep.get(k, 0)
+        if plan.in_rate != plan.sample_rate and frames:
+            frames = _atgpu.resample_output_frames(frames, plan.channels, plan.in_rate,
+                                                   plan.sample_rate)
+        try:
+            ready = prepare(classes[k], targets[k], plan.channels, plan.channel_mask,
+                            plan.bits_per_sample, plan.sample_rate, frames)
+        except (EncodingError, ValueError) as err:
+            results[k] = err
+            continue
+        jobs.append((k, plan, ready))
+    # rows whose target is refused are not decoded
+    wanted = set(k for k, _, _ in jobs)
+    if not jobs:
+        return results
+    free = []
+    eng = _atgpu.engine()
+    try:
+        decode_rows(batch, [r for r in rows if r.k in wanted])
+        good = []
+        for job in jobs:
+            if batch.errors[job[0]] is None:
+                good.append(job)
+            else:
+                results[job[0]] = batch.errors[job[0]]
+        done, more = run_chain_device([batch.rows[k] for k, _, _ in good],
+                                      [plan for _, plan, _ in good], dither,
+                                      streams=[k for k, _, _ in good])
+        free.extend(more)
+        tracks = []
+        for (k, plan, ready), d in zip(good, done):
             if classes[k] in (ShortenAudio, WaveAudio):
                 # their headers hold the length: made for the frames that came
                 try:

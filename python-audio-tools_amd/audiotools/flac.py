@@ -197,7 +197,14 @@ def finish_image(data, offsets, channels, bits_per_sample, channel_mask, interva
                 blocks[i] = (t, _set_comment(body, u"WAVEFORMATEXTENSIBLE_CHANNEL_MASK",
                                              u"0x%.4X" % channel_mask))
                 break
-    # update_metadata (flac.py:1389-1427): absorb the growth in PADDING
+    _absorb(blocks, old_len)
+    # with too little padding the metadata grows and the frames move
+    return _build(blocks) + data[frames_at:]
+
+
+def _absorb(blocks, old_len):
+    """update_metadata (flac.py:1389-1427): the growth of the blocks over
+    `old_len` bytes taken out of the PADDING blocks, where they hold it"""
     new_len = sum(4 + len(b) for _, b in blocks)
     delta = new_len - old_len
     pads = [i for i, (t, _) in enumerate(blocks) if t == PADDING]
@@ -213,7 +220,70 @@ def finish_image(data, offsets, channels, bits_per_sample, channel_mask, interva
                 delta = 0
             else:
                 break
-    # with too little padding the metadata grows and the frames move
+
+
+# ------------------------------------------------------- the CUESHEET block
+# header: 128-byte catalog, 64-bit lead-in, 1 bit CD flag + 2071 pad bits
+# (259 bytes), 8-bit track count; track: 64-bit offset, 8-bit number, 12-byte
+# ISRC, 2 flag bits + 110 pad bits (14 bytes), 8-bit index count; index:
+# 64-bit offset, 8-bit number, 24 pad bits (reference flac.py:739-1020)
+LEAD_OUT = 170
+
+
+def cuesheet_block(sheet, total_pcm_frames, sample_rate, is_cdda=True):
+    """the CUESHEET block body of a Sheet (Flac_CUESHEET.converted): every
+    index offset times the rate cut to an integer on its own, a track's
+    offset its first index and its indexes counted from there, a lead-out
+    track 170 at total_pcm_frames, a lead-in of 2 seconds"""
+    tracks = []
+    for track in sheet.tracks():
+        at = [int(i.offset() * sample_rate) for i in track.indexes()]
+        numbers = [i.number() for i in track.indexes()]
+        isrc = b"" if track.ISRC() is None else track.ISRC().encode("ascii")
+        tracks.append((at[0] if at else 0, track.number(), isrc, 0 if track.audio() else 1,
+                       [(a - at[0], n) for a, n in zip(at, numbers)]))
+    tracks.append((total_pcm_frames, LEAD_OUT, b"", 0, []))
+    catalog = b"" if sheet.catalog() is None else sheet.catalog().encode("ascii")
+    out = [struct.pack(">128sQ259sB", catalog, 2 * sample_rate,
+                       bytes([0x80 if is_cdda else 0]), len(tracks))]
+    for offset, number, isrc, kind, indexes in tracks:
+        out.append(struct.pack(">QB12s14sB", offset, number, isrc, bytes([kind << 7]),
+                               len(indexes)))
+        out += [struct.pack(">QB3x", o, n) for o, n in indexes]
+    return b"".join(out)
+
+
+def cuesheet_sheet(body, sample_rate):
+    """a CUESHEET block body -> its Sheet (FlacAudio.get_cuesheet,
+    flac.py:1629-1672): the lead-out track dropped, catalog and ISRC without
+    their NUL padding and None when empty"""
+    from fractions import Fraction
+    from .sheets import Sheet, SheetIndex, SheetTrack
+    catalog, _, _, n_tracks = struct.unpack_from(">128sQ259sB", body, 0)
+    pos, tracks = 396, []
+    for _ in range(n_tracks):
+        offset, number, isrc, flags, n_indexes = struct.unpack_from(">QB12s14sB", body, pos)
+        pos += 36
+        indexes = []
+        for _ in range(n_indexes):
+            o, n = struct.unpack_from(">QB3x", body, pos)
+            pos += 12
+            indexes.append(SheetIndex(n, Fraction(offset + o, sample_rate)))
+        if number != LEAD_OUT:
+            isrc = isrc.strip(b"\0").decode("ascii", "replace")
+            tracks.append(SheetTrack(number, indexes, flags[0] >> 7 == 0, isrc or None))
+    catalog = catalog.rstrip(b"\0").decode("ascii", "replace")
+    return Sheet(tracks, catalog or None)
+
+
+def embed_cuesheet(data, body):
+    """a .flac image with the CUESHEET block `body` added (in place of one
+    it has): placed by add_block's order, the growth taken out of PADDING as
+    finish_image takes it"""
+    blocks, frames_at = _blocks(data)
+    blocks = [b for b in blocks if b[0] != CUESHEET]
+    _add_block(blocks, (CUESHEET, body))
+    _absorb(blocks, frames_at - 4)
     return _build(blocks) + data[frames_at:]
 
 
@@ -310,6 +380,41 @@ class FlacAudio(AudioFile):
 
     def total_frames(self):
         return self._si.total_samples
+
+    def set_cuesheet(self, cuesheet):
+        """the Sheet written into the file as its CUESHEET block
+        (flac.py:1611-1627); None changes nothing.  The block takes its place
+        by add_block's order and its bytes come out of PADDING, the frames
+        staying where they are; with too little PADDING the file is
+        rewritten and the frames move.  A CUESHEET block the file already
+        has is replaced (the reference adds a second one, which FLAC does
+        not allow).  IOError if the file cannot be rewritten."""
+        if cuesheet is None:
+            return
+        with open(self.filename, "rb") as f:
+            data = f.read()
+        at = self.__stream_offset
+        out = embed_cuesheet(data[at:], cuesheet_block(
+            cuesheet, self.total_frames(), self.sample_rate(),
+            self.sample_rate() == 44100 and self.channels() == 2 and
+            self.bits_per_sample() == 16))
+        with open(self.filename, "wb") as f:
+            f.write(data[:at] + out)
+
+    def get_cuesheet(self):
+        """the Sheet of the file's CUESHEET block, None without one
+        (flac.py:1629-1672)"""
+        with open(self.filename, "rb") as f:
+            f.seek(self.__stream_offset + 4)
+            while True:  # the metadata alone, not the frames behind it
+                h = f.read(4)
+                if len(h) < 4:
+                    return None
+                body = f.read(int.from_bytes(h[1:], "big"))
+                if h[0] & 0x7F == CUESHEET:
+                    return cuesheet_sheet(body, self.sample_rate())
+                if h[0] & 0x80:
+                    return None
 
     def to_pcm(self):
         """FlacDecoder over the stream from the "fLaC" marker on; if it

@@ -381,6 +381,16 @@ def decode_windows_batch(sources, starts, lengths=None):
     damage outside the window is not an error, damage inside it is that row's
     DecodingError and stops nothing.  The stream's MD5 is never checked for a
     window, not even for one that spans the whole stream."""
+    out, rows, _ = plan_rows(sources, starts, lengths)
+    return decode_rows(out, rows)
+
+
+def plan_rows(sources, starts, lengths=None):
+    """the host half of decode_windows_batch: every distinct source read and
+    opened once and every row planned -> (WindowBatch with the rows'
+    parameters, the errors of sources that cannot be opened and the empty
+    rows filled in; the rows still to decode; the _Header (or None) of every
+    row).  No GPU work; ValueError as decode_windows_batch raises it."""
     from . import DecodingError
     from .pcmconverter import DevicePcm
     sources = list(sources)
@@ -393,7 +403,7 @@ def decode_windows_batch(sources, starts, lengths=None):
     out = WindowBatch(n)
     # every distinct source read and opened once
     index, headers, points, tables = {}, [], [], []
-    rows = []
+    rows, row_headers = [], []
     for k, source in enumerate(sources):
         key = source if isinstance(source, str) else id(source)
         if key not in index:
@@ -404,6 +414,7 @@ def decode_windows_batch(sources, starts, lengths=None):
             tables.append(None)
         i = index[key]
         h = headers[i]
+        row_headers.append(h)
         if h is None:
             out.errors[k] = DecodingError("%s cannot be opened as audio" % _name(source))
             continue
@@ -421,18 +432,26 @@ def decode_windows_batch(sources, starts, lengths=None):
             out.rows[k] = DevicePcm(None, _atgpu.PCM_S32, 0, 0)
             continue
         rows.append(r)
+    return out, rows, row_headers
+
+
+def decode_rows(out, rows):
+    """the device half: plan_rows' WindowBatch and rows -> the WindowBatch decoded"""
+    from . import DecodingError
+    from .pcmconverter import DevicePcm
     if not rows:
         return out
     eng = _atgpu.engine()
     try:
-        _run(out, rows, headers, eng, DecodingError, DevicePcm)
+        _run(out, rows, eng, DecodingError, DevicePcm)
     except Exception:
         out.close()
         raise
     return out
 
 
-def _run(out, rows, headers, eng, DecodingError, DevicePcm):
+def _run(out, rows, eng, DecodingError, DevicePcm):
+    headers = {r.src: r.header for r in rows}
     # the union of every source's bytes, 16-byte aligned pieces of one buffer
     pieces, pos = {}, 0
     for i in sorted(set(r.src for r in rows)):
